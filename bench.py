@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycle MLUPS + achieved HBM GB/s vs roofline (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input: ONE run of the
 reference program's timed window (src/MG_solver_CPU.cpp:156..429) over a generated
@@ -10,9 +10,15 @@ Gauss-Seidel solve, prolongation, correction -- from the state right after getSo
 inputs resident in HBM.  At --gpus 1 the workload is the configuration the metric is
 quoted on: N = 8192^2 fp64.  Prints ONE JSON line (see the driver's contract).
 
+A plain run does only what the headline needs: set up, warm up, time exactly K steps, print the line.
+--full adds everything else the line used to carry: the legs beside the headline (strong-scaling bases,
+hipGraph replay), the per-kernel live hipEvent profile and roofline of the timed steps, the single-sweep
+roofline, the device copy rate and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as .npy files.
+
 --gpus N > 1 without a torchrun environment: this process starts the N ranks itself (a child
 `python -m torch.distributed.run`, before anything here touches the GPU) and relays rank 0's line.
-Every line carries two legs: `value` = weak scaling (8192^2 points per GPU, the headline) and
+`value` = weak scaling (8192^2 points per GPU, the headline); with --full the line also carries
 `strong_scaling` = the V-cycle at N = 16384^2 on the same GPUs (BASELINE.json configs[3]; the
 >= 6x target of north_star is quoted there), at N = 1 as the one-GPU base of that curve.
 """
@@ -233,7 +239,10 @@ def self_launch(args):
     return child.returncode if child.returncode != 0 else (0 if line else 1)
 
 
-def time_cycle(mg, plan, steps, warmup, profile_min_N=None, first=None):
+SETTLE_S = 0.3   # seconds of sustained untimed load before the headline's timed steps (time_cycle)
+
+
+def time_cycle(mg, plan, steps, warmup, profile_min_N=None, first=None, settle_s=0.0):
     """W untimed runs, then exactly K windows enqueued back to back on the engine's stream (a fixed-step cycle
     file needs no per-step host sync), bracketed by synchronisation; optional live hipEvent pairs.
     first: the result of the plan's first run when the caller made it earlier (pool, tables, code objects)."""
@@ -247,6 +256,15 @@ def time_cycle(mg, plan, steps, warmup, profile_min_N=None, first=None):
     for _ in range(warmup):
         plan.enqueue()
     mg.sync()
+    # then, however small W is, further untimed windows until SETTLE_S of sustained load lie behind (the load the
+    # --full legs put in front of the headline; without it a short W times the clock ramp)
+    time_cycle.settle_windows = 0
+    t = time.perf_counter()
+    while settle_s and time.perf_counter() - t < settle_s:
+        for _ in range(20):
+            plan.enqueue()
+        mg.sync()
+        time_cycle.settle_windows += 20
     r0 = plan.collect()
     assert r0["status"] == 0, r0
     if profile_min_N is not None:
@@ -262,6 +280,34 @@ def time_cycle(mg, plan, steps, warmup, profile_min_N=None, first=None):
     prof = mg.profile_end() if profile_min_N is not None else []
     assert r["status"] == 0, r
     return (t1 - t0) * 1e3 / steps, r, prof
+
+
+DUMP_GRID = 1024   # U_strided: at most about DUMP_GRID^2 points
+DUMP_ROWS = 32     # U_rows: whole rows picked with a fixed seed
+
+
+def dump_outputs(mg, result, mg_error, out_dir):
+    """--dump-outputs: the solution U of the last timed step (fp64, N x N, what a caller of the cycle path receives
+    in device memory), as a fixed sample that stays far below 64 MB at any N: U_strided.npy = every s-th row and column,
+    s = ceil(N / DUMP_GRID) (all of U up to N = DUMP_GRID); U_rows.npy = DUMP_ROWS whole rows at indices drawn with a
+    fixed seed (sorted); mg_error.npy = the analytic error of that U.  Only the sampled rows leave the device."""
+    import numpy as np
+    N, ptr = int(result["N"]), int(result["U_ptr"])
+
+    def rows(idx):
+        out = np.empty((len(idx), N))
+        for k, i in enumerate(idx):
+            assert 0 <= i < N
+            mg.lib().mg_download(out[k].ctypes.data, ptr + int(i) * N * 8, N)
+        mg.sync()   # (raises on an engine error)
+        return out
+
+    s = -(-N // DUMP_GRID)
+    picked = np.sort(np.random.default_rng(0).choice(N, size=min(N, DUMP_ROWS), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "U_strided.npy"), np.ascontiguousarray(rows(range(0, N, s))[:, ::s]))
+    np.save(os.path.join(out_dir, "U_rows.npy"), rows(picked))
+    np.save(os.path.join(out_dir, "mg_error.npy"), np.array([mg_error], dtype=np.float64))
 
 
 def main():
@@ -288,7 +334,14 @@ def main():
                          "(BASELINE.json configs[4]: fp32 smoothing / fp64 residual correction)")
     ap.add_argument("--force-slab", action="store_true",
                     help="run the row-slab/RCCL leg even with one rank (plumbing rehearsal on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs and figures beside the headline (strong-scaling bases, graph replay, per-kernel "
+                         "profile and roofline, single-sweep roofline, device copy rate, CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (a fixed sample of U, see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_slab or args.scaling == "strong"):
+        ap.error("--dump-outputs writes the output of the one-GPU weak-scaling headline (--gpus 1, no --force-slab, --scaling weak)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))  # nothing above has touched the GPU
@@ -333,7 +386,8 @@ def main():
     # says what preceded the timed region and how the first and the last window of this leg compare).
     pre_legs, windows_before = {}, 0
     # ---- strong-scaling base: the V-cycle of BASELINE.json configs[3] (N = 16384^2) on this one GPU ----
-    if not args.no_strong and args.cycle == "V" and N != STRONG_N:
+    # (--full only, or when --scaling strong makes it the line's `value`)
+    if (args.full or args.scaling == "strong") and not args.no_strong and args.cycle == "V" and N != STRONG_N:
         try:
             scyc = os.path.join(tmp, f"Vcycle_{STRONG_N}.txt")
             mg.write_vcycle_file(scyc, STRONG_N, args.n_min, nu, 1e-7)
@@ -352,7 +406,7 @@ def main():
             pre_legs["strong_scaling"] = {"error": str(exc)}
 
     # ---- the same one level up: N = 32768^2 fp64 (few windows: 10 ms each) ----
-    if not args.no_strong and not args.no_large and args.cycle == "V" and not args.mixed and N != LARGE_N:
+    if args.full and not args.no_strong and not args.no_large and args.cycle == "V" and not args.mixed and N != LARGE_N:
         try:
             lcyc = os.path.join(tmp, f"Vcycle_{LARGE_N}.txt")
             mg.write_vcycle_file(lcyc, LARGE_N, args.n_min, nu, 1e-7)
@@ -372,7 +426,7 @@ def main():
 
     # ---- the headline cycle file replayed from a hipGraph (MG_CYCLE_GRAPH): a leg of its own -- is the captured window
     # faster than the eager one? -- and, run last before the headline, 50 windows of the very workload that is timed next ----
-    if not args.no_strong and args.mode == "eager" and not args.mixed:
+    if args.full and not args.no_strong and args.mode == "eager" and not args.mixed:
         try:
             gplan = mg.CyclePlan(cyc, fused=True, graph=True, report=False, error=False)
             gsteps = 50
@@ -387,10 +441,15 @@ def main():
 
     lups *= refine   # a window of the refinement runs the cycle file `refine` times (fp32), joined by an fp64 residual + correction
     # ---- timed region: exactly K steps, bracketed by synchronisation on both sides ----
-    ms_per_step, r, prof = time_cycle(mg, plan, args.steps, max(args.warmup, 2 if args.mode == "graph" else 0), profile_min_N=N, first=first_run)
+    # (--full: live hipEvent pairs around the finest-level launches, the per-kernel figures and the roofline below)
+    ms_per_step, r, prof = time_cycle(mg, plan, args.steps, max(args.warmup, 2 if args.mode == "graph" else 0),
+                                      profile_min_N=N if args.full else None, first=first_run, settle_s=SETTLE_S)
     for h in held:
         h.close()
     dev_ms = r["device_ms"]
+    mg_error = plan.analytic_error(r)
+    if args.dump_outputs:
+        dump_outputs(mg, r, mg_error, args.dump_outputs)
     mlups = lups / (ms_per_step * 1e-3) / 1e6
     elem = 0.5 if args.mixed else 1.0
 
@@ -439,12 +498,11 @@ def main():
                    "N": N, "levels": len(sizes), "cycle_file": os.path.basename(cyc)},
         "device_ms_per_step": round(dev_ms, 4),
         "fine_dof_per_s": round(N * N / (ms_per_step * 1e-3), 1),
-        "mg_error": plan.analytic_error(r),
-        "roofline": roof,
-        "kernels": kernels[:8],
-        # what the device had been doing when the timed region started (windows of all legs, this one's first run and its
-        # W untimed ones) and the device time of this leg's first and last window
-        "clock_state": {"windows_before_timed": windows_before + 1 + max(args.warmup, 2 if args.mode == "graph" else 0),
+        "mg_error": mg_error,
+        **({"roofline": roof, "kernels": kernels[:8]} if args.full else {}),
+        # what the device had been doing when the timed region started (windows of all legs, this one's first run, its
+        # W untimed ones and the settling ones) and the device time of this leg's first and last window
+        "clock_state": {"windows_before_timed": windows_before + 1 + max(args.warmup, 2 if args.mode == "graph" else 0) + time_cycle.settle_windows,
                         "first_window_ms": round(time_cycle.first_ms, 4), "last_window_ms": round(dev_ms, 4)},
     }
     out.update(pre_legs)
@@ -460,41 +518,42 @@ def main():
     plan.close()
     mg.lib().mg_pool_trim()
 
-    # north_star's own yardstick, measured beside the cycle: ONE fine-level Jacobi sweep per launch (doSmoothing with
-    # step = 1, 24 B per point: compulsory == algorithmic here) -- the one-row-per-block pair kernel that the engine
-    # routes a bare sweep of a large grid to, and the streaming kernel at S = 1 (smoother "stream_only")
-    try:
-        Ua, Ub, Ff = mg.DeviceGrid.uniform(N, 3), mg.DeviceGrid(N), mg.DeviceGrid.uniform(N, 7)
-        single = {}
-        for sm in ("stream", "stream_only"):
-            mg.set_smoother(sm)
-            for _ in range(3):
-                mg.smooth_pp(N, 1.0, Ua, Ub, Ff, 1)
-            mg.sync()
-            mg.profile_begin(min_N=N)
-            for _ in range(10):
-                mg.smooth_pp(N, 1.0, Ua, Ub, Ff, 1)
-            e = mg.profile_end()[0]
-            avg = e["total_ms"] / e["launches"]
-            gbs = 24.0 * N * N / (avg * 1e-3) / 1e9
-            single["k_" + e["name"].split("<")[0] + ("_S1" if "stream" in e["name"] else "")] = {
-                "launch": e["name"], "avg_ms": round(avg, 4), "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
-        out["single_sweep_roofline"] = single
-        mg.set_smoother(args.smoother)
-        # the box's own device-to-device copy rate: the practical ceiling SURVEY.md 8d asks for
-        mg.lib().mg_copy(Ub.ptr, Ua.ptr, Ua.size)
-        mg.sync()
-        tc = time.perf_counter()
-        for _ in range(10):
+    if args.full:
+        # north_star's own yardstick, measured beside the cycle: ONE fine-level Jacobi sweep per launch (doSmoothing with
+        # step = 1, 24 B per point: compulsory == algorithmic here) -- the one-row-per-block pair kernel that the engine
+        # routes a bare sweep of a large grid to, and the streaming kernel at S = 1 (smoother "stream_only")
+        try:
+            Ua, Ub, Ff = mg.DeviceGrid.uniform(N, 3), mg.DeviceGrid(N), mg.DeviceGrid.uniform(N, 7)
+            single = {}
+            for sm in ("stream", "stream_only"):
+                mg.set_smoother(sm)
+                for _ in range(3):
+                    mg.smooth_pp(N, 1.0, Ua, Ub, Ff, 1)
+                mg.sync()
+                mg.profile_begin(min_N=N)
+                for _ in range(10):
+                    mg.smooth_pp(N, 1.0, Ua, Ub, Ff, 1)
+                e = mg.profile_end()[0]
+                avg = e["total_ms"] / e["launches"]
+                gbs = 24.0 * N * N / (avg * 1e-3) / 1e9
+                single["k_" + e["name"].split("<")[0] + ("_S1" if "stream" in e["name"] else "")] = {
+                    "launch": e["name"], "avg_ms": round(avg, 4), "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
+            out["single_sweep_roofline"] = single
+            mg.set_smoother(args.smoother)
+            # the box's own device-to-device copy rate: the practical ceiling SURVEY.md 8d asks for
             mg.lib().mg_copy(Ub.ptr, Ua.ptr, Ua.size)
-        mg.sync()
-        tc = (time.perf_counter() - tc) / 10
-        out["device_copy_GBs"] = round(16.0 * N * N / tc / 1e9, 1)
-        for g in (Ua, Ub, Ff):
-            g.free()
-    except mg.MGError as exc:  # never let the side measurement take the bench line down
-        out["single_sweep_roofline"] = {"error": str(exc)}
+            mg.sync()
+            tc = time.perf_counter()
+            for _ in range(10):
+                mg.lib().mg_copy(Ub.ptr, Ua.ptr, Ua.size)
+            mg.sync()
+            tc = (time.perf_counter() - tc) / 10
+            out["device_copy_GBs"] = round(16.0 * N * N / tc / 1e9, 1)
+            for g in (Ua, Ub, Ff):
+                g.free()
+        except mg.MGError as exc:  # never let the side measurement take the bench line down
+            out["single_sweep_roofline"] = {"error": str(exc)}
 
     if args.scaling == "strong" and isinstance(out.get("strong_scaling"), dict) and "value" in out["strong_scaling"]:
         s = out["strong_scaling"]
@@ -503,7 +562,7 @@ def main():
         out["config"]["workload"] = s["workload"]
         out["config"]["N"] = STRONG_N
 
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         base = cpu_baseline(tmp, N, args.n_min, nu, write_cycle, args.cycle)
         if base:
             out["cpu_baseline"] = base

@@ -1,7 +1,7 @@
 """bench_multi.py -- the --gpus N > 1 leg of bench.py: one process per GPU (launched by
 torch.distributed.run, or by bench.py itself), 1-D row slabs, ghost rows over RCCL/xGMI.
 
-Two legs per run, both in the one JSON line rank 0 prints:
+The legs of a run, all in the one JSON line rank 0 prints (a plain run: the weak leg; bench.py --full: all of them):
   weak   (`value`): the per-GPU share of the finest grid stays at the 8192^2 points the single-GPU metric is
          quoted on, so the grid is N_g x N_g with N_g ~ 8192*sqrt(gpus) (8192, 11520, 16384, 23040 for 1, 2, 4, 8
          GPUs: sizes m * 2^j with m <= 64, so that every level above the coarse-tail kernel keeps an even size);
@@ -199,11 +199,13 @@ def run(args, rank, world, local_rank):
     # line's `value` -- starts at the clocks a long run holds (bench.py does the same on one GPU).
     keys = ("N", "n_gpus", "value", "unit", "ms_per_step", "steps", "workload", "mg_error", "rank0_ms_per_step", "ghost_exchanges",
             "cycle_roofline", "ms_per_step_ranks")
+    # (the legs beside the weak one: --full only, the strong leg also when --scaling strong makes it the line's `value`)
+    full = getattr(args, "full", False)
     strong = None
-    if not args.no_strong and N_weak != STRONG_N:
+    if (full or args.scaling == "strong") and not args.no_strong and N_weak != STRONG_N:
         strong = run_leg(mg, args, rank, world, STRONG_N, rehearsal_wire, tmp)
     large = None
-    if not args.no_strong and not getattr(args, "no_large", False) and not args.mixed:
+    if full and not args.no_strong and not getattr(args, "no_large", False) and not args.mixed:
         from bench import LARGE_N
         import copy
         largs = copy.copy(args)
@@ -213,10 +215,10 @@ def run(args, rank, world, local_rank):
     # slab at 8 GPUs: three distributed levels, the hierarchy collapses at 1024) -- a strong leg whose one-GPU base is the
     # N = 1 line's `value`
     head_grid = None
-    if not args.no_strong and world > 1 and N_weak != 8192 and not args.mixed:
+    if full and not args.no_strong and world > 1 and N_weak != 8192 and not args.mixed:
         head_grid = run_leg(mg, args, rank, world, 8192, rehearsal_wire, tmp)
     weak = run_leg(mg, args, rank, world, N_weak, rehearsal_wire, tmp)
-    if not args.no_strong and N_weak == STRONG_N:
+    if (full or args.scaling == "strong") and not args.no_strong and N_weak == STRONG_N:
         strong = weak  # 4 GPUs: the weak-scaling grid IS 16384^2
 
     if rank == 0:

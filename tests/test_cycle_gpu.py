@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, assert_bits
+from conftest import GOLDEN, ROOT, assert_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -591,3 +591,31 @@ def test_w_cycle_revisits_are_idempotent_in_the_reference_semantics(mg, oracle, 
     gw = mg.CyclePlan(w, fused=True).execute(fetch_U=True)
     assert np.array_equal(gv["U"], gw["U"])
     assert len(gw["records"]) == len(ow["records"])
+
+
+def test_bench_plain_run_and_dumped_outputs(mg, oracle, tmp_path):
+    """bench.py without --full times exactly K steps and prints the headline alone (none of the --full legs);
+    --dump-outputs writes the sample of the last timed step's U that bench.dump_outputs describes.  At N = 1024
+    U_strided is all of U: equal to the oracle's run of the same file, and so are the seeded rows and the error."""
+    import json
+    N, d = 1024, tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--n", str(N), "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "vcycle_mlups" and line["unit"] == "MLUPS" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 3 and line["config"]["N"] == N and line["ms_per_step"] > 0
+    for k in ("strong_scaling", "strong_scaling_32768", "graph_replay", "roofline", "kernels", "single_sweep_roofline",
+              "device_copy_GBs", "cpu_baseline"):
+        assert k not in line, k
+    path = str(tmp_path / f"V{N}.txt")
+    mg.write_vcycle_file(path, N, 8, 3, 1e-7)
+    want = oracle.run_cycle_file(path, want_report=False)
+    assert want["status"] == 0
+    assert_bits(np.load(d / "U_strided.npy"), want["U"], "dumped U", zero_sign=True)
+    rows = np.sort(np.random.default_rng(0).choice(N, size=32, replace=False))
+    assert_bits(np.load(d / "U_rows.npy"), want["U"][rows], "dumped rows", zero_sign=True)
+    assert np.load(d / "mg_error.npy")[0] == pytest.approx(want["mg_error"], rel=1e-10)
+    assert line["mg_error"] == np.load(d / "mg_error.npy")[0]
