@@ -328,6 +328,60 @@ int  mg_slab_gather_U(mg_slab_plan *plan, double *host_full);
 void mg_slab_want_error(mg_slab_plan *plan, int on);
 void mg_slab_destroy(mg_slab_plan *plan);
 
+/* ------------------------------------------------------------------------- */
+/* residual-tolerance solver: V(pre, post) cycles on a caller's F and boundary    */
+/* until ||F - AU||_2 <= max(rtol*||F||_2, atol) over the interior points         */
+/* ------------------------------------------------------------------------- */
+/* Hierarchy: N, N/2, ... while >= N_min (the sizes mg_cycle_load derives for a header `N N_min` with con_N = 1);
+ * N_min in [3, 32], at least two levels (N >= 2*N_min).  One cycle is the reference driver's V(pre, post) node order
+ * (src/MG_solver_CPU.cpp:259-416) started from the caller's U (the finest level keeps its guess, :252-257; coarser
+ * levels start from zero) with two changes: the smoother is weighted Jacobi, U <- U + c*t with t the reference's bracket
+ * star - 4U - dx^2 F and c = 0.25*omega (product and sum rounded separately; omega = 1 is doSmoothing bit for bit), and
+ * the coarsest level runs the reference's red-black Gauss-Seidel from zero until err <= max(coarse_atol,
+ * coarse_rtol*err0), err0 = sum_interior|F| / (N-2)^2, at most coarse_max_iters iterations (coarse_rtol = 0 with
+ * coarse_atol = tol is the reference's exact solve).  Residual, restriction, prolongation, addition and the sign flip
+ * are the reference operators.  U (in/out): initial guess whose rim carries the Dirichlet values; the rim of F is
+ * ignored.  On N = 2^k and 2^k + 1 hierarchies the rim comes back bit-identical; on other sizes the reference's
+ * prolongation may move rim points by rounding (about 1e-14 seen). */
+typedef struct mg_solve_opts {
+    int    pre, post;          /* sweeps per level on the way down / up, 1..4 */
+    int    N_min;              /* coarsest size bound, 3..32 */
+    double omega;              /* Jacobi weight, (0, 1] */
+    double coarse_rtol, coarse_atol;
+    int    coarse_max_iters;   /* >= 1; reaching it is reported (coarse_capped), not fatal */
+    double rtol, atol;         /* stopping rule on the L2 residual */
+    int    max_cycles;         /* >= 0 */
+} mg_solve_opts;
+
+#define MG_SOLVE_CONVERGED      0
+#define MG_SOLVE_NOT_CONVERGED (-1)   /* max_cycles cycles ran without meeting the tolerance */
+
+typedef struct mg_solve_result {
+    int    status;             /* MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED, or an error code (> 0, mg_last_error) */
+    int    cycles;             /* V-cycles run */
+    int    converged;
+    int    coarse_capped;      /* 1 when some coarse solve stopped at coarse_max_iters above its target */
+    double res0, res, ref_norm;   /* ||F - AU_0||, ||F - AU_cycles||, ||F|| (interior L2) */
+    double device_ms;          /* hipEvent time of the whole call */
+    int    n_history;          /* cycles + 1 */
+    const double *history;     /* r_0 .. r_cycles, owned by the solver, valid until its next solve */
+} mg_solve_result;
+
+typedef struct mg_solver mg_solver;
+
+/* V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, coarse_atol 0, coarse_max_iters 10000, rtol 1e-10, atol 0, 50 cycles.
+ * rtol is relative to ||F||: on large grids the fp64 rounding of inv*(star - 4U) (inv = 1/dx^2) puts a floor under the
+ * reachable residual -- about 8e-10 relative at N = 8192 on the getSource problem -- so a default solve there runs all
+ * max_cycles and returns MG_SOLVE_NOT_CONVERGED; ask for rtol >= 1e-9 at that size. */
+void       mg_solve_opts_default(mg_solve_opts *o);
+/* every level array is allocated here (NULL opts: the defaults); NULL on bad arguments (mg_last_error) */
+mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *o);
+/* F_dev, U_dev: N x N device arrays (16-byte aligned).  Allocates nothing, works on the engine stream (mg_set_stream) and
+ * reads one norm back per cycle.  Returns out->status.  The cycle runs through the fused nodes of the streaming smoother
+ * (weighted instantiations); with mg_set_smoother("simple") operator by operator -- the same bits. */
+int        mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_result *out);
+void       mg_solver_destroy(mg_solver *s);
+
 #ifdef __cplusplus
 }
 #endif

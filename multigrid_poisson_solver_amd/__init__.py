@@ -44,6 +44,21 @@ class CycleResult(C.Structure):
 _vp, _i, _d, _sz, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_size_t, C.c_uint64
 _dptr = C.POINTER(C.c_double)
 
+
+class SolveOpts(C.Structure):
+    _fields_ = [("pre", C.c_int), ("post", C.c_int), ("N_min", C.c_int), ("omega", C.c_double), ("coarse_rtol", C.c_double),
+                ("coarse_atol", C.c_double), ("coarse_max_iters", C.c_int), ("rtol", C.c_double), ("atol", C.c_double),
+                ("max_cycles", C.c_int)]
+
+
+class SolveResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("cycles", C.c_int), ("converged", C.c_int), ("coarse_capped", C.c_int),
+                ("res0", C.c_double), ("res", C.c_double), ("ref_norm", C.c_double), ("device_ms", C.c_double),
+                ("n_history", C.c_int), ("history", _dptr)]
+
+
+MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED = 0, -1
+
 # every symbol include/mg_hip.h declares: name -> (restype, argtypes)
 ABI = {
     "mg_init": (_i, [_i]), "mg_finalize": (None, []), "mg_set_stream": (None, [_vp]),
@@ -92,6 +107,9 @@ ABI = {
     "mg_slab_load": (_vp, [C.c_char_p, _i, _i, _i]), "mg_slab_load_flags": (_vp, [C.c_char_p, _i, _i, _i, _i]), "mg_slab_execute": (_i, [_vp, C.POINTER(CycleResult)]),
     "mg_slab_enqueue": (_i, [_vp]), "mg_slab_collect": (_i, [_vp, C.POINTER(CycleResult)]),
     "mg_slab_gather_U": (_i, [_vp, _vp]), "mg_slab_want_error": (None, [_vp, _i]), "mg_slab_destroy": (None, [_vp]),
+    "mg_solve_opts_default": (None, [C.POINTER(SolveOpts)]),
+    "mg_solver_create": (_vp, [_i, _d, C.POINTER(SolveOpts)]),
+    "mg_solver_solve": (_i, [_vp, _vp, _vp, C.POINTER(SolveResult)]), "mg_solver_destroy": (None, [_vp]),
     "mg_profile_begin": (None, [_i]), "mg_profile_sample": (None, [_i]), "mg_profile_end": (_i, [C.POINTER(ProfileEntry), _i]),
 }
 
@@ -747,3 +765,111 @@ def write_wcycle_file(path, N, N_min=8, steps=3, tol=1e-7, L=1.0, depth=None):
     with open(path, "w") as f:
         f.write(f"{L} 0.0 0.0\n{steps} 1\n{N} {N_min}\n" + "\n".join(nodes) + "\n2")
     return len(sizes)
+
+
+def solve_opts(**opts):
+    """mg_solve_opts: the library's defaults (V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, rtol 1e-10, 50 cycles) with
+    the named fields replaced.  rtol is relative to ||F||; large grids have an fp64 rounding floor above 1e-10 (about
+    8e-10 at N = 8192 on the getSource problem): there a default solve runs all max_cycles and reports not converged,
+    so pass rtol=1e-9 or more at that size."""
+    o = SolveOpts()
+    lib().mg_solve_opts_default(C.byref(o))
+    names = {f for f, _ in SolveOpts._fields_}
+    for k, v in opts.items():
+        if k not in names:
+            raise TypeError(f"unknown solver option {k!r} (have {sorted(names)})")
+        setattr(o, k, v)
+    return o
+
+
+class Solver:
+    """Residual-tolerance solver of include/mg_hip.h: V(pre, post) cycles with a weighted Jacobi smoother and a
+    relative coarse target, on a caller's F and Dirichlet rim, until ||F - AU||_2 <= max(rtol*||F||_2, atol).  Every
+    level array is allocated here; solve() allocates nothing on the device."""
+
+    def __init__(self, N, L=1.0, **opts):
+        self.N, self.L = int(N), float(L)
+        self.opts = solve_opts(**opts)
+        self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
+        if not self._s:
+            _check()
+            raise MGError("mg_solver_create returned NULL")
+
+    def solve_ptr(self, F_ptr, U_ptr):
+        """F_ptr, U_ptr: device addresses of N x N fp64 arrays (U in/out), on the engine stream."""
+        res = SolveResult()
+        status = _lib.mg_solver_solve(self._s, F_ptr, U_ptr, C.byref(res))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_solver_solve failed with status {status}")
+        history = [res.history[i] for i in range(res.n_history)]
+        return dict(status=res.status, cycles=res.cycles, converged=bool(res.converged),
+                    coarse_capped=bool(res.coarse_capped), res0=res.res0, res=res.res, ref_norm=res.ref_norm,
+                    device_ms=res.device_ms, history=history)
+
+    def solve(self, F, U=None):
+        """F, U: numpy arrays, DeviceGrid, or float64 torch CUDA tensors (worked on in place, on
+        torch.cuda.current_stream()).  U = None starts from zero (zero rim).  Returns (U, info); a numpy U comes back
+        as a new numpy array."""
+        N = self.N
+        if _is_torch(F) or _is_torch(U):
+            import torch
+            if U is None:
+                U = torch.zeros((N, N), dtype=torch.float64, device=F.device)
+            for name, t in (("F", F), ("U", U)):
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                        and t.is_contiguous()):
+                    raise MGError(f"{name}: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(F.device).cuda_stream)
+            try:
+                info = self.solve_ptr(F.data_ptr(), U.data_ptr())
+            finally:
+                _lib.mg_set_stream(prev)
+            return U, info
+        keep = []
+
+        def dev(a, what):
+            if isinstance(a, DeviceGrid):
+                if a.shape != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        Fd = dev(F, "F")
+        host_U = U is None or not isinstance(U, DeviceGrid)
+        Ud = DeviceGrid.zeros((N, N)) if U is None else dev(U, "U")
+        info = self.solve_ptr(Fd.ptr, Ud.ptr)
+        return (Ud.to_host() if host_U else Ud), info
+
+    def close(self):
+        if getattr(self, "_s", None) and _initialised:
+            _lib.mg_solver_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _is_torch(a):
+    return a is not None and type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
+
+
+def solve(F, U=None, L=1.0, **opts):
+    """Solve the Poisson problem A U = F on the N x N grid of F (Dirichlet values on U's rim) to the residual
+    tolerance; returns (U, info).  See Solver, and solve_opts for the defaults (the default rtol of 1e-10 is below the
+    rounding floor of large grids: about 8e-10 at N = 8192)."""
+    N = int(F.shape[0])
+    s = Solver(N, L, **opts)
+    try:
+        return s.solve(F, U)
+    finally:
+        s.close()

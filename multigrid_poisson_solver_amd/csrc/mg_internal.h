@@ -284,7 +284,10 @@ void jacobi_stream(hipStream_t s, int N, double dx2, double inv, const double *i
                    int pre = 0, bool no_out = false,
                    // batch: the same node on batch->n instances in one launch (in/F/out/coarse/Fc above then only tell the
                    // node's shape -- which of them a node of this kind has -- and err_out is ignored)
-                   const NodeBatch *batch = nullptr);
+                   const NodeBatch *batch = nullptr,
+                   // cw != 0.25: the weighted sweep U + (cw*t) of the residual-tolerance solver (cw = 0.25*omega, fp64, no
+                   // recomputing pair, no batch); 0.25 is the reference's sweep
+                   double cw = 0.25);
 // register-tile fused nodes of the small levels (mg_tile.hip / mg_tile_f32.hip): one launch = level 0 (zero | in | in +
 // P(coarse)), `steps` sweeps, the error norm, optionally the d_sign-ed residual restricted into Fc; whole grid only
 bool tile_wanted(int N);      // MG_TILE_MIN_N <= N <= MG_TILE_MAX_N
@@ -370,6 +373,19 @@ void gauss_seidel(hipStream_t s, int N, double h2, double inv, double *U, const 
                   int *state);
 void gauss_seidel_blocks_launch(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double tol, int *state);
 int  gs_single_workgroup_max_n();
+// residual-tolerance solver (mg_solve_kernels.hip, driven by mg_solve.cpp)
+// one weighted Jacobi sweep U = U_old + cw*(star - 4 U_old - dx^2 F), cw = 0.25*omega, rim kept (in == nullptr: all zero)
+void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out);
+// *out = sqrt(sum over interior points of d^2), d = inv*(star - 4U) - F (U == nullptr: d = F); part holds at least
+// resnorm_partials(N) doubles; the partials are summed in a fixed order (bit-reproducible)
+size_t resnorm_partials(int N);
+void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out);
+// red-black Gauss-Seidel from zero to err <= max(atol, rtol*err0) (err0: the metric at U = 0), 1 ... max_iters iterations,
+// one workgroup; state[1] = iterations, state[2] = 1 when the cap ended it above the target; err_out[0..1] = err0, err
+constexpr int GS_RELATIVE_MAX_N = 64;
+bool gs_relative_fits(int N);
+void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double atol, double rtol,
+                           int max_iters, int *state, double *err_out);
 }  // namespace k
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When

@@ -1,0 +1,334 @@
+// mg_solve.cpp -- residual-tolerance solver (include/mg_hip.h, "residual-tolerance solver"): V(pre, post) cycles on a
+// caller's F and Dirichlet rim until the interior L2 residual meets the tolerance.  One cycle follows the reference
+// driver's node order (src/MG_solver_CPU.cpp:259-416) with the weighted Jacobi smoother and the relative coarse target
+// of mg_solve_kernels.hip; the transfer operators are the engine's own (mg_kernels.hip).  A driver of its own, not a mode
+// of the cycle-file interpreter (mg_cycle.cpp): every level array is allocated at creation, a solve allocates nothing.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mg_internal.h"
+
+using namespace mg;
+
+struct mg_solver {
+    int N = 0;
+    double L = 1.0;
+    mg_solve_opts o{};
+    std::vector<int> sizes;                  // N, N/2, ... >= N_min
+    std::vector<double *> A, B, F;           // per level (level 0: only B, the scratch field beside the caller's U)
+    double *part = nullptr;                  // norm partials
+    double *dev_scal = nullptr;              // [4]: residual norm, reference norm, coarse err0, coarse err
+    int *gs_state = nullptr;                 // [4]
+    double *host_scal = nullptr;             // pinned [4]
+    int *host_state = nullptr;               // pinned [4]
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_norm = nullptr;
+    std::vector<double> history;
+};
+
+namespace {
+
+bool finite(double v) { return std::isfinite(v); }
+
+bool opts_ok(int N, double L, const mg_solve_opts &o)
+{
+    if (!(L > 0.0) || !finite(L)) { fail(MG_ERR_ARG, "mg_solver_create: L = %g must be positive and finite", L); return false; }
+    if (o.N_min < 3 || o.N_min > 32) { fail(MG_ERR_ARG, "mg_solver_create: N_min = %d outside [3, 32]", o.N_min); return false; }
+    if (N < 2 * o.N_min) {
+        fail(MG_ERR_ARG, "mg_solver_create: N = %d needs at least two levels (N >= 2*N_min = %d)", N, 2 * o.N_min);
+        return false;
+    }
+    if (o.pre < 1 || o.pre > 4 || o.post < 1 || o.post > 4) {
+        fail(MG_ERR_ARG, "mg_solver_create: pre = %d / post = %d sweeps outside [1, 4]", o.pre, o.post);
+        return false;
+    }
+    if (!(o.omega > 0.0 && o.omega <= 1.0)) { fail(MG_ERR_ARG, "mg_solver_create: omega = %g outside (0, 1]", o.omega); return false; }
+    if (!(o.coarse_rtol >= 0.0) || !(o.coarse_atol >= 0.0) || !finite(o.coarse_rtol) || !finite(o.coarse_atol) ||
+        !(o.coarse_rtol > 0.0 || o.coarse_atol > 0.0)) {
+        fail(MG_ERR_ARG, "mg_solver_create: coarse_rtol = %g, coarse_atol = %g (non-negative, finite, not both zero)", o.coarse_rtol,
+             o.coarse_atol);
+        return false;
+    }
+    if (o.coarse_max_iters < 1) { fail(MG_ERR_ARG, "mg_solver_create: coarse_max_iters = %d < 1", o.coarse_max_iters); return false; }
+    if (!(o.rtol >= 0.0) || !(o.atol >= 0.0) || !finite(o.rtol) || !finite(o.atol)) {
+        fail(MG_ERR_ARG, "mg_solver_create: rtol = %g, atol = %g must be non-negative and finite", o.rtol, o.atol);
+        return false;
+    }
+    if (o.max_cycles < 0) { fail(MG_ERR_ARG, "mg_solver_create: max_cycles = %d < 0", o.max_cycles); return false; }
+    return true;
+}
+
+double spacing_sq(int N, double L)
+{
+    const double dx = L / (double)(N - 1);
+    return dx * dx;
+}
+
+void release(mg_solver *s)
+{
+    for (double *p : s->A) if (p) (void)hipFree(p);
+    for (double *p : s->B) if (p) (void)hipFree(p);
+    for (double *p : s->F) if (p) (void)hipFree(p);
+    if (s->part) (void)hipFree(s->part);
+    if (s->dev_scal) (void)hipFree(s->dev_scal);
+    if (s->gs_state) (void)hipFree(s->gs_state);
+    if (s->host_scal) (void)hipHostFree(s->host_scal);
+    if (s->host_state) (void)hipHostFree(s->host_state);
+    if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
+    if (s->ev_end) (void)hipEventDestroy(s->ev_end);
+    if (s->ev_norm) (void)hipEventDestroy(s->ev_norm);
+    delete s;
+}
+
+template <typename T>
+bool dev_alloc(T **p, size_t n)
+{
+    return MG_HIP(hipMalloc((void **)p, n * sizeof(T)));
+}
+
+// one V(pre, post) cycle from the caller's U (level 0 keeps its guess; coarser levels start from zero), operator by
+// operator: one launch per sweep (MG_SMOOTHER=simple, and the yardstick of the fused cycle below)
+void vcycle_simple(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+{
+    const mg_solve_opts &o = s->o;
+    const int nl = (int)s->sizes.size();
+    const double cw = 0.25 * o.omega;
+    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
+    for (int l = 0; l + 1 < nl; ++l) {
+        const int N = s->sizes[l], M = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L);
+        const double *F = l == 0 ? F0 : s->F[l];
+        double *cur = l == 0 ? U0 : s->A[l], *other = s->B[l];
+        int sweeps = o.pre;
+        if (l > 0) {   // memset(U, 0) (:256) folded into the first sweep
+            k::wjacobi(st, N, dx2, cw, nullptr, F, cur);
+            --sweeps;
+        }
+        for (int i = 0; i < sweeps; ++i) {
+            k::wjacobi(st, N, dx2, cw, cur, F, other);
+            std::swap(cur, other);
+        }
+        // D = -getResidual(U) (:268, :277-280) into the free field, F_c = doRestriction(D) (:287)
+        k::residual(st, N, 1.0 / dx2, cur, F, other, -1);
+        k::restrict_gather(st, N, other, M, s->F[l + 1], restrict_table(N, M), +1);
+        x[l] = cur;
+        y[l] = other;
+    }
+    const int Nc = s->sizes[nl - 1];
+    const double h2 = spacing_sq(Nc, s->L);
+    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                             s->gs_state, s->dev_scal + 2);
+    x[nl - 1] = s->A[nl - 1];
+    for (int l = nl - 2; l >= 0; --l) {
+        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L);
+        const double *F = l == 0 ? F0 : s->F[l];
+        double *cur = x[l], *other = y[l];
+        // U = U + doProlongation(U_c) (:354, :368) into the free field
+        k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
+        std::swap(cur, other);
+        for (int i = 0; i < o.post; ++i) {
+            k::wjacobi(st, N, dx2, cw, cur, F, other);
+            std::swap(cur, other);
+        }
+        x[l] = cur;
+    }
+    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)s->N * s->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+
+// the same cycle through the fused nodes of the streaming smoother (its weighted instantiations): per level one `-1`
+// launch (all pre sweeps + the restricted residual) and one `1` launch (prolongation-add + all post sweeps) where the
+// transfer stages fuse (even N, nested tables), the sweeps in one launch and the transfers operator by operator elsewhere.
+// Level 0: the `-1` node reads the caller's U and stores into B[0]; U is free until the `1` node writes the result there.
+void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+{
+    const mg_solve_opts &o = s->o;
+    const int nl = (int)s->sizes.size();
+    const double cw = 0.25 * o.omega;
+    std::vector<double *> x(nl);   // per level: the field holding the pre-smoothed iterate, then the result
+    for (int l = 0; l + 1 < nl; ++l) {
+        const int N = s->sizes[l], M = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double *F = l == 0 ? F0 : s->F[l];
+        const double *in = l == 0 ? U0 : nullptr;   // coarser levels: memset(U, 0) (:256) folded into the first sweep
+        double *out = l == 0 ? s->B[0] : s->A[l], *scratch = l == 0 ? U0 : s->B[l];
+        const RestrictTable &rt = restrict_table(N, M);
+        if (k::stream_fusable(N) && rt.fusable) {
+            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.pre, nullptr, nullptr, -1, nullptr, 0, nullptr, s->F[l + 1], M, &rt,
+                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+        } else {
+            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.pre, nullptr, nullptr, -1, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            k::residual(st, N, inv, out, F, scratch, -1);
+            k::restrict_gather(st, N, scratch, M, s->F[l + 1], rt, +1);
+        }
+        x[l] = out;
+    }
+    const int Nc = s->sizes[nl - 1];
+    const double h2 = spacing_sq(Nc, s->L);
+    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                             s->gs_state, s->dev_scal + 2);
+    x[nl - 1] = s->A[nl - 1];
+    for (int l = nl - 2; l >= 0; --l) {
+        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double *F = l == 0 ? F0 : s->F[l];
+        double *in = x[l], *out = l == 0 ? U0 : s->B[l];
+        const ProlongTable &pt = prolong_table(Nc_l, N);
+        if (k::stream_fusable(N) && pt.fusable) {
+            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.post, nullptr, nullptr, +1, x[l + 1], Nc_l, &pt, nullptr, 0, nullptr,
+                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            x[l] = out;
+        } else {
+            // U + doProlongation(U_c) (:354, :368) into `out`, the sweeps back into `in`
+            k::prolong(st, Nc_l, x[l + 1], N, in, out, pt);
+            k::jacobi_stream(st, N, dx2, inv, out, F, in, o.post, nullptr, nullptr, +1, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            x[l] = in;
+        }
+    }
+    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)s->N * s->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+
+void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+{
+    if (ctx().smoother == SMOOTHER_SIMPLE) vcycle_simple(s, st, F0, U0);
+    else vcycle_fused(s, st, F0, U0);
+}
+
+// enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
+void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
+{
+    k::resnorm(st, s->N, 1.0 / spacing_sq(s->N, s->L), U0, F0, s->part, s->dev_scal + slot);
+}
+
+bool read_back(mg_solver *s, hipStream_t st)
+{
+    if (!MG_HIP(hipMemcpyAsync(s->host_scal, s->dev_scal, 4 * sizeof(double), hipMemcpyDeviceToHost, st))) return false;
+    if (!MG_HIP(hipMemcpyAsync(s->host_state, s->gs_state, 4 * sizeof(int), hipMemcpyDeviceToHost, st))) return false;
+    if (!MG_HIP(hipEventRecord(s->ev_norm, st))) return false;
+    return MG_HIP(hipEventSynchronize(s->ev_norm));
+}
+
+}  // namespace
+
+extern "C" {
+
+void mg_solve_opts_default(mg_solve_opts *o)
+{
+    if (!o) return;
+    o->pre = 3;
+    o->post = 3;
+    o->N_min = 8;
+    o->omega = 0.8;
+    o->coarse_rtol = 1e-2;
+    o->coarse_atol = 0.0;
+    o->coarse_max_iters = 10000;
+    o->rtol = 1e-10;
+    o->atol = 0.0;
+    o->max_cycles = 50;
+}
+
+mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
+{
+    if (!require_ready("mg_solver_create")) return nullptr;
+    mg_solve_opts o;
+    mg_solve_opts_default(&o);
+    if (opts) o = *opts;
+    if (!opts_ok(N, L, o)) return nullptr;
+    mg_solver *s = new mg_solver;
+    s->N = N;
+    s->L = L;
+    s->o = o;
+    for (int n = N; n >= o.N_min; n /= 2) s->sizes.push_back(n);   // mg_cycle_load's halving sizes (con_N = 1)
+    const int nl = (int)s->sizes.size();
+    if (!k::gs_relative_fits(s->sizes[nl - 1])) {   // (N_min <= 32 keeps the coarsest level below 64)
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_create: coarsest level %d does not fit the coarse solver", s->sizes[nl - 1]);
+        release(s);
+        return nullptr;
+    }
+    s->A.assign(nl, nullptr);
+    s->B.assign(nl, nullptr);
+    s->F.assign(nl, nullptr);
+    bool ok = true;
+    for (int l = 0; l < nl && ok; ++l) {
+        const size_t n = (size_t)s->sizes[l] * s->sizes[l];
+        ok = dev_alloc(&s->B[l], n);
+        if (ok && l > 0) ok = dev_alloc(&s->A[l], n) && dev_alloc(&s->F[l], n);
+    }
+    for (int l = 0; l + 1 < nl && ok; ++l) {   // the transfer tables, built once here
+        const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
+        ok = restrict_table(Nf, Nc).lo != nullptr && prolong_table(Nc, Nf).owner_row != nullptr;
+    }
+    ok = ok && dev_alloc(&s->part, k::resnorm_partials(N)) && dev_alloc(&s->dev_scal, 4) && dev_alloc(&s->gs_state, 4) &&
+         MG_HIP(hipHostMalloc((void **)&s->host_scal, 4 * sizeof(double), hipHostMallocDefault)) &&
+         MG_HIP(hipHostMalloc((void **)&s->host_state, 4 * sizeof(int), hipHostMallocDefault)) &&
+         MG_HIP(hipEventCreate(&s->ev_begin)) && MG_HIP(hipEventCreate(&s->ev_end)) &&
+         MG_HIP(hipEventCreateWithFlags(&s->ev_norm, hipEventDisableTiming));
+    ok = ok && MG_HIP(hipMemset(s->dev_scal, 0, 4 * sizeof(double))) && MG_HIP(hipMemset(s->gs_state, 0, 4 * sizeof(int)));
+    if (!ok) {
+        release(s);
+        return nullptr;
+    }
+    s->history.reserve((size_t)o.max_cycles + 1);
+    return s;
+}
+
+int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_result *out)
+{
+    mg_solve_result r;
+    std::memset(&r, 0, sizeof r);
+    auto finish = [&](int status) {
+        r.status = status;
+        r.n_history = (int)(s ? s->history.size() : 0);
+        r.history = s && !s->history.empty() ? s->history.data() : nullptr;
+        if (out) *out = r;
+        return status;
+    };
+    if (!require_ready("mg_solver_solve")) return finish(MG_ERR_NOT_INIT);
+    if (!s || !F_dev || !U_dev) {
+        fail(MG_ERR_ARG, "mg_solver_solve: NULL solver or array");
+        return finish(MG_ERR_ARG);
+    }
+    if (((uintptr_t)F_dev | (uintptr_t)U_dev) % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_solver_solve: F and U must be 16-byte aligned");
+        return finish(MG_ERR_ARG);
+    }
+    s->history.clear();
+    const hipStream_t st = ctx().stream;
+    const mg_solve_opts &o = s->o;
+    if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
+    if (!MG_HIP(hipMemsetAsync(s->gs_state, 0, 4 * sizeof(int), st))) return finish(MG_ERR_HIP);
+    norm(s, st, F_dev, nullptr, 1);
+    norm(s, st, F_dev, U_dev, 0);
+    if (!read_back(s, st)) return finish(MG_ERR_HIP);
+    r.ref_norm = s->host_scal[1];
+    double res = s->host_scal[0];
+    r.res0 = res;
+    s->history.push_back(res);
+    const double tol = std::fmax(o.rtol * r.ref_norm, o.atol);
+    while (!(res <= tol) && r.cycles < o.max_cycles) {
+        vcycle(s, st, F_dev, U_dev);
+        norm(s, st, F_dev, U_dev, 0);
+        if (!read_back(s, st)) return finish(MG_ERR_HIP);
+        res = s->host_scal[0];
+        s->history.push_back(res);
+        r.cycles += 1;
+        if (s->host_state[2]) r.coarse_capped = 1;
+    }
+    if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return finish(MG_ERR_HIP);
+    float ms = 0.0f;
+    if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) r.device_ms = ms;
+    r.res = res;
+    r.converged = res <= tol ? 1 : 0;
+    return finish(r.converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED);
+}
+
+void mg_solver_destroy(mg_solver *s)
+{
+    if (!s) return;
+    if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+    release(s);
+}
+
+}  // extern "C"

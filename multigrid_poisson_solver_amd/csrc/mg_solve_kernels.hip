@@ -1,0 +1,339 @@
+// mg_solve_kernels.hip -- fp64 kernels of the residual-tolerance solver (mg_solve.cpp): the weighted Jacobi sweep, the
+// red-black Gauss-Seidel coarse solve with a target relative to its own start residual, and the residual L2 norm.
+// Built with -ffp-contract=off like every kernel file: the weighted update U + c*t rounds the product and the sum
+// separately, and every bracket keeps the reference's association order (src/MG_solver_CPU.cpp:590, :1020, :560).
+// The sweeps here are the operator-by-operator form (MG_SMOOTHER=simple); the default cycle runs the weighted
+// instantiations of the streaming smoother (mg_stream_impl.h, WT).
+#include <hip/hip_runtime.h>
+
+#include "mg_internal.h"
+
+namespace mg {
+namespace k {
+
+namespace {
+
+constexpr int TB = 256;       // threads per block of the streaming kernels
+constexpr int ROWS_PB = 4;    // rows per block, one point per lane
+constexpr int PR = 4;         // rows per thread of the 16-byte forms (rolling window of three row pairs)
+constexpr int PAIR_MIN_N = 512;
+constexpr int NT_MIN_N = 4096;   // from here on the arrays are far larger than the caches: non-temporal F loads
+typedef double double2_s __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// sum over the block in a fixed order; valid in thread 0
+__device__ __forceinline__ double block_sum(double v)
+{
+    __shared__ double sm[16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) sm[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) {
+        const int nw = (blockDim.x + 63) >> 6;
+        for (int i = 0; i < nw; ++i) r += sm[i];
+    }
+    return r;
+}
+
+__device__ __forceinline__ bool rim(int r, int c, int N)
+{
+    return r == 0 || c == 0 || r == N - 1 || c == N - 1;
+}
+
+// 5-point bracket in the reference's order: row+1, row-1, col+1, col-1, then -4*centre (src/MG_solver_CPU.cpp:590)
+__device__ __forceinline__ double star_minus4(const double *__restrict__ A, size_t p, int N)
+{
+    return A[p + N] + A[p - N] + A[p + 1] + A[p - 1] - 4 * A[p];
+}
+
+template <bool NT>
+__device__ __forceinline__ double2_s load_f(const double *p)
+{
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const double2_s *>(p));
+    return *reinterpret_cast<const double2_s *>(p);
+}
+
+// ---------------------------------------------------------------- weighted Jacobi, one sweep
+// U = U_old + c*t, t = star(U_old) - 4 U_old - dx^2 F, c = 0.25*omega (formed on the host).  At omega = 1 the product
+// with 0.25 is exact and this is doSmoothing's sweep bit for bit.  Rim points keep their value.
+template <bool ZERO_IN>
+__global__ __launch_bounds__(TB) void k_wjacobi(int N, double dx2, double cw, const double *__restrict__ in,
+                                                const double *__restrict__ F, double *__restrict__ out)
+{
+    const int c = blockIdx.x * TB + threadIdx.x;
+    if (c >= N) return;
+    const int r0 = blockIdx.y * ROWS_PB;
+#pragma unroll
+    for (int k = 0; k < ROWS_PB; ++k) {
+        const int r = r0 + k;
+        if (r >= N) return;
+        const size_t p = (size_t)r * N + c;
+        double v;
+        if (ZERO_IN) {
+            // the bracket of an all-zero field: (0+0+0+0 - 4*0) - dx^2 F = 0 - dx^2 F
+            v = rim(r, c, N) ? 0.0 : 0.0 + cw * (0.0 - dx2 * F[p]);
+        } else {
+            v = in[p];
+            if (!rim(r, c, N)) v = v + cw * (star_minus4(in, p, N) - dx2 * F[p]);
+        }
+        out[p] = v;
+    }
+}
+
+// the same sweep on even N >= PAIR_MIN_N with 16 B per lane and PR rows per thread (the shape of k_jacobi_pair_rows):
+// every row of `in` is read once, its outer neighbours are single doubles (L1 hits of the neighbouring lanes' pairs)
+template <bool NT>
+__global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double cw, const double *__restrict__ in,
+                                                      const double *__restrict__ F, double *__restrict__ out)
+{
+    const int c = 2 * (blockIdx.x * TB + threadIdx.x);
+    const int r0 = blockIdx.y * PR;
+    if (c >= N) return;
+    auto row_pair = [&](int r) {
+        r = r < 0 ? 0 : (r < N ? r : N - 1);   // (rows beyond the grid: clamped, never used)
+        return *reinterpret_cast<const double2_s *>(in + (size_t)r * N + c);
+    };
+    double2_s dn = row_pair(r0 - 1), ctr = row_pair(r0);
+#pragma unroll
+    for (int k = 0; k < PR; ++k) {
+        const int r = r0 + k;
+        if (r >= N) break;
+        const double2_s up = row_pair(r + 1);
+        const size_t p = (size_t)r * N + c;
+        double2_s o = ctr;
+        if (r > 0 && r < N - 1) {
+            const double2_s f = load_f<NT>(F + p);
+            if (c > 0) {
+                const double w = in[p - 1];
+                o.x = ctr.x + cw * (up.x + dn.x + ctr.y + w - 4 * ctr.x - dx2 * f.x);
+            }
+            if (c + 1 < N - 1) {
+                const double e = in[p + 2];
+                o.y = ctr.y + cw * (up.y + dn.y + e + ctr.x - 4 * ctr.y - dx2 * f.y);
+            }
+        }
+        if (NT) __builtin_nontemporal_store(o, reinterpret_cast<double2_s *>(out + p));
+        else *reinterpret_cast<double2_s *>(out + p) = o;
+        dn = ctr;
+        ctr = up;
+    }
+}
+
+// ---------------------------------------------------------------- residual L2 norm
+// per-block partial sums of d^2 over interior points, d = inv*(star - 4U) - F (getResidual's value, :560);
+// HAS_U = false: U == 0, d = -F (the reference norm ||F||).  Nothing but the partials is written.
+template <bool HAS_U>
+__global__ __launch_bounds__(TB) void k_resnorm(int N, double inv, const double *__restrict__ U,
+                                                const double *__restrict__ F, double *__restrict__ part)
+{
+    const int c = blockIdx.x * TB + threadIdx.x;
+    const int r0 = blockIdx.y * ROWS_PB;
+    double acc = 0.0;
+    if (c < N) {
+#pragma unroll
+        for (int k = 0; k < ROWS_PB; ++k) {
+            const int r = r0 + k;
+            if (r < N && !rim(r, c, N)) {
+                const size_t p = (size_t)r * N + c;
+                const double d = HAS_U ? inv * star_minus4(U, p, N) - F[p] : F[p];
+                acc += d * d;
+            }
+        }
+    }
+    const double s = block_sum(acc);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// even N >= PAIR_MIN_N: 16 B per lane, PR rows per thread with a rolling window of three row pairs (every row of U read
+// once), F through 16-byte (non-temporal from NT_MIN_N on) loads -- 16 B of HBM traffic per point
+template <bool HAS_U, bool NT>
+__global__ __launch_bounds__(TB) void k_resnorm_pairs(int N, double inv, const double *__restrict__ U,
+                                                      const double *__restrict__ F, double *__restrict__ part)
+{
+    const int c = 2 * (blockIdx.x * TB + threadIdx.x);
+    const int r0 = blockIdx.y * PR;
+    double acc = 0.0;
+    if (c < N) {
+        const int cl = c > 0 ? c - 1 : 0, cr = c + 2 < N ? c + 2 : N - 1;
+        auto row_pair = [&](int r) {
+            r = r < 0 ? 0 : (r < N ? r : N - 1);
+            return *reinterpret_cast<const double2_s *>(U + (size_t)r * N + c);
+        };
+        double2_s up = {0.0, 0.0}, mid = {0.0, 0.0};
+        if (HAS_U) {
+            up = row_pair(r0 - 1);
+            mid = row_pair(r0);
+        }
+#pragma unroll
+        for (int k = 0; k < PR; ++k) {
+            const int r = r0 + k;
+            if (r >= N) break;
+            double2_s down = {0.0, 0.0};
+            if (HAS_U) down = row_pair(r + 1);
+            if (r > 0 && r < N - 1) {
+                const size_t p = (size_t)r * N + c;
+                const double2_s f = load_f<NT>(F + p);
+                double2_s d = f;
+                if (HAS_U) {
+                    const double left = U[(size_t)r * N + cl], right = U[(size_t)r * N + cr];
+                    d.x = inv * (down.x + up.x + mid.y + left - 4 * mid.x) - f.x;
+                    d.y = inv * (down.y + up.y + right + mid.x - 4 * mid.y) - f.y;
+                }
+                if (c > 0) acc += d.x * d.x;
+                if (c + 1 < N - 1) acc += d.y * d.y;
+            }
+            up = mid;
+            mid = down;
+        }
+    }
+    const double s = block_sum(acc);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// second stage: *out = sqrt(sum of the n partials), one block in a fixed order (run-to-run reproducible)
+__global__ __launch_bounds__(1024) void k_resnorm_finish(const double *__restrict__ part, size_t n, double *__restrict__ out)
+{
+    double acc = 0.0;
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc += part[i];
+    const double s = block_sum(acc);
+    if (threadIdx.x == 0) *out = sqrt(s);
+}
+
+// ---------------------------------------------------------------- coarse solve
+// red-black Gauss-Seidel of src/MG_solver_CPU.cpp:952-1066 in ONE workgroup (U and F in LDS): zero start (:993),
+// colour 0 = (row+col) even then colour 1, update :1020/:1043, err :1051-1059 = sum|residual| / (N-2)^2.  The target
+// is max(atol, rtol*err0) with err0 the same metric at U = 0 (sum|F| / (N-2)^2), evaluated here from F before the
+// first iteration; at least one iteration, at most max_iters.  state[1] = iterations, state[2] = 1 when the cap ended
+// the solve above the target, state[3] = bits of nothing (kept zero).  *err_out (when given) = err0, final err.
+__global__ __launch_bounds__(1024) void k_gs_relative(int N, double h2, double inv, double *__restrict__ Ug,
+                                                      const double *__restrict__ Fg, double atol, double rtol,
+                                                      int max_iters, int *__restrict__ state, double *__restrict__ err_out)
+{
+    extern __shared__ __align__(16) double lds[];
+    __shared__ double s_val;
+    const int n = N * N;
+    double *U = lds, *F = lds + n;
+    const double denom = (double)((N - 2) * (N - 2));
+    double acc = 0.0;
+    for (int p = threadIdx.x; p < n; p += blockDim.x) {
+        const double f = Fg[p];
+        F[p] = f;
+        U[p] = 0.0;
+        const int r = p / N, c = p - r * N;
+        if (!rim(r, c, N)) acc = acc + fabs(f);
+    }
+    double s = block_sum(acc);
+    if (threadIdx.x == 0) s_val = s / denom;
+    __syncthreads();
+    const double err0 = s_val;
+    const double target = rtol * err0 > atol ? rtol * err0 : atol;
+
+    int iterations = 0;
+    double err = 0.0;
+    for (;;) {
+        for (int colour = 0; colour < 2; ++colour) {
+            for (int p = threadIdx.x; p < n; p += blockDim.x) {
+                const int r = p / N, c = p - r * N;
+                if (!rim(r, c, N) && ((r + c) & 1) == colour)
+                    U[p] = 0.25 * (U[p - 1] + U[p + 1] + U[p + N] + U[p - N] - h2 * F[p]);
+            }
+            __syncthreads();
+        }
+        ++iterations;
+        acc = 0.0;
+        for (int p = threadIdx.x; p < n; p += blockDim.x) {
+            const int r = p / N, c = p - r * N;
+            if (!rim(r, c, N))
+                acc = acc + fabs(inv * (U[p + N] + U[p - N] + U[p + 1] + U[p - 1] - 4 * U[p]) - F[p]);
+        }
+        s = block_sum(acc);
+        if (threadIdx.x == 0) s_val = s / denom;
+        __syncthreads();
+        err = s_val;
+        __syncthreads();   // every thread has read s_val before thread 0 writes the next one
+        if (!(err > target) || iterations >= max_iters) break;
+    }
+    for (int p = threadIdx.x; p < n; p += blockDim.x) Ug[p] = U[p];
+    if (threadIdx.x == 0) {
+        state[0] = 1;
+        state[1] = iterations;
+        state[2] = err > target ? 1 : 0;
+        state[3] = 0;
+        if (err_out) {
+            err_out[0] = err0;
+            err_out[1] = err;
+        }
+    }
+}
+
+inline dim3 grid_rows(int N) { return dim3((N + TB - 1) / TB, (N + ROWS_PB - 1) / ROWS_PB); }
+inline bool use_pairs(int N) { return N % 2 == 0 && N >= PAIR_MIN_N; }
+inline dim3 grid_pairs(int N) { return dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR); }
+
+}  // namespace
+
+// ------------------------------------------------------------------ launchers
+void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out)
+{
+    if (!in) {
+        hipLaunchKernelGGL(k_wjacobi<true>, grid_rows(N), dim3(TB), 0, s, N, dx2, cw, in, F, out);
+        return;
+    }
+    if (use_pairs(N)) {
+        if (N >= NT_MIN_N) hipLaunchKernelGGL(k_wjacobi_pairs<true>, grid_pairs(N), dim3(TB), 0, s, N, dx2, cw, in, F, out);
+        else hipLaunchKernelGGL(k_wjacobi_pairs<false>, grid_pairs(N), dim3(TB), 0, s, N, dx2, cw, in, F, out);
+        return;
+    }
+    hipLaunchKernelGGL(k_wjacobi<false>, grid_rows(N), dim3(TB), 0, s, N, dx2, cw, in, F, out);
+}
+
+size_t resnorm_partials(int N)
+{
+    const dim3 g = use_pairs(N) ? grid_pairs(N) : grid_rows(N);
+    return (size_t)g.x * g.y;
+}
+
+void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out)
+{
+    const size_t np = resnorm_partials(N);
+    if (use_pairs(N)) {
+        const dim3 g = grid_pairs(N);
+        const bool nt = N >= NT_MIN_N;
+        if (U) {
+            if (nt) hipLaunchKernelGGL((k_resnorm_pairs<true, true>), g, dim3(TB), 0, s, N, inv, U, F, part);
+            else hipLaunchKernelGGL((k_resnorm_pairs<true, false>), g, dim3(TB), 0, s, N, inv, U, F, part);
+        } else {
+            if (nt) hipLaunchKernelGGL((k_resnorm_pairs<false, true>), g, dim3(TB), 0, s, N, inv, U, F, part);
+            else hipLaunchKernelGGL((k_resnorm_pairs<false, false>), g, dim3(TB), 0, s, N, inv, U, F, part);
+        }
+    } else {
+        if (U) hipLaunchKernelGGL(k_resnorm<true>, grid_rows(N), dim3(TB), 0, s, N, inv, U, F, part);
+        else hipLaunchKernelGGL(k_resnorm<false>, grid_rows(N), dim3(TB), 0, s, N, inv, U, F, part);
+    }
+    hipLaunchKernelGGL(k_resnorm_finish, dim3(1), dim3(1024), 0, s, part, np, out);
+}
+
+bool gs_relative_fits(int N) { return N >= 3 && N < GS_RELATIVE_MAX_N; }
+
+void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double atol,
+                           double rtol, int max_iters, int *state, double *err_out)
+{
+    const size_t n = (size_t)N * N;
+    const size_t lds = 2 * n * sizeof(double);
+    int threads = (int)((n + 63) / 64 * 64);
+    if (threads > 1024) threads = 1024;
+    // (N <= 63: at most 63 KiB of U and F, inside the default 64 KiB of dynamic LDS)
+    hipLaunchKernelGGL(k_gs_relative, dim3(1), dim3(threads), lds, s, N, h2, inv, U, F, atol, rtol, max_iters, state, err_out);
+}
+
+}  // namespace k
+}  // namespace mg

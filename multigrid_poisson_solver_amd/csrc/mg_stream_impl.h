@@ -152,6 +152,10 @@ struct StreamParams {
     int part_stride;    // partials per instance
     int n_batch;                // (host side only: instances of the launch, and where each one's error goes)
     double *const *err_outs;
+    // WT instantiations (the weighted Jacobi sweep of the residual-tolerance solver, mg_solve.cpp): U + (cw*t), cw =
+    // 0.25*omega formed on the host, product and sum rounded separately.  Last, so that the other fields keep their offsets.
+    real_t cw;
+    int wt;                     // (host side only: launch the WT instantiation)
 };
 
 
@@ -374,7 +378,7 @@ __device__ __forceinline__ Row<COLS> ring_unpack(const typename RingVec<COLS>::f
 #define MG_WPE_UP 2   // (3 = 168 VGPRs: the allocator spills 15-27 dwords, and a spill reload drains the load queue: 580 us)   waves per SIMD the allocator is asked to make room for in the LDS-ring form of the `1` node
 #endif
 
-template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0>
+template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(LdsRing<COLS, PRE>::value ? MG_WPE_UP : WavesPerSimd<S, COLS, IN, RESTRICT, PRE>::min)))
 void k_jacobi_stream(const StreamParams p)
 {
@@ -387,6 +391,7 @@ void k_jacobi_stream(const StreamParams p)
     // node), the prolongation is added to level PRE, S more sweeps follow (levels PRE+1..L).  8 B per point less to
     // read here, 8 B per point less to write there, for PRE more sweeps of arithmetic in a kernel that waits for memory.
     static_assert(PRE == 0 || (IN == IN_PROLONG && !RESTRICT), "recomputed pre-smoothing belongs to the fused `1` node");
+    static_assert(!WT || (PRE == 0 && sizeof(real_t) == 8), "the weighted sweep: fp64 nodes that store and re-read U");
     constexpr int L = S + PRE;                         // levels of the pipeline
     constexpr bool LDSR = LdsRing<COLS, PRE>::value;   // F rows in LDS (dx2*F for the sweeps, one column of F for the norm)
     constexpr bool HALF = LDSR;                        // norm-only residual stage: one column per row
@@ -460,7 +465,7 @@ void k_jacobi_stream(const StreamParams p)
         col_in[j] = x >= 0 && x < N;
         col_edge[j] = x <= 0 || x >= N - 1;
         lane_owns = lane_owns && x >= own_x0 && x < own_x0 + OW && x < N;
-        qc[j] = col_edge[j] ? real_t(0.0) : real_t(0.25);
+        qc[j] = col_edge[j] ? real_t(0.0) : (WT ? p.cw : real_t(0.25));
     }
     // error norm (:610/:617): interior points with (row + col) even, each counted by the lane that owns it: as bit
     // masks per lane and row parity (AND-ed onto |r|, so a NaN in a row that is not counted cannot leak in)
@@ -876,7 +881,10 @@ void k_jacobi_stream(const StreamParams p)
                         for (int j = 0; j < COLS; ++j) {
                             // q*(0 - dx2*F) + 0: `0 - p` is -p exactly, and whichever zero the product is, adding +0 gives +0:
                             // the negation rides on the fma's operand instead of costing a subtraction
-                            o.v[j] = fused_mul_add(hi_bits_and(qc[j], inner), -g.v[j], real_t(0.0));
+                            // (WT: cw*(0 - dx2*F) + 0, the product rounded once -- the same as the fma; cw is no power of two,
+                            // so the rim rows take their zero weight from a select)
+                            if constexpr (WT) o.v[j] = fused_mul_add(inner ? qc[j] : real_t(0.0), -g.v[j], real_t(0.0));
+                            else o.v[j] = fused_mul_add(hi_bits_and(qc[j], inner), -g.v[j], real_t(0.0));
                         }
                         older[l - 1] = c;
                         newer[l - 1] = nw;
@@ -897,7 +905,9 @@ void k_jacobi_stream(const StreamParams p)
                     // `U + 0.25*t` through one fma as well: the product with a power of two is exact, so the fused form
                     // rounds once exactly like the sum does; with q = 0 on the rim (row or column) the point keeps its
                     // value, which replaces the rim selects
-                    o.v[j] = fused_mul_add(hi_bits_and(qc[j], inner), t4, c.v[j]);
+                    // WT: U + (cw*t) rounded twice: cw is no power of two, its product is not exact
+                    if constexpr (WT) o.v[j] = c.v[j] + (inner ? qc[j] : real_t(0.0)) * t4;
+                    else o.v[j] = fused_mul_add(hi_bits_and(qc[j], inner), t4, c.v[j]);
                 }
                 older[l - 1] = c;
                 newer[l - 1] = nw;
@@ -1090,13 +1100,13 @@ void k_jacobi_stream(const StreamParams p)
 // One launch: tile the grid for ONE resident round of workgroups (measured occupancy of
 // this instantiation x CUs) where the grid is large enough, never fewer than 8 rows per
 // chunk (each chunk re-reads 2(S+1) halo rows), then the fixed-order error reduction.
-template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0>
+template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false>
 void launch_k(hipStream_t s, StreamParams p, double *err_out)
 {
     static int blocks_per_cu = 0;
     if (blocks_per_cu == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE>, 64 * WAVES_PER_WG, 0) != hipSuccess || n < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT>, 64 * WAVES_PER_WG, 0) != hipSuccess || n < 1) {
             (void)hipGetLastError();
             n = 2;
         }
@@ -1148,7 +1158,7 @@ void launch_k(hipStream_t s, StreamParams p, double *err_out)
     }
     p.part_stride = (int)n_part;
     const int grid = ((p.n_blocks + 7) / 8) * 8;   // (a multiple of 8: with x fastest in the dispatch order, x & 7 stays the XCD of a workgroup for every y)
-    hipLaunchKernelGGL((k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE>), dim3(grid, nb), dim3(64 * WAVES_PER_WG), 0, s, p);
+    hipLaunchKernelGGL((k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT>), dim3(grid, nb), dim3(64 * WAVES_PER_WG), 0, s, p);
 #ifdef MG_STREAM_TRACE
     {
         long long t[4];
@@ -1226,6 +1236,25 @@ void launch_variant(hipStream_t s, const StreamParams &p, double *err_out)
             return;
         }
     }
+    if constexpr (sizeof(real_t) == 8) {
+        if (p.wt) {   // the weighted sweep: the zero / load / fused restriction / fused prolongation forms, no recomputing pair
+            if (p.N % 2 != 0) {
+                if (zero) launch_k<S, 1, IN_ZERO, false, PF, false, 0, true>(s, p, err_out);
+                else launch_k<S, 1, IN_LOAD, false, PF, false, 0, true>(s, p, err_out);
+            } else if (restrict_out) {
+                if (zero) launch_k<S, 2, IN_ZERO, true, (PF == 2 && S <= 3 ? MG_PF_DOWN : PF), false, 0, true>(s, p, err_out);
+                else launch_k<S, 2, IN_LOAD, true, PF, false, 0, true>(s, p, err_out);
+            } else if (prolong_in) {
+                if (p.pre != 0) fail(MG_ERR_UNSUPPORTED, "jacobi_stream: no recomputing `1` node for the weighted sweep");
+                else if (nt) launch_k<S, 2, IN_PROLONG, false, PF, true, 0, true>(s, p, err_out);
+                else launch_k<S, 2, IN_PROLONG, false, PF, false, 0, true>(s, p, err_out);
+            } else {
+                if (zero) launch_k<S, 2, IN_ZERO, false, PF, false, 0, true>(s, p, err_out);
+                else launch_k<S, 2, IN_LOAD, false, PF, false, 0, true>(s, p, err_out);
+            }
+            return;
+        }
+    }
     if (p.N % 2 != 0) {  // 8 B lanes: odd row pitch; the fused transfer stages are not built for it
         if (zero) launch_k<S, 1, IN_ZERO, false, PF>(s, p, err_out);
         else launch_k<S, 1, IN_LOAD, false, PF>(s, p, err_out);
@@ -1280,7 +1309,8 @@ void launch_steps(hipStream_t s, const StreamParams &p, double *err_out)
 inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, const real_t *F, real_t *out, int steps,
                 double *err_out, real_t *D_out, int d_sign, const real_t *coarse, int Nc, real_t *Fc, int M,
                 const StreamTables &tb, const RowWindow *fine_w, const RowWindow *coarse_w, const RowWindow *fc_w,
-                double *out_wide = nullptr, int pre = 0, bool no_out = false, const NodeBatch *batch = nullptr)
+                double *out_wide = nullptr, int pre = 0, bool no_out = false, const NodeBatch *batch = nullptr,
+                double cw = 0.25)
 {
     if (batch && (fine_w || coarse_w || fc_w || D_out || out_wide || batch->n < 1)) {
         fail(MG_ERR_ARG, "jacobi_stream: a batch of instances runs whole grids without a stored residual");
@@ -1288,6 +1318,10 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
     }
     if (pre != 0 && !(recompute_instantiated(pre, steps) && coarse && !Fc)) {
         fail(MG_ERR_ARG, "jacobi_stream: recomputed pre-smoothing exists for pre + steps <= 6 sweeps of the fused `1` node (pre=%d steps=%d)", pre, steps);
+        return;
+    }
+    if (cw != 0.25 && (pre != 0 || batch || sizeof(real_t) != 8)) {
+        fail(MG_ERR_ARG, "jacobi_stream: the weighted sweep runs fp64 nodes that store and re-read U, one instance");
         return;
     }
     if (pre != 0 && D_out) {
@@ -1317,6 +1351,8 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
     p.out_wide = out_wide;
     p.pre = pre;
     p.no_out = no_out ? 1 : 0;
+    p.cw = (real_t)cw;
+    p.wt = cw != 0.25 ? 1 : 0;   // (0.25: the unweighted instantiations, the same bits: the product with 0.25 is exact)
     p.D = D_out;
     p.d_sign = d_sign;
     p.row_base = fine_w ? fine_w->base : 0;
