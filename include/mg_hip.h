@@ -382,6 +382,38 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *o);
 int        mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_result *out);
 void       mg_solver_destroy(mg_solver *s);
 
+/* ------------------------------------------------------------------------- */
+/* batched residual-tolerance solver: B problems of one size and one set of   */
+/* options in one call, each solved exactly as mg_solver_solve solves it      */
+/* ------------------------------------------------------------------------- */
+/* Instance i gives the same U, cycles, status, converged, coarse_capped, res0, res, ref_norm and history, bit for bit, as
+ * mg_solver_solve on F_dev[i], U_dev[i] with the same options, whatever the other instances are and wherever it sits in
+ * the batch.  An instance leaves the batch once it meets its own tolerance max(rtol*||F_i||, atol); its U is never written
+ * after that (a start that meets it: 0 cycles, U untouched).  One cycle runs the single solve's launches ONCE over all
+ * active instances (blockIdx picks the instance): the launches per cycle do not depend on the batch size.  Several
+ * instances may share one F (the same source with different boundary values). */
+typedef struct mg_batch_solve_stats {
+    int    cycles;             /* the most cycles any instance ran */
+    int    launches;           /* kernel launches the call enqueued */
+    double device_ms;          /* hipEvent time of the whole call */
+} mg_batch_solve_stats;
+
+typedef struct mg_batch_solver mg_batch_solver;
+
+/* every level array for max_batch instances, the per-instance norm partials and scalars and the pinned read-back buffers
+ * are allocated here (NULL opts: the defaults; the options are checked as mg_solver_create checks them) */
+mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg_solve_opts *o);
+/* F_dev[i], U_dev[i]: host arrays of n device pointers to N x N arrays (each 16-byte aligned), 1 <= n <= max_batch; no two
+ * U arrays overlap and no U overlaps an F (F pointers may repeat).  out: n results (out[i].device_ms: the whole call;
+ * out[i].history: owned by the batch solver, valid until its next solve); stats may be NULL.  Allocates nothing, works on
+ * the engine stream and reads the n norms back once per cycle in one copy.  Returns MG_SOLVE_CONVERGED when every
+ * instance converged, MG_SOLVE_NOT_CONVERGED when at least one did not, an error code (> 0) otherwise (MG_ERR_ARG for bad
+ * arguments, before anything is enqueued).  The cycle runs through batched launches of the fused nodes; with
+ * mg_set_smoother("simple") operator by operator, instance by instance -- the same bits. */
+int  mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev, double *const *U_dev, mg_solve_result *out,
+                           mg_batch_solve_stats *stats);
+void mg_batch_solver_destroy(mg_batch_solver *s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,10 @@ class SolveResult(C.Structure):
                 ("n_history", C.c_int), ("history", _dptr)]
 
 
+class BatchSolveStats(C.Structure):
+    _fields_ = [("cycles", C.c_int), ("launches", C.c_int), ("device_ms", C.c_double)]
+
+
 MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED = 0, -1
 
 # every symbol include/mg_hip.h declares: name -> (restype, argtypes)
@@ -110,6 +114,9 @@ ABI = {
     "mg_solve_opts_default": (None, [C.POINTER(SolveOpts)]),
     "mg_solver_create": (_vp, [_i, _d, C.POINTER(SolveOpts)]),
     "mg_solver_solve": (_i, [_vp, _vp, _vp, C.POINTER(SolveResult)]), "mg_solver_destroy": (None, [_vp]),
+    "mg_batch_solver_create": (_vp, [_i, _d, _i, C.POINTER(SolveOpts)]),
+    "mg_batch_solver_solve": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(BatchSolveStats)]),
+    "mg_batch_solver_destroy": (None, [_vp]),
     "mg_profile_begin": (None, [_i]), "mg_profile_sample": (None, [_i]), "mg_profile_end": (_i, [C.POINTER(ProfileEntry), _i]),
 }
 
@@ -869,6 +876,180 @@ def solve(F, U=None, L=1.0, **opts):
     rounding floor of large grids: about 8e-10 at N = 8192)."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
+    try:
+        return s.solve(F, U)
+    finally:
+        s.close()
+
+
+def _instances(X, what):
+    """[B, N, N] array / tensor or a list of (N, N) ones -> list of instances; a single (N, N) one -> [it] (broadcast)."""
+    if isinstance(X, (list, tuple)):
+        return list(X), False
+    if len(X.shape) == 3:
+        return [X[i] for i in range(X.shape[0])], False
+    if len(X.shape) == 2:
+        return [X], True
+    raise MGError(f"{what}: expected [B, N, N], (N, N) or a list of (N, N) arrays, got shape {tuple(X.shape)}")
+
+
+class BatchSolver:
+    """Batched residual-tolerance solver of include/mg_hip.h: up to max_batch problems of size N with one set of options
+    (see solve_opts) in one call, every instance bit-identical to a Solver solve of it alone (U, history, cycles, status).
+    An instance stops once it meets its own tolerance; one cycle is one launch per node over all active instances.
+    Every level array for max_batch instances is allocated here; solve() allocates nothing on the device."""
+
+    def __init__(self, N, L=1.0, max_batch=64, **opts):
+        self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
+        self.opts = solve_opts(**opts)
+        self._s = lib().mg_batch_solver_create(self.N, self.L, self.max_batch, C.byref(self.opts))
+        if not self._s:
+            _check()
+            raise MGError("mg_batch_solver_create returned NULL")
+
+    def solve_ptrs(self, F_ptrs, U_ptrs):
+        """F_ptrs, U_ptrs: sequences of device addresses of N x N fp64 arrays (16-byte aligned; F addresses may repeat),
+        on the engine stream.  Returns one info dict per instance (the keys of Solver.solve_ptr, plus `stats` of the
+        call: cycles = the most any instance ran, launches, device_ms)."""
+        n = len(U_ptrs)
+        if len(F_ptrs) != n:
+            raise MGError(f"{len(F_ptrs)} F pointers for {n} U pointers")
+        Fa = (C.c_void_p * max(n, 1))(*F_ptrs)
+        Ua = (C.c_void_p * max(n, 1))(*U_ptrs)
+        res = (SolveResult * max(n, 1))()
+        st = BatchSolveStats()
+        status = _lib.mg_batch_solver_solve(self._s, n, Fa, Ua, res, C.byref(st))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_batch_solver_solve failed with status {status}")
+        stats = dict(status=status, cycles=st.cycles, launches=st.launches, device_ms=st.device_ms)
+        out = []
+        for r in res[:n]:
+            out.append(dict(status=r.status, cycles=r.cycles, converged=bool(r.converged), coarse_capped=bool(r.coarse_capped),
+                            res0=r.res0, res=r.res, ref_norm=r.ref_norm, device_ms=r.device_ms,
+                            history=[r.history[i] for i in range(r.n_history)], stats=stats))
+        return out
+
+    def solve(self, F, U=None):
+        """F, U: numpy arrays [B, N, N], float64 torch CUDA tensors [B, N, N] (contiguous; worked on in place, on
+        torch.cuda.current_stream()), or lists of B (N, N) arrays / tensors / DeviceGrids.  A single (N, N) F serves
+        every instance (one shared array, no copy).  U = None starts from zero (zero rim).  Returns (U, infos); numpy
+        input comes back as a new numpy array [B, N, N].  Torch instances that are not 16-byte aligned -- every odd
+        instance of a contiguous [B, N, N] tensor with N odd -- go through a staging buffer whose instance pitch is
+        N*N + 1 doubles (copied in and back on the same stream)."""
+        if _is_torch(F if not isinstance(F, (list, tuple)) else F[0]) or \
+                (U is not None and _is_torch(U if not isinstance(U, (list, tuple)) else U[0])):
+            return self._solve_torch(F, U)
+        return self._solve_host(F, U)
+
+    def _solve_torch(self, F, U):
+        import torch
+        N = self.N
+        Fs, shared = _instances(F, "F")
+        if U is None:
+            U = torch.zeros((1 if shared else len(Fs), N, N), dtype=torch.float64, device=Fs[0].device)
+        Us, _ = _instances(U, "U")
+        if shared:
+            Fs = Fs * len(Us)
+        if len(Fs) != len(Us):
+            raise MGError(f"{len(Fs)} F instances for {len(Us)} U instances")
+        for name, ts in (("F", Fs), ("U", Us)):
+            for t in ts:
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                        and t.is_contiguous()):
+                    raise MGError(f"{name}: expected contiguous float64 CUDA tensors of shape ({N}, {N})")
+        dev = Us[0].device
+        stream = torch.cuda.current_stream(dev)
+        nn, B = N * N, len(Us)
+
+        def staged(ts, share):
+            """device addresses of ts, through a staging buffer of pitch N*N + 1 when one of them is not 16-byte aligned"""
+            if all(t.data_ptr() % 16 == 0 for t in ts):
+                return [t.data_ptr() for t in ts], None
+            if share:
+                buf = torch.empty((1, nn + 1), dtype=torch.float64, device=dev)
+                buf[0, :nn].copy_(ts[0].reshape(-1))
+                return [buf.data_ptr()] * len(ts), buf
+            buf = torch.empty((len(ts), nn + 1), dtype=torch.float64, device=dev)
+            for i, t in enumerate(ts):
+                buf[i, :nn].copy_(t.reshape(-1))
+            return [buf[i].data_ptr() for i in range(len(ts))], buf
+
+        F_ptrs, Fbuf = staged(Fs, shared)
+        U_ptrs, Ubuf = staged(Us, False)
+        prev = _lib.mg_get_stream()
+        _lib.mg_set_stream(stream.cuda_stream)
+        try:
+            infos = self.solve_ptrs(F_ptrs, U_ptrs)
+        finally:
+            _lib.mg_set_stream(prev)
+        if Ubuf is not None:
+            for i in range(B):
+                Us[i].copy_(Ubuf[i, :nn].view(N, N))
+        del Fbuf
+        return U, infos
+
+    def _solve_host(self, F, U):
+        N = self.N
+        keep = []
+
+        def dev(a, what):
+            if isinstance(a, DeviceGrid):
+                if a.shape != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        if isinstance(F, DeviceGrid):
+            Fs, shared = [F], True
+        else:
+            Fs, shared = _instances(F if isinstance(F, (list, tuple)) else np.asarray(F), "F")
+        Fd = [dev(f, "F") for f in Fs]
+        if U is None:
+            B = 1 if shared else len(Fd)
+            Ud = [DeviceGrid.zeros((N, N)) for _ in range(B)]
+            host_U = True
+        else:
+            Us = [U] if isinstance(U, DeviceGrid) else _instances(U if isinstance(U, (list, tuple)) else np.asarray(U), "U")[0]
+            host_U = not all(isinstance(u, DeviceGrid) for u in Us)
+            Ud = [dev(u, "U") for u in Us]
+        if shared:
+            Fd = Fd * len(Ud)
+        if len(Fd) != len(Ud):
+            raise MGError(f"{len(Fd)} F instances for {len(Ud)} U instances")
+        infos = self.solve_ptrs([f.ptr for f in Fd], [u.ptr for u in Ud])
+        if host_U:
+            return np.stack([u.to_host() for u in Ud]), infos
+        return Ud, infos
+
+    def close(self):
+        if getattr(self, "_s", None) and _initialised:
+            _lib.mg_batch_solver_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def solve_batched(F, U=None, L=1.0, **opts):
+    """Solve B Poisson problems of one size to the residual tolerance in one batched call; returns (U, infos).  F: [B, N, N]
+    (or a list, or one (N, N) F shared by every instance when U gives B), U: the initial guesses with their Dirichlet rims
+    (None: zero).  See BatchSolver for the accepted types and solve_opts for the defaults."""
+    Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
+    if U is None:
+        B = 1 if shared else len(Fs)
+    else:
+        B = len(U) if isinstance(U, (list, tuple)) else (1 if isinstance(U, DeviceGrid) or len(U.shape) == 2 else int(U.shape[0]))
+    N = int(Fs[0].shape[-1])
+    s = BatchSolver(N, L, max_batch=max(B, 1), **opts)
     try:
         return s.solve(F, U)
     finally:

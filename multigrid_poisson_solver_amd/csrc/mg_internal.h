@@ -286,7 +286,7 @@ void jacobi_stream(hipStream_t s, int N, double dx2, double inv, const double *i
                    // node's shape -- which of them a node of this kind has -- and err_out is ignored)
                    const NodeBatch *batch = nullptr,
                    // cw != 0.25: the weighted sweep U + (cw*t) of the residual-tolerance solver (cw = 0.25*omega, fp64, no
-                   // recomputing pair, no batch); 0.25 is the reference's sweep
+                   // recomputing pair; a batch: the batched solver); 0.25 is the reference's sweep
                    double cw = 0.25);
 // register-tile fused nodes of the small levels (mg_tile.hip / mg_tile_f32.hip): one launch = level 0 (zero | in | in +
 // P(coarse)), `steps` sweeps, the error norm, optionally the d_sign-ed residual restricted into Fc; whole grid only
@@ -386,7 +386,33 @@ constexpr int GS_RELATIVE_MAX_N = 64;
 bool gs_relative_fits(int N);
 void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double atol, double rtol,
                            int max_iters, int *state, double *err_out);
+// the same kernels on n instances of one size in ONE launch each (batched solver, mg_solve_batch.cpp): items[i] (device
+// memory) holds instance i's arrays, each instance runs exactly the code and the partition of its single-instance form.
+// resnorm_batch: in = U (has_u), F; out[i] = its norm, its partials at part + i*resnorm_partials(N)
+void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out);
+// out = U, F; instance i's state at state + 4i (no err_out)
+void gauss_seidel_relative_batch(hipStream_t s, int n, int N, double h2, double inv, const NodeBatchItem *items, double atol,
+                                 double rtol, int max_iters, int *state);
+// residual (in = U, F, out = D), restriction N -> M (in -> out), out = in + prolongation of coarse (N -> M), copy in -> out
+void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign);
+void restrict_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const RestrictTable &t, int sign);
+void prolong_add_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const ProlongTable &t);
+void copy_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items);
 }  // namespace k
+
+// residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
+bool solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o);
+// the arrays of one instance's hierarchy (level 0: the caller's F and U, only B[0] is used)
+struct SolveLevels {
+    const std::vector<int> *sizes;
+    double L;
+    const mg_solve_opts *o;
+    std::vector<double *> A, B, F;
+    int *gs_state;
+    double *gs_err;   // may be nullptr
+};
+// one V(pre, post) cycle operator by operator (MG_SMOOTHER=simple); returns the kernel launches it enqueued
+int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

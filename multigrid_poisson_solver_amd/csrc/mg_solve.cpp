@@ -30,31 +30,31 @@ namespace {
 
 bool finite(double v) { return std::isfinite(v); }
 
-bool opts_ok(int N, double L, const mg_solve_opts &o)
+bool opts_ok(const char *who, int N, double L, const mg_solve_opts &o)
 {
-    if (!(L > 0.0) || !finite(L)) { fail(MG_ERR_ARG, "mg_solver_create: L = %g must be positive and finite", L); return false; }
-    if (o.N_min < 3 || o.N_min > 32) { fail(MG_ERR_ARG, "mg_solver_create: N_min = %d outside [3, 32]", o.N_min); return false; }
+    if (!(L > 0.0) || !finite(L)) { fail(MG_ERR_ARG, "%s: L = %g must be positive and finite", who, L); return false; }
+    if (o.N_min < 3 || o.N_min > 32) { fail(MG_ERR_ARG, "%s: N_min = %d outside [3, 32]", who, o.N_min); return false; }
     if (N < 2 * o.N_min) {
-        fail(MG_ERR_ARG, "mg_solver_create: N = %d needs at least two levels (N >= 2*N_min = %d)", N, 2 * o.N_min);
+        fail(MG_ERR_ARG, "%s: N = %d needs at least two levels (N >= 2*N_min = %d)", who, N, 2 * o.N_min);
         return false;
     }
     if (o.pre < 1 || o.pre > 4 || o.post < 1 || o.post > 4) {
-        fail(MG_ERR_ARG, "mg_solver_create: pre = %d / post = %d sweeps outside [1, 4]", o.pre, o.post);
+        fail(MG_ERR_ARG, "%s: pre = %d / post = %d sweeps outside [1, 4]", who, o.pre, o.post);
         return false;
     }
-    if (!(o.omega > 0.0 && o.omega <= 1.0)) { fail(MG_ERR_ARG, "mg_solver_create: omega = %g outside (0, 1]", o.omega); return false; }
+    if (!(o.omega > 0.0 && o.omega <= 1.0)) { fail(MG_ERR_ARG, "%s: omega = %g outside (0, 1]", who, o.omega); return false; }
     if (!(o.coarse_rtol >= 0.0) || !(o.coarse_atol >= 0.0) || !finite(o.coarse_rtol) || !finite(o.coarse_atol) ||
         !(o.coarse_rtol > 0.0 || o.coarse_atol > 0.0)) {
-        fail(MG_ERR_ARG, "mg_solver_create: coarse_rtol = %g, coarse_atol = %g (non-negative, finite, not both zero)", o.coarse_rtol,
+        fail(MG_ERR_ARG, "%s: coarse_rtol = %g, coarse_atol = %g (non-negative, finite, not both zero)", who, o.coarse_rtol,
              o.coarse_atol);
         return false;
     }
-    if (o.coarse_max_iters < 1) { fail(MG_ERR_ARG, "mg_solver_create: coarse_max_iters = %d < 1", o.coarse_max_iters); return false; }
+    if (o.coarse_max_iters < 1) { fail(MG_ERR_ARG, "%s: coarse_max_iters = %d < 1", who, o.coarse_max_iters); return false; }
     if (!(o.rtol >= 0.0) || !(o.atol >= 0.0) || !finite(o.rtol) || !finite(o.atol)) {
-        fail(MG_ERR_ARG, "mg_solver_create: rtol = %g, atol = %g must be non-negative and finite", o.rtol, o.atol);
+        fail(MG_ERR_ARG, "%s: rtol = %g, atol = %g must be non-negative and finite", who, o.rtol, o.atol);
         return false;
     }
-    if (o.max_cycles < 0) { fail(MG_ERR_ARG, "mg_solver_create: max_cycles = %d < 0", o.max_cycles); return false; }
+    if (o.max_cycles < 0) { fail(MG_ERR_ARG, "%s: max_cycles = %d < 0", who, o.max_cycles); return false; }
     return true;
 }
 
@@ -86,55 +86,68 @@ bool dev_alloc(T **p, size_t n)
     return MG_HIP(hipMalloc((void **)p, n * sizeof(T)));
 }
 
+}  // namespace
+
 // one V(pre, post) cycle from the caller's U (level 0 keeps its guess; coarser levels start from zero), operator by
-// operator: one launch per sweep (MG_SMOOTHER=simple, and the yardstick of the fused cycle below)
-void vcycle_simple(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+// operator: one launch per sweep (MG_SMOOTHER=simple, and the yardstick of the fused cycle below); the launches it enqueued
+int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0)
 {
-    const mg_solve_opts &o = s->o;
-    const int nl = (int)s->sizes.size();
+    const mg_solve_opts &o = *lv.o;
+    const std::vector<int> &sizes = *lv.sizes;
+    const int nl = (int)sizes.size();
+    int launches = 0;
     const double cw = 0.25 * o.omega;
     std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
     for (int l = 0; l + 1 < nl; ++l) {
-        const int N = s->sizes[l], M = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L);
-        const double *F = l == 0 ? F0 : s->F[l];
-        double *cur = l == 0 ? U0 : s->A[l], *other = s->B[l];
+        const int N = sizes[l], M = sizes[l + 1];
+        const double dx2 = spacing_sq(N, lv.L);
+        const double *F = l == 0 ? F0 : lv.F[l];
+        double *cur = l == 0 ? U0 : lv.A[l], *other = lv.B[l];
         int sweeps = o.pre;
         if (l > 0) {   // memset(U, 0) (:256) folded into the first sweep
             k::wjacobi(st, N, dx2, cw, nullptr, F, cur);
+            ++launches;
             --sweeps;
         }
         for (int i = 0; i < sweeps; ++i) {
             k::wjacobi(st, N, dx2, cw, cur, F, other);
+            ++launches;
             std::swap(cur, other);
         }
         // D = -getResidual(U) (:268, :277-280) into the free field, F_c = doRestriction(D) (:287)
         k::residual(st, N, 1.0 / dx2, cur, F, other, -1);
-        k::restrict_gather(st, N, other, M, s->F[l + 1], restrict_table(N, M), +1);
+        k::restrict_gather(st, N, other, M, lv.F[l + 1], restrict_table(N, M), +1);
+        launches += 2;
         x[l] = cur;
         y[l] = other;
     }
-    const int Nc = s->sizes[nl - 1];
-    const double h2 = spacing_sq(Nc, s->L);
-    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
-                             s->gs_state, s->dev_scal + 2);
-    x[nl - 1] = s->A[nl - 1];
+    const int Nc = sizes[nl - 1];
+    const double h2 = spacing_sq(Nc, lv.L);
+    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, lv.A[nl - 1], lv.F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                             lv.gs_state, lv.gs_err);
+    ++launches;
+    x[nl - 1] = lv.A[nl - 1];
     for (int l = nl - 2; l >= 0; --l) {
-        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L);
-        const double *F = l == 0 ? F0 : s->F[l];
+        const int N = sizes[l], Nc_l = sizes[l + 1];
+        const double dx2 = spacing_sq(N, lv.L);
+        const double *F = l == 0 ? F0 : lv.F[l];
         double *cur = x[l], *other = y[l];
         // U = U + doProlongation(U_c) (:354, :368) into the free field
         k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
+        ++launches;
         std::swap(cur, other);
         for (int i = 0; i < o.post; ++i) {
             k::wjacobi(st, N, dx2, cw, cur, F, other);
+            ++launches;
             std::swap(cur, other);
         }
         x[l] = cur;
     }
-    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)s->N * s->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)sizes[0] * sizes[0] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return launches;
 }
+
+namespace {
 
 // the same cycle through the fused nodes of the streaming smoother (its weighted instantiations): per level one `-1`
 // launch (all pre sweeps + the restricted residual) and one `1` launch (prolongation-add + all post sweeps) where the
@@ -192,7 +205,8 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 {
-    if (ctx().smoother == SMOOTHER_SIMPLE) vcycle_simple(s, st, F0, U0);
+    if (ctx().smoother == SMOOTHER_SIMPLE)
+        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0);
     else vcycle_fused(s, st, F0, U0);
 }
 
@@ -211,6 +225,8 @@ bool read_back(mg_solver *s, hipStream_t st)
 }
 
 }  // namespace
+
+bool mg::solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o) { return opts_ok(who, N, L, o); }
 
 extern "C" {
 
@@ -235,7 +251,7 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
     mg_solve_opts o;
     mg_solve_opts_default(&o);
     if (opts) o = *opts;
-    if (!opts_ok(N, L, o)) return nullptr;
+    if (!solve_opts_ok("mg_solver_create", N, L, o)) return nullptr;
     mg_solver *s = new mg_solver;
     s->N = N;
     s->L = L;

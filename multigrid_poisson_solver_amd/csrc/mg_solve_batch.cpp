@@ -1,0 +1,398 @@
+// mg_solve_batch.cpp -- batched residual-tolerance solver (include/mg_hip.h, "batched residual-tolerance solver"): n
+// problems of one size and one set of options in one call, each instance bit-identical to mg_solver_solve alone.
+// One cycle follows vcycle_fused's node order and choices (mg_solve.cpp) for all active instances together: each launch
+// of the single cycle becomes ONE launch over the active set, the instance taken from a NodeBatchItem table by blockIdx
+// (the weighted streaming nodes, mg_stream_impl.h; the norm, coarse solve and transfer kernels, mg_solve_kernels.hip).
+// After each read-back the host drops the instances that met their tolerance from the active set and rebuilds and
+// uploads the tables when the set changed (the read-back already synchronises once per cycle, so one pinned staging
+// buffer serves every upload).
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mg_internal.h"
+
+using namespace mg;
+
+struct mg_batch_solver {
+    int N = 0;
+    double L = 1.0;
+    int max_batch = 0;
+    mg_solve_opts o{};
+    std::vector<int> sizes;                  // N, N/2, ... >= N_min
+    std::vector<size_t> pitch;               // doubles from one instance's level array to the next one's
+    std::vector<double *> A, B, F;           // per level, max_batch instances each (level 0: only B)
+    double *part = nullptr;                  // norm partials, resnorm_partials(N) per instance
+    void *dev_rb = nullptr, *host_rb = nullptr;   // read-back block: res[max_batch], ref[max_batch], gs_state[4*max_batch]
+    NodeBatchItem *dev_tab = nullptr, *host_tab = nullptr;   // [n_tables][max_batch]
+    int n_tables = 0;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_sync = nullptr;
+    std::vector<std::vector<double>> history;   // per instance of the last solve
+};
+
+namespace {
+
+double spacing_sq(int N, double L)
+{
+    const double dx = L / (double)(N - 1);
+    return dx * dx;
+}
+
+size_t rb_bytes(int mb) { return (size_t)mb * (2 * sizeof(double) + 4 * sizeof(int)); }
+double *rb_res(void *rb) { return static_cast<double *>(rb); }
+double *rb_ref(void *rb, int mb) { return static_cast<double *>(rb) + mb; }
+int *rb_state(void *rb, int mb) { return reinterpret_cast<int *>(static_cast<double *>(rb) + 2 * (size_t)mb); }
+
+// table slots of one cycle, in launch order: the norm, per level on the way down the node (+0), residual (+1) and
+// restriction (+2), the coarse solve, per level on the way up the node (+0) and prolongation (+1), the final copy
+int t_down(int l) { return 1 + 3 * l; }
+int t_gs(int nl) { return 1 + 3 * (nl - 1); }
+int t_up(int nl, int l) { return 2 + 3 * (nl - 1) + 2 * l; }
+int t_copy(int nl) { return 2 + 5 * (nl - 1); }
+int n_tables(int nl) { return 3 + 5 * (nl - 1); }
+
+bool down_fused(const mg_batch_solver *s, int l)
+{
+    return k::stream_fusable(s->sizes[l]) && restrict_table(s->sizes[l], s->sizes[l + 1]).fusable;
+}
+bool up_fused(const mg_batch_solver *s, int l)
+{
+    return k::stream_fusable(s->sizes[l]) && prolong_table(s->sizes[l + 1], s->sizes[l]).fusable;
+}
+
+double *level(const mg_batch_solver *s, const std::vector<double *> &v, int l, int i) { return v[l] + (size_t)i * s->pitch[l]; }
+
+void release(mg_batch_solver *s)
+{
+    for (double *p : s->A) if (p) (void)hipFree(p);
+    for (double *p : s->B) if (p) (void)hipFree(p);
+    for (double *p : s->F) if (p) (void)hipFree(p);
+    if (s->part) (void)hipFree(s->part);
+    if (s->dev_rb) (void)hipFree(s->dev_rb);
+    if (s->host_rb) (void)hipHostFree(s->host_rb);
+    if (s->dev_tab) (void)hipFree(s->dev_tab);
+    if (s->host_tab) (void)hipHostFree(s->host_tab);
+    if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
+    if (s->ev_end) (void)hipEventDestroy(s->ev_end);
+    if (s->ev_sync) (void)hipEventDestroy(s->ev_sync);
+    delete s;
+}
+
+// the arrays of instance i (active slot j) in every launch of one cycle: vcycle_fused's dataflow
+void fill_tables(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
+{
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * mb + j]; };
+    std::vector<double *> x(nl);
+    item(0) = NodeBatchItem{U0, F0, nullptr, nullptr, nullptr};
+    for (int l = 0; l + 1 < nl; ++l) {
+        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
+        double *out = l == 0 ? level(s, s->B, 0, i) : level(s, s->A, l, i);
+        double *scratch = l == 0 ? U0 : level(s, s->B, l, i);
+        double *Fc = level(s, s->F, l + 1, i);
+        const bool fused = down_fused(s, l);
+        item(t_down(l)) = NodeBatchItem{l == 0 ? U0 : nullptr, F, nullptr, out, fused ? Fc : nullptr};
+        item(t_down(l) + 1) = NodeBatchItem{out, F, nullptr, scratch, nullptr};      // residual into the free field
+        item(t_down(l) + 2) = NodeBatchItem{scratch, nullptr, nullptr, Fc, nullptr};  // its restriction
+        x[l] = out;
+    }
+    item(t_gs(nl)) = NodeBatchItem{nullptr, level(s, s->F, nl - 1, i), nullptr, level(s, s->A, nl - 1, i), nullptr};
+    x[nl - 1] = level(s, s->A, nl - 1, i);
+    for (int l = nl - 2; l >= 0; --l) {
+        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
+        double *in = x[l], *out = l == 0 ? U0 : level(s, s->B, l, i);
+        if (up_fused(s, l)) {
+            item(t_up(nl, l)) = NodeBatchItem{in, F, x[l + 1], out, nullptr};
+            x[l] = out;
+        } else {
+            item(t_up(nl, l) + 1) = NodeBatchItem{in, nullptr, x[l + 1], out, nullptr};   // in + P(coarse) into `out`
+            item(t_up(nl, l)) = NodeBatchItem{out, F, nullptr, in, nullptr};              // the sweeps back into `in`
+            x[l] = in;
+        }
+    }
+    item(t_copy(nl)) = NodeBatchItem{x[0], nullptr, nullptr, U0, nullptr};
+}
+
+bool upload_tables(mg_batch_solver *s, hipStream_t st)
+{
+    return MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)s->n_tables * s->max_batch * sizeof(NodeBatchItem),
+                                 hipMemcpyHostToDevice, st));
+}
+
+// one V(pre, post) cycle of the n active instances whose tables are uploaded; returns the launches it enqueued
+int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
+{
+    const mg_solve_opts &o = s->o;
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    const double cw = 0.25 * o.omega;
+    const NodeBatchItem *h = s->host_tab, *d = s->dev_tab;   // (slot 0 of a host table: the shape of a node)
+    auto node = [&](int t) { return NodeBatch{n, d + (size_t)t * mb, nullptr}; };
+    int launches = 0;
+    for (int l = 0; l + 1 < nl; ++l) {
+        const int N = s->sizes[l], M = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const int t = t_down(l);
+        const NodeBatchItem &it = h[(size_t)t * mb];
+        const NodeBatch nb = node(t);
+        const RestrictTable &rt = restrict_table(N, M);
+        if (down_fused(s, l)) {
+            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.pre, nullptr, nullptr,
+                             -1, nullptr, 0, nullptr, (double *)it.Fc, M, &rt, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            launches += 1;
+        } else {
+            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.pre, nullptr, nullptr,
+                             -1, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            k::residual_batch(st, n, N, inv, d + (size_t)(t + 1) * mb, -1);
+            k::restrict_batch(st, n, N, M, d + (size_t)(t + 2) * mb, rt, +1);
+            launches += 3;
+        }
+    }
+    const int Nc = s->sizes[nl - 1];
+    const double h2 = spacing_sq(Nc, s->L);
+    k::gauss_seidel_relative_batch(st, n, Nc, h2, 1.0 / h2, d + (size_t)t_gs(nl) * mb, o.coarse_atol, o.coarse_rtol,
+                                   o.coarse_max_iters, rb_state(s->dev_rb, mb));
+    launches += 1;
+    bool copy = false;
+    for (int l = nl - 2; l >= 0; --l) {
+        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
+        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const int t = t_up(nl, l);
+        const NodeBatchItem &it = h[(size_t)t * mb];
+        const NodeBatch nb = node(t);
+        const ProlongTable &pt = prolong_table(Nc_l, N);
+        if (up_fused(s, l)) {
+            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.post, nullptr, nullptr,
+                             +1, (const double *)it.coarse, Nc_l, &pt, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            launches += 1;
+        } else {
+            k::prolong_add_batch(st, n, Nc_l, N, d + (size_t)(t + 1) * mb, pt);
+            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.post, nullptr, nullptr,
+                             +1, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            launches += 2;
+            copy = l == 0;   // the result is in B[0], not in the caller's U
+        }
+    }
+    if (copy) {
+        k::copy_batch(st, n, (size_t)s->N * s->N, d + (size_t)t_copy(nl) * mb);
+        launches += 1;
+    }
+    return launches;
+}
+
+// the same cycle operator by operator, instance by instance (MG_SMOOTHER=simple): the yardstick of the batched launches
+int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int> &act, const double *const *F0,
+                       double *const *U0)
+{
+    const int nl = (int)s->sizes.size();
+    int launches = 0;
+    for (size_t j = 0; j < act.size(); ++j) {
+        const int i = act[j];
+        SolveLevels lv{&s->sizes, s->L, &s->o, {}, {}, {}, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr};
+        for (int l = 0; l < nl; ++l) {
+            lv.A.push_back(level(s, s->A, l, i));
+            lv.B.push_back(level(s, s->B, l, i));
+            lv.F.push_back(level(s, s->F, l, i));
+        }
+        launches += solve_vcycle_simple(st, lv, F0[i], U0[i]);
+    }
+    return launches;
+}
+
+int norms(mg_batch_solver *s, hipStream_t st, int n, bool has_u, double *out)
+{
+    k::resnorm_batch(st, n, s->N, 1.0 / spacing_sq(s->N, s->L), has_u, s->dev_tab, s->part, out);
+    return 2;
+}
+
+bool read_back(mg_batch_solver *s, hipStream_t st)
+{
+    if (!MG_HIP(hipMemcpyAsync(s->host_rb, s->dev_rb, rb_bytes(s->max_batch), hipMemcpyDeviceToHost, st))) return false;
+    if (!MG_HIP(hipEventRecord(s->ev_sync, st))) return false;
+    return MG_HIP(hipEventSynchronize(s->ev_sync));
+}
+
+bool overlap(const void *a, const void *b, size_t bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg_solve_opts *opts)
+{
+    if (!require_ready("mg_batch_solver_create")) return nullptr;
+    mg_solve_opts o;
+    mg_solve_opts_default(&o);
+    if (opts) o = *opts;
+    if (!solve_opts_ok("mg_batch_solver_create", N, L, o)) return nullptr;
+    if (max_batch < 1 || max_batch > 65535) {
+        fail(MG_ERR_ARG, "mg_batch_solver_create: max_batch = %d outside [1, 65535]", max_batch);
+        return nullptr;
+    }
+    mg_batch_solver *s = new mg_batch_solver;
+    s->N = N;
+    s->L = L;
+    s->max_batch = max_batch;
+    s->o = o;
+    for (int n = N; n >= o.N_min; n /= 2) s->sizes.push_back(n);   // mg_solver_create's hierarchy
+    const int nl = (int)s->sizes.size();
+    if (!k::gs_relative_fits(s->sizes[nl - 1])) {
+        fail(MG_ERR_UNSUPPORTED, "mg_batch_solver_create: coarsest level %d does not fit the coarse solver", s->sizes[nl - 1]);
+        release(s);
+        return nullptr;
+    }
+    s->A.assign(nl, nullptr);
+    s->B.assign(nl, nullptr);
+    s->F.assign(nl, nullptr);
+    s->pitch.assign(nl, 0);
+    bool ok = true;
+    for (int l = 0; l < nl && ok; ++l) {
+        // (instance pitch rounded up to 256 B: every instance's rows start where a lone allocation's would)
+        s->pitch[l] = ((size_t)s->sizes[l] * s->sizes[l] + 31) / 32 * 32;
+        const size_t bytes = s->pitch[l] * max_batch * sizeof(double);
+        ok = MG_HIP(hipMalloc((void **)&s->B[l], bytes));
+        if (ok && l > 0) ok = MG_HIP(hipMalloc((void **)&s->A[l], bytes)) && MG_HIP(hipMalloc((void **)&s->F[l], bytes));
+    }
+    for (int l = 0; l + 1 < nl && ok; ++l) {
+        const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
+        ok = restrict_table(Nf, Nc).lo != nullptr && prolong_table(Nc, Nf).owner_row != nullptr;
+    }
+    s->n_tables = n_tables(nl);
+    const size_t tab_bytes = (size_t)s->n_tables * max_batch * sizeof(NodeBatchItem);
+    ok = ok && MG_HIP(hipMalloc((void **)&s->part, k::resnorm_partials(N) * max_batch * sizeof(double))) &&
+         MG_HIP(hipMalloc(&s->dev_rb, rb_bytes(max_batch))) &&
+         MG_HIP(hipHostMalloc(&s->host_rb, rb_bytes(max_batch), hipHostMallocDefault)) &&
+         MG_HIP(hipMalloc((void **)&s->dev_tab, tab_bytes)) &&
+         MG_HIP(hipHostMalloc((void **)&s->host_tab, tab_bytes, hipHostMallocDefault)) &&
+         MG_HIP(hipEventCreate(&s->ev_begin)) && MG_HIP(hipEventCreate(&s->ev_end)) &&
+         MG_HIP(hipEventCreateWithFlags(&s->ev_sync, hipEventDisableTiming));
+    ok = ok && MG_HIP(hipMemset(s->dev_rb, 0, rb_bytes(max_batch)));
+    if (!ok) {
+        release(s);
+        return nullptr;
+    }
+    std::memset(s->host_tab, 0, tab_bytes);
+    s->history.resize(max_batch);
+    for (auto &h : s->history) h.reserve((size_t)o.max_cycles + 1);
+    return s;
+}
+
+int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev, double *const *U_dev, mg_solve_result *out,
+                          mg_batch_solve_stats *stats)
+{
+    mg_batch_solve_stats bs;
+    std::memset(&bs, 0, sizeof bs);
+    std::vector<mg_solve_result> r(n > 0 ? (size_t)n : 0);
+    for (auto &x : r) std::memset(&x, 0, sizeof x);
+    auto finish = [&](int status) {
+        if (out && s && n >= 1 && n <= s->max_batch) {
+            for (int i = 0; i < n; ++i) {
+                if (status > 0) r[i].status = status;
+                r[i].device_ms = bs.device_ms;
+                r[i].n_history = (int)s->history[i].size();
+                r[i].history = s->history[i].empty() ? nullptr : s->history[i].data();
+                out[i] = r[i];
+            }
+        }
+        if (stats) *stats = bs;
+        return status;
+    };
+    if (!require_ready("mg_batch_solver_solve")) return finish(MG_ERR_NOT_INIT);
+    if (!s || !F_dev || !U_dev || !out) {
+        fail(MG_ERR_ARG, "mg_batch_solver_solve: NULL solver, array or result array");
+        return finish(MG_ERR_ARG);
+    }
+    if (n < 1 || n > s->max_batch) {
+        fail(MG_ERR_ARG, "mg_batch_solver_solve: n = %d outside [1, max_batch = %d]", n, s->max_batch);
+        return finish(MG_ERR_ARG);
+    }
+    for (int i = 0; i < n; ++i) s->history[i].clear();
+    const size_t bytes = (size_t)s->N * s->N * sizeof(double);
+    for (int i = 0; i < n; ++i) {
+        if (!F_dev[i] || !U_dev[i]) {
+            fail(MG_ERR_ARG, "mg_batch_solver_solve: NULL F or U of instance %d", i);
+            return finish(MG_ERR_ARG);
+        }
+        if (((uintptr_t)F_dev[i] | (uintptr_t)U_dev[i]) % 16 != 0) {
+            fail(MG_ERR_ARG, "mg_batch_solver_solve: F and U of instance %d must be 16-byte aligned", i);
+            return finish(MG_ERR_ARG);
+        }
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (j > i && overlap(U_dev[i], U_dev[j], bytes)) {
+                fail(MG_ERR_ARG, "mg_batch_solver_solve: U of instances %d and %d overlap", i, j);
+                return finish(MG_ERR_ARG);
+            }
+            if (overlap(U_dev[i], F_dev[j], bytes)) {
+                fail(MG_ERR_ARG, "mg_batch_solver_solve: U of instance %d overlaps F of instance %d", i, j);
+                return finish(MG_ERR_ARG);
+            }
+        }
+    const hipStream_t st = ctx().stream;
+    const mg_solve_opts &o = s->o;
+    const int mb = s->max_batch;
+    const bool simple = ctx().smoother == SMOOTHER_SIMPLE;
+    std::vector<int> act(n);
+    std::vector<double> tol(n);
+    for (int i = 0; i < n; ++i) act[i] = i;
+    auto build = [&]() {
+        for (size_t j = 0; j < act.size(); ++j) fill_tables(s, (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
+        return upload_tables(s, st);
+    };
+    if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
+    if (!build()) return finish(MG_ERR_HIP);
+    bs.launches += norms(s, st, n, false, rb_ref(s->dev_rb, mb));
+    bs.launches += norms(s, st, n, true, rb_res(s->dev_rb));
+    if (!read_back(s, st)) return finish(MG_ERR_HIP);
+    std::vector<int> next;
+    for (int i = 0; i < n; ++i) {
+        r[i].ref_norm = rb_ref(s->host_rb, mb)[i];
+        r[i].res0 = r[i].res = rb_res(s->host_rb)[i];
+        s->history[i].push_back(r[i].res);
+        tol[i] = std::fmax(o.rtol * r[i].ref_norm, o.atol);
+        if (!(r[i].res <= tol[i]) && o.max_cycles > 0) next.push_back(i);
+    }
+    while (!next.empty()) {
+        if (next != act) {   // the active set changed: compact it, rebuild and upload the tables
+            act.swap(next);
+            if (!build()) return finish(MG_ERR_HIP);
+        }
+        const int na = (int)act.size();
+        bs.launches += simple ? vcycle_simple_each(s, st, act, F_dev, U_dev) : vcycle_batch(s, st, na);
+        bs.launches += norms(s, st, na, true, rb_res(s->dev_rb));
+        if (!read_back(s, st)) return finish(MG_ERR_HIP);
+        next.clear();
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j];
+            r[i].res = rb_res(s->host_rb)[j];
+            s->history[i].push_back(r[i].res);
+            r[i].cycles += 1;
+            if (rb_state(s->host_rb, mb)[4 * j + 2]) r[i].coarse_capped = 1;
+            if (r[i].cycles > bs.cycles) bs.cycles = r[i].cycles;
+            if (!(r[i].res <= tol[i]) && r[i].cycles < o.max_cycles) next.push_back(i);
+        }
+    }
+    if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return finish(MG_ERR_HIP);
+    float ms = 0.0f;
+    if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) bs.device_ms = ms;
+    bool all = true;
+    for (int i = 0; i < n; ++i) {
+        r[i].converged = r[i].res <= tol[i] ? 1 : 0;
+        r[i].status = r[i].converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED;
+        all = all && r[i].converged;
+    }
+    return finish(all ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED);
+}
+
+void mg_batch_solver_destroy(mg_batch_solver *s)
+{
+    if (!s) return;
+    if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+    release(s);
+}
+
+}  // extern "C"

@@ -4,6 +4,9 @@
 // separately, and every bracket keeps the reference's association order (src/MG_solver_CPU.cpp:590, :1020, :560).
 // The sweeps here are the operator-by-operator form (MG_SMOOTHER=simple); the default cycle runs the weighted
 // instantiations of the streaming smoother (mg_stream_impl.h, WT).
+// The batched solver (mg_solve_batch.cpp) runs the norm, the coarse solve and the transfer operators of its non-fusable
+// levels on all active instances in one launch each: the `_b` kernels below take every instance's arrays from a
+// NodeBatchItem table in device memory and run, per instance, the same code as their single-instance forms.
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"
@@ -131,9 +134,10 @@ __global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double 
 // ---------------------------------------------------------------- residual L2 norm
 // per-block partial sums of d^2 over interior points, d = inv*(star - 4U) - F (getResidual's value, :560);
 // HAS_U = false: U == 0, d = -F (the reference norm ||F||).  Nothing but the partials is written.
+// (the bodies are shared with the batched forms: the same partition into partials for every instance)
 template <bool HAS_U>
-__global__ __launch_bounds__(TB) void k_resnorm(int N, double inv, const double *__restrict__ U,
-                                                const double *__restrict__ F, double *__restrict__ part)
+__device__ __forceinline__ void resnorm_body(int N, double inv, const double *__restrict__ U, const double *__restrict__ F,
+                                             double *__restrict__ part)
 {
     const int c = blockIdx.x * TB + threadIdx.x;
     const int r0 = blockIdx.y * ROWS_PB;
@@ -153,11 +157,18 @@ __global__ __launch_bounds__(TB) void k_resnorm(int N, double inv, const double 
     if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
+template <bool HAS_U>
+__global__ __launch_bounds__(TB) void k_resnorm(int N, double inv, const double *__restrict__ U,
+                                                const double *__restrict__ F, double *__restrict__ part)
+{
+    resnorm_body<HAS_U>(N, inv, U, F, part);
+}
+
 // even N >= PAIR_MIN_N: 16 B per lane, PR rows per thread with a rolling window of three row pairs (every row of U read
 // once), F through 16-byte (non-temporal from NT_MIN_N on) loads -- 16 B of HBM traffic per point
 template <bool HAS_U, bool NT>
-__global__ __launch_bounds__(TB) void k_resnorm_pairs(int N, double inv, const double *__restrict__ U,
-                                                      const double *__restrict__ F, double *__restrict__ part)
+__device__ __forceinline__ void resnorm_pairs_body(int N, double inv, const double *__restrict__ U,
+                                                   const double *__restrict__ F, double *__restrict__ part)
 {
     const int c = 2 * (blockIdx.x * TB + threadIdx.x);
     const int r0 = blockIdx.y * PR;
@@ -199,13 +210,49 @@ __global__ __launch_bounds__(TB) void k_resnorm_pairs(int N, double inv, const d
     if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
+template <bool HAS_U, bool NT>
+__global__ __launch_bounds__(TB) void k_resnorm_pairs(int N, double inv, const double *__restrict__ U,
+                                                      const double *__restrict__ F, double *__restrict__ part)
+{
+    resnorm_pairs_body<HAS_U, NT>(N, inv, U, F, part);
+}
+
 // second stage: *out = sqrt(sum of the n partials), one block in a fixed order (run-to-run reproducible)
-__global__ __launch_bounds__(1024) void k_resnorm_finish(const double *__restrict__ part, size_t n, double *__restrict__ out)
+__device__ __forceinline__ void resnorm_finish_body(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
     double acc = 0.0;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc += part[i];
     const double s = block_sum(acc);
     if (threadIdx.x == 0) *out = sqrt(s);
+}
+
+__global__ __launch_bounds__(1024) void k_resnorm_finish(const double *__restrict__ part, size_t n, double *__restrict__ out)
+{
+    resnorm_finish_body(part, n, out);
+}
+
+// batched forms: instance z = blockIdx.z (blockIdx.x for the finish) of items[] (in = U, F), its n partials at part + z*n
+template <bool HAS_U>
+__global__ __launch_bounds__(TB) void k_resnorm_b(int N, double inv, const NodeBatchItem *__restrict__ items,
+                                                  double *__restrict__ part, size_t n)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    resnorm_body<HAS_U>(N, inv, static_cast<const double *>(it.in), static_cast<const double *>(it.F), part + blockIdx.z * n);
+}
+
+template <bool HAS_U, bool NT>
+__global__ __launch_bounds__(TB) void k_resnorm_pairs_b(int N, double inv, const NodeBatchItem *__restrict__ items,
+                                                        double *__restrict__ part, size_t n)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    resnorm_pairs_body<HAS_U, NT>(N, inv, static_cast<const double *>(it.in), static_cast<const double *>(it.F),
+                                  part + blockIdx.z * n);
+}
+
+// out[i] = sqrt(sum of instance i's n partials): one block per instance, each the single-instance finish
+__global__ __launch_bounds__(1024) void k_resnorm_finish_b(const double *__restrict__ part, size_t n, double *__restrict__ out)
+{
+    resnorm_finish_body(part + blockIdx.x * n, n, out + blockIdx.x);
 }
 
 // ---------------------------------------------------------------- coarse solve
@@ -214,9 +261,9 @@ __global__ __launch_bounds__(1024) void k_resnorm_finish(const double *__restric
 // is max(atol, rtol*err0) with err0 the same metric at U = 0 (sum|F| / (N-2)^2), evaluated here from F before the
 // first iteration; at least one iteration, at most max_iters.  state[1] = iterations, state[2] = 1 when the cap ended
 // the solve above the target, state[3] = bits of nothing (kept zero).  *err_out (when given) = err0, final err.
-__global__ __launch_bounds__(1024) void k_gs_relative(int N, double h2, double inv, double *__restrict__ Ug,
-                                                      const double *__restrict__ Fg, double atol, double rtol,
-                                                      int max_iters, int *__restrict__ state, double *__restrict__ err_out)
+__device__ __forceinline__ void gs_relative_body(int N, double h2, double inv, double *__restrict__ Ug,
+                                                 const double *__restrict__ Fg, double atol, double rtol, int max_iters,
+                                                 int *__restrict__ state, double *__restrict__ err_out)
 {
     extern __shared__ __align__(16) double lds[];
     __shared__ double s_val;
@@ -273,6 +320,102 @@ __global__ __launch_bounds__(1024) void k_gs_relative(int N, double h2, double i
             err_out[1] = err;
         }
     }
+}
+
+__global__ __launch_bounds__(1024) void k_gs_relative(int N, double h2, double inv, double *__restrict__ Ug,
+                                                      const double *__restrict__ Fg, double atol, double rtol,
+                                                      int max_iters, int *__restrict__ state, double *__restrict__ err_out)
+{
+    gs_relative_body(N, h2, inv, Ug, Fg, atol, rtol, max_iters, state, err_out);
+}
+
+// one workgroup per instance (items[i]: out = U, F): its own err0, its own stop, its state at state + 4i
+__global__ __launch_bounds__(1024) void k_gs_relative_b(int N, double h2, double inv, const NodeBatchItem *__restrict__ items,
+                                                        double atol, double rtol, int max_iters, int *__restrict__ state)
+{
+    const NodeBatchItem &it = items[blockIdx.x];
+    gs_relative_body(N, h2, inv, static_cast<double *>(it.out), static_cast<const double *>(it.F), atol, rtol, max_iters,
+                     state + 4 * blockIdx.x, nullptr);
+}
+
+// ---------------------------------------------------------------- transfer operators of the non-fusable levels, batched
+// The expressions of k_residual, k_restrict<double> and k_prolong<true, double> (mg_kernels.hip), one point per lane;
+// instance blockIdx.z of items[].  residual: in = U, F, out = D.
+__global__ __launch_bounds__(TB) void k_residual_b(int N, double inv, const NodeBatchItem *__restrict__ items, int sign)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    const double *__restrict__ U = static_cast<const double *>(it.in);
+    const double *__restrict__ F = static_cast<const double *>(it.F);
+    double *__restrict__ D = static_cast<double *>(it.out);
+    const int c = blockIdx.x * TB + threadIdx.x;
+    if (c >= N) return;
+    const int r0 = blockIdx.y * ROWS_PB;
+#pragma unroll
+    for (int k = 0; k < ROWS_PB; ++k) {
+        const int r = r0 + k;
+        if (r >= N) return;
+        const size_t p = (size_t)r * N + c;
+        double v = 0.0;
+        if (!rim(r, c, N)) v = inv * star_minus4(U, p, N) - F[p];
+        D[p] = sign < 0 ? -v : v;
+    }
+}
+
+// restriction N -> M (doRestriction, :656-678): in = fine field, out = coarse field
+__global__ __launch_bounds__(TB) void k_restrict_b(int N, int M, const NodeBatchItem *__restrict__ items,
+                                                   const int *__restrict__ lo, const double *__restrict__ w, int sign)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    const double *__restrict__ Uf = static_cast<const double *>(it.in);
+    double *__restrict__ Uc = static_cast<double *>(it.out);
+    const int cc = blockIdx.x * TB + threadIdx.x;
+    const int rc = blockIdx.y;
+    if (cc >= M) return;
+    double v = 0.0;
+    if (!rim(rc, cc, M)) {
+        const double a = w[cc], b = 1.0 - a;
+        const double c = w[rc], d = 1.0 - c;
+        const size_t f = (size_t)lo[cc] + (size_t)lo[rc] * N;
+        v = b * d * Uf[f] + a * d * Uf[f + 1] + c * b * Uf[f + N] + a * c * Uf[f + N + 1];
+        if (sign < 0) v = -v;
+    }
+    Uc[(size_t)rc * M + cc] = v;
+}
+
+// out = in + doProlongation(coarse) (:354 + :368), coarse N -> fine M: coarse, in, out
+__global__ __launch_bounds__(TB) void k_prolong_add_b(int N, int M, const NodeBatchItem *__restrict__ items,
+                                                      const int *__restrict__ orow, const int *__restrict__ ocol,
+                                                      const double *__restrict__ row_hi, const double *__restrict__ row_lo,
+                                                      const double *__restrict__ col_hi, const double *__restrict__ col_lo,
+                                                      double c_dx)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    const double *__restrict__ Uc = static_cast<const double *>(it.coarse);
+    const double *__restrict__ Uf_in = static_cast<const double *>(it.in);
+    double *__restrict__ Uf_out = static_cast<double *>(it.out);
+    const int l = blockIdx.x * TB + threadIdx.x;
+    const int kf = blockIdx.y;
+    if (l >= M) return;
+    const int i = orow[kf], j = ocol[l];
+    const size_t q = (size_t)kf * M + l;
+    if (i < 0 || j < 0) {  // no coarse cell writes this point (never for M >= N)
+        Uf_out[q] = Uf_in[q];
+        return;
+    }
+    const size_t p = (size_t)i * N + j;
+    const double c1 = Uc[p], c2 = Uc[p + 1], c3 = Uc[p + N], c4 = Uc[p + N + 1];
+    const double xh = col_hi[l], xl = col_lo[l], yh = row_hi[kf], yl = row_lo[kf];
+    const double v = ((c1 * xh + c2 * xl) * yh + (c3 * xh + c4 * xl) * yl) / c_dx / c_dx;
+    Uf_out[q] = Uf_in[q] + v;   // doGridAddition :569: U1 = U1 + U2
+}
+
+// out = in, n doubles per instance (blockIdx.y)
+__global__ __launch_bounds__(TB) void k_copy_b(size_t n, const NodeBatchItem *__restrict__ items)
+{
+    const NodeBatchItem &it = items[blockIdx.y];
+    const double *__restrict__ src = static_cast<const double *>(it.in);
+    double *__restrict__ dst = static_cast<double *>(it.out);
+    for (size_t i = (size_t)blockIdx.x * TB + threadIdx.x; i < n; i += (size_t)gridDim.x * TB) dst[i] = src[i];
 }
 
 inline dim3 grid_rows(int N) { return dim3((N + TB - 1) / TB, (N + ROWS_PB - 1) / ROWS_PB); }
@@ -333,6 +476,65 @@ void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *
     if (threads > 1024) threads = 1024;
     // (N <= 63: at most 63 KiB of U and F, inside the default 64 KiB of dynamic LDS)
     hipLaunchKernelGGL(k_gs_relative, dim3(1), dim3(threads), lds, s, N, h2, inv, U, F, atol, rtol, max_iters, state, err_out);
+}
+
+// ------------------------------------------------------------------ batched launchers (mg_solve_batch.cpp)
+void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out)
+{
+    const size_t np = resnorm_partials(N);
+    if (use_pairs(N)) {
+        dim3 g = grid_pairs(N);
+        g.z = n;
+        const bool nt = N >= NT_MIN_N;
+        if (has_u) {
+            if (nt) hipLaunchKernelGGL((k_resnorm_pairs_b<true, true>), g, dim3(TB), 0, s, N, inv, items, part, np);
+            else hipLaunchKernelGGL((k_resnorm_pairs_b<true, false>), g, dim3(TB), 0, s, N, inv, items, part, np);
+        } else {
+            if (nt) hipLaunchKernelGGL((k_resnorm_pairs_b<false, true>), g, dim3(TB), 0, s, N, inv, items, part, np);
+            else hipLaunchKernelGGL((k_resnorm_pairs_b<false, false>), g, dim3(TB), 0, s, N, inv, items, part, np);
+        }
+    } else {
+        dim3 g = grid_rows(N);
+        g.z = n;
+        if (has_u) hipLaunchKernelGGL(k_resnorm_b<true>, g, dim3(TB), 0, s, N, inv, items, part, np);
+        else hipLaunchKernelGGL(k_resnorm_b<false>, g, dim3(TB), 0, s, N, inv, items, part, np);
+    }
+    hipLaunchKernelGGL(k_resnorm_finish_b, dim3(n), dim3(1024), 0, s, part, np, out);
+}
+
+void gauss_seidel_relative_batch(hipStream_t s, int n, int N, double h2, double inv, const NodeBatchItem *items, double atol,
+                                 double rtol, int max_iters, int *state)
+{
+    const size_t cells = (size_t)N * N;
+    int threads = (int)((cells + 63) / 64 * 64);
+    if (threads > 1024) threads = 1024;
+    hipLaunchKernelGGL(k_gs_relative_b, dim3(n), dim3(threads), 2 * cells * sizeof(double), s, N, h2, inv, items, atol, rtol,
+                       max_iters, state);
+}
+
+void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign)
+{
+    dim3 g = grid_rows(N);
+    g.z = n;
+    hipLaunchKernelGGL(k_residual_b, g, dim3(TB), 0, s, N, inv, items, sign);
+}
+
+void restrict_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const RestrictTable &t, int sign)
+{
+    hipLaunchKernelGGL(k_restrict_b, dim3((M + TB - 1) / TB, M, n), dim3(TB), 0, s, N, M, items, t.lo, t.w, sign);
+}
+
+void prolong_add_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const ProlongTable &t)
+{
+    hipLaunchKernelGGL(k_prolong_add_b, dim3((M + TB - 1) / TB, M, n), dim3(TB), 0, s, N, M, items, t.owner_row, t.owner_col,
+                       t.row_hi, t.row_lo, t.col_hi, t.col_lo, t.c_dx);
+}
+
+void copy_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items)
+{
+    size_t blocks = (count + TB - 1) / TB;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_copy_b, dim3((unsigned)blocks, n), dim3(TB), 0, s, count, items);
 }
 
 }  // namespace k

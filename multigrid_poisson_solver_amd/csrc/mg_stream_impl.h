@@ -1320,8 +1320,10 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
         fail(MG_ERR_ARG, "jacobi_stream: recomputed pre-smoothing exists for pre + steps <= 6 sweeps of the fused `1` node (pre=%d steps=%d)", pre, steps);
         return;
     }
-    if (cw != 0.25 && (pre != 0 || batch || sizeof(real_t) != 8)) {
-        fail(MG_ERR_ARG, "jacobi_stream: the weighted sweep runs fp64 nodes that store and re-read U, one instance");
+    // (a batch of weighted nodes: the batched solver, mg_solve_batch.cpp -- the kernel body takes every instance's arrays,
+    // `in` included, from the table; slab windows are refused above for every batch)
+    if (cw != 0.25 && (pre != 0 || sizeof(real_t) != 8)) {
+        fail(MG_ERR_ARG, "jacobi_stream: the weighted sweep runs fp64 nodes that store and re-read U");
         return;
     }
     if (pre != 0 && D_out) {
