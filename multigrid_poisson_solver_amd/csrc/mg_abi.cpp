@@ -252,26 +252,33 @@ inline double spacing_sq(int N, double L)
     return dx * dx;
 }
 
-// fused transfer stages (streaming smoother only): level 0 = U_in + P(coarse) for the first
-// launch, restriction of the signed residual into Fc for the last launch
-struct Fusion {
-    const double *coarse = nullptr;
-    int Nc = 0;
-    const ProlongTable *pt = nullptr;
-    double *Fc = nullptr;
-    int M = 0;
-    const RestrictTable *rt = nullptr;
-    int pre = 0;          // `1` node: recompute the pre-smoothed field (pre sweeps from zero) instead of reading U_in
-    bool no_out = false;  // `-1` node: do not store the smoothed field
-};
+// profile name and algorithmic bytes of one fused fp64 launch of `kernel`: 24 B per sweep and point, + 8 for
+// a folded zero-fill, + 24 for a folded residual, + 8n + 8m for a folded restriction, + 8m + 16n for a folded
+// prolongation+addition; the fused error costs nothing
+double node_profile(const char *kernel, const k::SmoothNode<double> &nd, char (&name)[48])
+{
+    const double n = (double)nd.N * nd.N;
+    const bool zero = !nd.in && !nd.pre, res = nd.D || nd.Fc;
+    char pre_tag[8] = "";
+    if (nd.pre) snprintf(pre_tag, sizeof pre_tag, ",pre%d", nd.pre);
+    snprintf(name, sizeof name, "%s<%d%s%s%s%s%s%s>", kernel, nd.steps, zero ? ",zero" : "", nd.coarse ? ",prolong" : "",
+             res ? ",res" : "", nd.Fc ? ",restrict" : "", nd.no_out ? ",noU" : "", pre_tag);
+    double bytes = n * (24.0 * (nd.steps + nd.pre) + (zero ? 8.0 : 0.0) + (res ? 24.0 : 0.0));
+    if (nd.Fc) bytes += 8.0 * n + 8.0 * nd.M * nd.M;
+    if (nd.coarse) bytes += 16.0 * n + 8.0 * nd.Nc * nd.Nc;
+    return bytes;
+}
 
-void smooth_pp(int N, double L, const double *U_in, double *U_out, double *F, int step, double *error_dev,
-               double *D_out, int d_sign, const Fusion &fu = Fusion())
+// One smoothing node on the whole grid: nd.steps sweeps from nd.in (nullptr: zero) into nd.out, in one fused launch or
+// several.  The fused transfer stages (streaming smoother only) go to the first launch (coarse: level 0 = in + P(coarse))
+// and the last (Fc: restriction of the signed residual); so do the error and a stored residual (D).  dx2 / inv are set here.
+void smooth_pp(double L, k::SmoothNode<double> nd)
 {
     Context &c = ctx();
     hipStream_t s = c.stream;
-    const double dx2 = spacing_sq(N, L);
-    const double inv = 1.0 / dx2;
+    const int N = nd.N, step = nd.steps;
+    nd.dx2 = spacing_sq(N, L);
+    nd.inv = 1.0 / nd.dx2;
     const size_t n = (size_t)N * N;
 
     if (step <= 0 && c.trace) {
@@ -279,10 +286,10 @@ void smooth_pp(int N, double L, const double *U_in, double *U_out, double *F, in
         return;
     }
     if (step <= 0) {  // no sweep: U_out = U_in
-        if (U_in) (void)hipMemcpyAsync(U_out, U_in, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-        else (void)hipMemsetAsync(U_out, 0, n * sizeof(double), s);
-        if (error_dev) k::smoothing_error(s, N, inv, U_out, F, error_dev);
-        if (D_out) k::residual(s, N, inv, U_out, F, D_out, d_sign);
+        if (nd.in) (void)hipMemcpyAsync(nd.out, nd.in, n * sizeof(double), hipMemcpyDeviceToDevice, s);
+        else (void)hipMemsetAsync(nd.out, 0, n * sizeof(double), s);
+        if (nd.err) k::smoothing_error(s, N, nd.inv, nd.out, nd.F, nd.err);
+        if (nd.D) k::residual(s, N, nd.inv, nd.out, nd.F, nd.D, nd.d_sign);
         return;
     }
 
@@ -291,36 +298,17 @@ void smooth_pp(int N, double L, const double *U_in, double *U_out, double *F, in
         // the cycle driver's dataflow trace: describe the launch instead of enqueueing it.  Only a node that is ONE fused
         // launch of the streaming or the tile kernel can be batched with its peers
         const int smax1 = stream ? k::stream_max_steps() : 1;
-        if (!stream || step > smax1 || D_out || !error_dev || (fu.coarse && fu.Fc)) {
+        if (!stream || step > smax1 || nd.D || !nd.err || (nd.coarse && nd.Fc)) {
             c.trace_failed = true;
             return;
         }
         NodeOp op;
         // (levels between the batched schedule's coarse tail and the tile kernel's usual range: the tile kernel as well)
-        const bool as_tile = c.smoother == SMOOTHER_STREAM && fu.pre == 0 && (k::tile_wanted(N) || (N >= 16 && N <= k::TAIL_MAX_N)) && step <= k::tile_max_steps();
+        const bool as_tile = c.smoother == SMOOTHER_STREAM && nd.pre == 0 && (k::tile_wanted(N) || (N >= 16 && N <= k::TAIL_MAX_N)) && step <= k::tile_max_steps();
         op.kind = as_tile ? 1 : 0;
-        op.N = N;
         op.L = L;
-        op.src = U_in;
-        op.F = F;
-        op.dst = U_out;
-        op.take = step;
-        op.err = error_dev;
-        op.d_sign = d_sign;
-        op.coarse = fu.coarse;
-        op.Nc = fu.Nc;
-        op.Fc = fu.Fc;
-        op.M = fu.M;
-        op.pre = fu.pre;
-        op.no_out = fu.no_out;
-        const bool pro = fu.coarse != nullptr, rst = fu.Fc != nullptr;
-        char pre_tag[8] = "";
-        if (fu.pre) snprintf(pre_tag, sizeof pre_tag, ",pre%d", fu.pre);
-        snprintf(op.name, sizeof op.name, "%s<%d%s%s%s%s%s>", as_tile ? "jacobi_tile" : "jacobi_stream", step, (U_in || fu.pre) ? "" : ",zero",
-                 pro ? ",prolong" : "", rst ? ",res,restrict" : "", fu.no_out ? ",noU" : "", pre_tag);
-        op.bytes = (double)n * (24.0 * (step + fu.pre) + ((U_in || fu.pre) ? 0.0 : 8.0) + (rst ? 24.0 : 0.0));
-        if (rst) op.bytes += 8.0 * n + 8.0 * fu.M * fu.M;
-        if (pro) op.bytes += 16.0 * n + 8.0 * fu.Nc * fu.Nc;
+        op.node = nd;
+        op.bytes = node_profile(as_tile ? "jacobi_tile" : "jacobi_stream", nd, op.name);
         c.trace->push_back(op);
         return;
     }
@@ -332,76 +320,70 @@ void smooth_pp(int N, double L, const double *U_in, double *U_out, double *F, in
     int launches = (step + smax - 1) / smax;
     if (launches % 2 == 0 && step > launches) launches += 1;
     const bool needs_copy = (launches % 2 == 0);  // only smax == 1 with an even step
-    double *partner = const_cast<double *>(U_in);
+    double *partner = const_cast<double *>(nd.in);
     bool own_partner = false;
     if ((launches > 1 && !partner) || needs_copy) {
         partner = (double *)scratch_pool().get(n * sizeof(double));
         own_partner = true;
         if (!partner) return;
     }
-    const double *src = U_in;
+    const double *src = nd.in;
     int left = step;
     for (int i = 0; i < launches; ++i) {
         const int take = (left + (launches - i) - 1) / (launches - i);
         const bool last = (i == launches - 1);
         // odd count: dst alternates so that the last is U_out.  even count (own partner):
         // start in the partner, the last launch then lands in U_out as well.
-        double *dst = ((launches - 1 - i) % 2 == 0) ? U_out : partner;
-        const bool plain_single = stream && c.smoother != SMOOTHER_STREAM_ONLY && take == 1 && src && !(i == 0 && fu.coarse) && !(last && (D_out || fu.Fc || error_dev)) &&
+        double *dst = ((launches - 1 - i) % 2 == 0) ? nd.out : partner;
+        const bool plain_single = stream && c.smoother != SMOOTHER_STREAM_ONLY && take == 1 && src && !(i == 0 && nd.coarse) && !(last && (nd.D || nd.Fc || nd.err)) &&
                                   N >= 2048 && N % 2 == 0;
         // small levels: the whole node as one launch of the register-tile kernel (mg_tile_impl.h) -- the streaming kernel's
         // march down a column strip is pure latency there.  Same bits.  Not for a stored residual (the unfused driver) and
         // not for the recomputing pair (large levels only).
-        const bool tile = stream && c.smoother == SMOOTHER_STREAM && launches == 1 && !D_out && fu.pre == 0 && k::tile_wanted(N) &&
+        const bool tile = stream && c.smoother == SMOOTHER_STREAM && launches == 1 && !nd.D && nd.pre == 0 && k::tile_wanted(N) &&
                           take <= k::tile_max_steps();
+        // this launch: the prolongation in the first, the residual, the restriction and the error in the last
+        k::SmoothNode<double> ln = nd;
+        ln.in = src;
+        ln.out = dst;
+        ln.steps = take;
+        if (i > 0) ln.coarse = nullptr;
+        if (!last) {
+            ln.err = nullptr;
+            ln.D = nullptr;
+            ln.Fc = nullptr;
+        }
+        char name[48];
         if (tile) {
-            const bool pro = fu.coarse != nullptr, rst = fu.Fc != nullptr;
-            char name[48];
-            snprintf(name, sizeof name, "jacobi_tile<%d%s%s%s%s>", take, src ? "" : ",zero", pro ? ",prolong" : "", rst ? ",res,restrict" : "",
-                     fu.no_out ? ",noU" : "");
-            double bytes = (double)n * (24.0 * take + (src ? 0.0 : 8.0) + (rst ? 24.0 : 0.0));
-            if (rst) bytes += 8.0 * n + 8.0 * fu.M * fu.M;
-            if (pro) bytes += 16.0 * n + 8.0 * fu.Nc * fu.Nc;
+            const double bytes = node_profile("jacobi_tile", ln, name);
             ProfScope ps(name, N, bytes);
-            k::jacobi_tile(s, N, dx2, inv, src, F, dst, take, error_dev, d_sign, fu.coarse, fu.Nc, fu.pt, fu.Fc, fu.M, fu.rt, fu.no_out);
+            k::jacobi_tile(s, ln);
         } else if (plain_single) {
             // one bare sweep of a large grid: the one-row-per-block pair kernel is the faster of the two
             // (5.1 vs 4.5 TB/s at N = 8192; same bits) -- there is nothing to fuse and no row history to amortise
             ProfScope ps("jacobi_pair", N, (double)n * 24.0);
-            k::jacobi_simple(s, N, dx2, src, F, dst);
+            k::jacobi_simple(s, N, nd.dx2, src, nd.F, dst);
         } else if (stream) {
-            // algorithmic bytes: 24 B per sweep and point, + 8 for a folded
-            // zero-fill, + 24 for a folded residual, + 8n + 8m for a folded restriction,
-            // + 8m + 16n for a folded prolongation+addition; the fused error costs nothing
-            const bool pro = (i == 0 && fu.coarse), res = last && (D_out || fu.Fc), rst = last && fu.Fc;
-            char name[48], pre_tag[8] = "";
-            if (fu.pre) snprintf(pre_tag, sizeof pre_tag, ",pre%d", fu.pre);
-            snprintf(name, sizeof name, "jacobi_stream<%d%s%s%s%s%s%s>", take, (src || fu.pre) ? "" : ",zero", pro ? ",prolong" : "",
-                     res ? ",res" : "", rst ? ",restrict" : "", fu.no_out ? ",noU" : "", pre_tag);
-            double bytes = (double)n * (24.0 * (take + fu.pre) + ((src || fu.pre) ? 0.0 : 8.0) + (res ? 24.0 : 0.0));
-            if (rst) bytes += 8.0 * n + 8.0 * fu.M * fu.M;
-            if (pro) bytes += 16.0 * n + 8.0 * fu.Nc * fu.Nc;
+            const double bytes = node_profile("jacobi_stream", ln, name);
             ProfScope ps(name, N, bytes);
-            k::jacobi_stream(s, N, dx2, inv, src, F, dst, take, last ? error_dev : nullptr, last ? D_out : nullptr,
-                             d_sign, pro ? fu.coarse : nullptr, fu.Nc, fu.pt, rst ? fu.Fc : nullptr, fu.M, fu.rt, nullptr, nullptr, nullptr,
-                             fu.pre, fu.no_out);
+            k::jacobi_stream(s, ln);
         } else {
             // (k_jacobi_pair on even N, k_jacobi_simple on odd N: the launcher picks)
             ProfScope ps(src ? (N % 2 == 0 && N >= 512 ? "jacobi_pair" : "jacobi_simple") : "jacobi_simple<zero>", N, (double)n * (src ? 24.0 : 32.0));
-            k::jacobi_simple(s, N, dx2, src, F, dst);
+            k::jacobi_simple(s, N, nd.dx2, src, nd.F, dst);
         }
         src = dst;
         left -= take;
     }
     if (own_partner) scratch_pool().put(partner);  // stream-ordered: later users queue behind us
     if (!stream) {
-        if (error_dev) {
+        if (nd.err) {
             ProfScope ps("smoothing_error", N, 0.0);
-            k::smoothing_error(s, N, inv, U_out, F, error_dev);
+            k::smoothing_error(s, N, nd.inv, nd.out, nd.F, nd.err);
         }
-        if (D_out) {
+        if (nd.D) {
             ProfScope ps("residual", N, (double)n * 24.0);
-            k::residual(s, N, inv, U_out, F, D_out, d_sign);
+            k::residual(s, N, nd.inv, nd.out, nd.F, nd.D, nd.d_sign);
         }
     }
 }
@@ -436,12 +418,7 @@ void smooth_restrict_no_out(int N, double L, double *U_unused, double *F, int st
         fail(MG_ERR_UNSUPPORTED, "smooth_restrict_no_out: N=%d M=%d step=%d is not a fused `-1` node", N, M, step);
         return;
     }
-    Fusion fu;
-    fu.Fc = F_c;
-    fu.M = M;
-    fu.rt = &rt;
-    fu.no_out = true;
-    smooth_pp(N, L, nullptr, U_unused, F, step, error_dev, nullptr, -1, fu);
+    smooth_pp(L, {.N = N, .F = F, .out = U_unused, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt, .no_out = true});
 }
 
 void prolong_smooth_recompute(int Nc, const double *U_c, int N, double L, double *U_out, double *F, int pre, int step, double *error_dev)
@@ -450,33 +427,23 @@ void prolong_smooth_recompute(int Nc, const double *U_c, int N, double L, double
         fail(MG_ERR_UNSUPPORTED, "prolong_smooth_recompute: Nc=%d N=%d pre=%d step=%d", Nc, N, pre, step);
         return;
     }
-    Fusion fu;
-    fu.coarse = U_c;
-    fu.Nc = Nc;
-    fu.pt = &prolong_table(Nc, N);
-    fu.pre = pre;
-    smooth_pp(N, L, nullptr, U_out, F, step, error_dev, nullptr, +1, fu);
+    smooth_pp(L, {.N = N, .F = F, .out = U_out, .steps = step, .err = error_dev, .d_sign = +1, .coarse = U_c, .Nc = Nc,
+                  .pt = &prolong_table(Nc, N), .pre = pre});
 }
 
 // One launch for n recorded instances of the same fused node (the independent visits of a level, mg_cycle.cpp); the
 // name carries the batch size, the algorithmic bytes are those of all instances.
 void replay_node(const NodeOp &op, const NodeBatch *batch)
 {
-    Context &c = ctx();
-    const double dx2 = spacing_sq(op.N, op.L), inv = 1.0 / dx2;
-    const ProlongTable *pt = op.coarse ? &prolong_table(op.Nc, op.N) : nullptr;
-    const RestrictTable *rt = op.Fc ? &restrict_table(op.N, op.M) : nullptr;
     const int nb = batch ? batch->n : 1;
     char name[64];
     if (nb > 1) snprintf(name, sizeof name, "%s x%d", op.name, nb);
     else snprintf(name, sizeof name, "%s", op.name);
-    ProfScope ps(name, op.N, op.bytes * nb);
-    if (op.kind == 1)
-        k::jacobi_tile(c.stream, op.N, dx2, inv, op.src, op.F, op.dst, op.take, op.err, op.d_sign, op.coarse, op.Nc, pt, op.Fc, op.M, rt, op.no_out,
-                       nullptr, nullptr, nullptr, batch);
-    else
-        k::jacobi_stream(c.stream, op.N, dx2, inv, op.src, op.F, op.dst, op.take, op.err, nullptr, op.d_sign, op.coarse, op.Nc, pt, op.Fc, op.M, rt,
-                         nullptr, nullptr, nullptr, op.pre, op.no_out, batch);
+    ProfScope ps(name, op.node.N, op.bytes * nb);
+    k::SmoothNode<double> nd = op.node;
+    nd.batch = batch;
+    if (op.kind == 1) k::jacobi_tile(ctx().stream, nd);
+    else k::jacobi_stream(ctx().stream, nd);
 }
 
 }  // namespace mg
@@ -787,100 +754,62 @@ void fill_source_rows(int N, double L, double min_x, double min_y, int row_lo, i
 
 // one fused launch on a row window (slab mode supports step <= stream_max_steps(): a second
 // launch would need a ghost exchange of the intermediate field)
-void slab_smooth(int N, double L, const double *U_in, double *U_out, const double *F, int step, double *raw_norm_out,
-                 const SlabFusion &sf)
+template <typename T>
+void slab_smooth(int N, double L, const T *U_in, T *U_out, const T *F, int step, double *raw_norm_out, const SlabFusion &sf)
 {
+    constexpr bool f32 = sizeof(T) == 4;
     Context &c = ctx();
     const double dx2 = spacing_sq(N, L);
-    const double inv = 1.0 / dx2;
     if (step < 1 || step > k::stream_max_steps() || !k::stream_fusable(N)) {
         fail(MG_ERR_UNSUPPORTED, "row-slab mode: %d smoothing steps on N=%d (need 1..%d steps, even N)", step, N,
              k::stream_max_steps());
         return;
     }
-    const ProlongTable *pt = nullptr;
-    const RestrictTable *rt = nullptr;
+    k::SmoothNode<T> nd{.N = N, .dx2 = (T)dx2, .inv = (T)(1.0 / dx2), .in = U_in, .F = F, .out = U_out, .steps = step,
+                        .err = raw_norm_out, .fine_w = &sf.fine_w, .pre = sf.pre, .no_out = sf.no_out, .out_wide = sf.out_wide};
     if (sf.coarse) {
-        pt = &prolong_table(sf.Nc, N);
-        if (!pt->owner_row || !pt->fusable) {
+        nd.pt = &prolong_table(sf.Nc, N);
+        if (!nd.pt->owner_row || !nd.pt->fusable) {
             fail(MG_ERR_UNSUPPORTED, "row-slab mode: prolongation %d -> %d is not fusable", sf.Nc, N);
             return;
         }
+        nd.coarse = (const T *)sf.coarse;
+        nd.Nc = sf.Nc;
+        nd.coarse_w = &sf.coarse_w;
     }
     if (sf.Fc) {
-        rt = &restrict_table(N, sf.M);
-        if (!rt->lo || !rt->fusable) {
+        nd.rt = &restrict_table(N, sf.M);
+        if (!nd.rt->lo || !nd.rt->fusable) {
             fail(MG_ERR_UNSUPPORTED, "row-slab mode: restriction %d -> %d is not fusable", N, sf.M);
             return;
         }
+        nd.Fc = (T *)sf.Fc;
+        nd.M = sf.M;
+        nd.fc_w = &sf.fc_w;
     }
+    // the fp64 figures, halved for fp32 fields (exact)
     const size_t n = (size_t)(sf.fine_w.own_hi - sf.fine_w.own_lo) * N;
     double bytes = (double)n * (24.0 * step + (U_in ? 0.0 : 8.0) + (sf.Fc ? 24.0 : 0.0));
     if (sf.Fc) bytes += 8.0 * n + 2.0 * n;
     if (sf.coarse) bytes += 16.0 * n + 2.0 * n;
-    char name[48], pre_tag[8] = "";
-    if (sf.pre) snprintf(pre_tag, sizeof pre_tag, ",pre%d", sf.pre);
-    // a slab of a level the caches hold: the register-tile kernel on the row window (mg_tile_impl.h)
-    const bool as_tile = !sf.pre && c.smoother == SMOOTHER_STREAM && k::tile_wanted_slab(N) && step <= k::tile_max_steps();
-    snprintf(name, sizeof name, "%s<%d%s%s%s%s%s>", as_tile ? "slab_tile" : "slab_stream", step, (U_in || sf.pre) ? "" : ",zero", sf.coarse ? ",prolong" : "",
-             sf.Fc ? ",res,restrict" : "", sf.no_out ? ",noU" : "", pre_tag);
-    if (as_tile) {
-        ProfScope ps(name, N, bytes);
-        k::jacobi_tile(c.stream, N, dx2, inv, U_in, F, U_out, step, raw_norm_out, -1, sf.coarse, sf.Nc, pt, sf.Fc, sf.M, rt, sf.no_out,
-                       &sf.fine_w, sf.coarse ? &sf.coarse_w : nullptr, sf.Fc ? &sf.fc_w : nullptr);
-        return;
-    }
-    ProfScope ps(name, N, bytes);
-    k::jacobi_stream(c.stream, N, dx2, inv, U_in, F, U_out, step, raw_norm_out, nullptr, -1, sf.coarse, sf.Nc, pt, sf.Fc,
-                     sf.M, rt, &sf.fine_w, sf.coarse ? &sf.coarse_w : nullptr, sf.Fc ? &sf.fc_w : nullptr, sf.pre, sf.no_out);
-}
-
-void slab_smooth_f32(int N, double L, const float *U_in, float *U_out, const float *F, int step, double *raw_norm_out,
-                     const SlabFusion &sf)
-{
-    Context &c = ctx();
-    const double dx2 = spacing_sq(N, L);
-    if (step < 1 || step > k::stream_max_steps() || !k::stream_fusable(N)) {
-        fail(MG_ERR_UNSUPPORTED, "row-slab mode: %d smoothing steps on N=%d (need 1..%d steps, even N)", step, N,
-             k::stream_max_steps());
-        return;
-    }
-    const ProlongTable *pt = nullptr;
-    const RestrictTable *rt = nullptr;
-    if (sf.coarse) {
-        pt = &prolong_table(sf.Nc, N);
-        if (!pt->owner_row || !pt->fusable) {
-            fail(MG_ERR_UNSUPPORTED, "row-slab mode: prolongation %d -> %d is not fusable", sf.Nc, N);
-            return;
-        }
-    }
-    if (sf.Fc) {
-        rt = &restrict_table(N, sf.M);
-        if (!rt->lo || !rt->fusable) {
-            fail(MG_ERR_UNSUPPORTED, "row-slab mode: restriction %d -> %d is not fusable", N, sf.M);
-            return;
-        }
-    }
-    const size_t n = (size_t)(sf.fine_w.own_hi - sf.fine_w.own_lo) * N;
-    double bytes = (double)n * (12.0 * step + (U_in ? 0.0 : 4.0) + (sf.Fc ? 12.0 : 0.0));
-    if (sf.Fc) bytes += 4.0 * n + 1.0 * n;
-    if (sf.coarse) bytes += 8.0 * n + 1.0 * n;
+    bytes *= sizeof(T) / 8.0;
     char name[56], pre_tag[8] = "";
     if (sf.pre) snprintf(pre_tag, sizeof pre_tag, ",pre%d", sf.pre);
+    // a slab of a level the caches hold: the register-tile kernel on the row window (mg_tile_impl.h)
     const bool as_tile = !sf.pre && !sf.out_wide && c.smoother == SMOOTHER_STREAM && k::tile_wanted_slab(N) && step <= k::tile_max_steps();
-    snprintf(name, sizeof name, "%s<%d%s%s%s%s%s%s>", as_tile ? "slab_tile_f32" : "slab_stream_f32", step, (U_in || sf.pre) ? "" : ",zero",
+    snprintf(name, sizeof name, "%s%s<%d%s%s%s%s%s%s>", as_tile ? "slab_tile" : "slab_stream", f32 ? "_f32" : "", step, (U_in || sf.pre) ? "" : ",zero",
              sf.coarse ? ",prolong" : "", sf.out_wide ? ",widen" : "", sf.Fc ? ",res,restrict" : "", sf.no_out ? ",noU" : "", pre_tag);
-    if (as_tile) {
-        ProfScope ps(name, N, bytes);
-        k::jacobi_tile_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), U_in, F, U_out, step, raw_norm_out, -1, (const float *)sf.coarse, sf.Nc, pt,
-                           (float *)sf.Fc, sf.M, rt, sf.no_out, &sf.fine_w, sf.coarse ? &sf.coarse_w : nullptr, sf.Fc ? &sf.fc_w : nullptr);
-        return;
-    }
     ProfScope ps(name, N, bytes);
-    k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), U_in, F, U_out, step, raw_norm_out, (const float *)sf.coarse,
-                         sf.Nc, pt, (float *)sf.Fc, sf.M, rt, &sf.fine_w, sf.coarse ? &sf.coarse_w : nullptr,
-                         sf.Fc ? &sf.fc_w : nullptr, sf.out_wide, nullptr, -1, sf.pre, sf.no_out);
+    if constexpr (f32) {
+        if (as_tile) k::jacobi_tile_f32(c.stream, nd);
+        else k::jacobi_stream_f32(c.stream, nd);
+    } else {
+        if (as_tile) k::jacobi_tile(c.stream, nd);
+        else k::jacobi_stream(c.stream, nd);
+    }
 }
+template void slab_smooth(int, double, const double *, double *, const double *, int, double *, const SlabFusion &);
+template void slab_smooth(int, double, const float *, float *, const float *, int, double *, const SlabFusion &);
 }  // namespace mg
 
 extern "C" {
@@ -929,7 +858,7 @@ void mg_smooth_pp(int N, double L, const double *U_in, double *U_out, double *F,
         fail(MG_ERR_ARG, "mg_smooth_pp: U_out must differ from U_in");
         return;
     }
-    smooth_pp(N, L, U_in, U_out, F, step, error_dev, D_out, d_sign < 0 ? -1 : +1);
+    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D_out, .d_sign = d_sign < 0 ? -1 : +1});
 }
 
 // pre-smoothing + getResidual + sign flip + doRestriction of one "-1" node
@@ -948,18 +877,14 @@ void mg_smooth_restrict(int N, double L, const double *U_in, double *U_out, doub
     const RestrictTable &rt = restrict_table(N, M);
     if (!rt.lo) return;
     if (step > 0 && c.smoother != SMOOTHER_SIMPLE && k::stream_fusable(N) && rt.fusable) {
-        Fusion fu;
-        fu.Fc = F_c;
-        fu.M = M;
-        fu.rt = &rt;
-        smooth_pp(N, L, U_in, U_out, F, step, error_dev, nullptr, -1, fu);
+        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt});
         return;
     }
     // operator by operator, D in pool scratch
     const size_t n = (size_t)N * N;
     double *D = (double *)scratch_pool().get(n * sizeof(double));
     if (!D) return;
-    smooth_pp(N, L, U_in, U_out, F, step, error_dev, D, -1);
+    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D});
     {
         ProfScope ps("restrict", N, 8.0 * N * N + 8.0 * M * M);
         k::restrict_gather(c.stream, N, D, M, F_c, rt, +1);
@@ -983,11 +908,7 @@ void mg_prolong_smooth(int Nc, const double *U_c, int N, double L, const double 
     const ProlongTable &pt = prolong_table(Nc, N);
     if (!pt.owner_row) return;
     if (step > 0 && c.smoother != SMOOTHER_SIMPLE && k::stream_fusable(N) && pt.fusable) {
-        Fusion fu;
-        fu.coarse = U_c;
-        fu.Nc = Nc;
-        fu.pt = &pt;
-        smooth_pp(N, L, U_in, U_out, F, step, error_dev, nullptr, +1, fu);
+        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .d_sign = +1, .coarse = U_c, .Nc = Nc, .pt = &pt});
         return;
     }
     {
@@ -999,7 +920,7 @@ void mg_prolong_smooth(int Nc, const double *U_c, int N, double L, const double 
         const size_t n = (size_t)N * N;
         double *tmp = (double *)scratch_pool().get(n * sizeof(double));
         if (!tmp) return;
-        smooth_pp(N, L, U_out, tmp, F, step, error_dev, nullptr, +1);
+        smooth_pp(L, {.N = N, .in = U_out, .F = F, .out = tmp, .steps = step, .err = error_dev, .d_sign = +1});
         MG_HIP(hipMemcpyAsync(U_out, tmp, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
         scratch_pool().put(tmp);
     }
@@ -1025,16 +946,18 @@ void mg_smooth_restrict_f32(int N, double L, const float *U_in, float *U_out, fl
     }
     const double dx2 = spacing_sq(N, L);
     const size_t n = (size_t)N * N;
+    k::SmoothNode<float> nd{.N = N, .dx2 = (float)dx2, .inv = (float)(1.0 / dx2), .F = F, .out = U_out, .steps = step, .err = error_dev};
     if (k::stream_fusable(N) && rt.fusable) {
+        nd.Fc = F_c;
+        nd.M = M;
+        nd.rt = &rt;
         if (c.smoother == SMOOTHER_STREAM && k::tile_wanted(N) && step <= k::tile_max_steps()) {  // small levels: mg_tile_impl.h
             ProfScope ps("jacobi_tile_f32<zero,res,restrict>", N, (double)n * (12.0 * step + 4.0 + 12.0 + 4.0) + 4.0 * M * M);
-            k::jacobi_tile_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), nullptr, F, U_out, step, error_dev, -1, nullptr, 0, nullptr, F_c, M,
-                               &rt, false);
+            k::jacobi_tile_f32(c.stream, nd);
             return;
         }
         ProfScope ps("jacobi_stream_f32<zero,res,restrict>", N, (double)n * (12.0 * step + 4.0 + 12.0 + 4.0) + 4.0 * M * M);
-        k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), nullptr, F, U_out, step, error_dev, nullptr, 0, nullptr, F_c,
-                             M, &rt);
+        k::jacobi_stream_f32(c.stream, nd);
         return;
     }
     // odd or non-nested sizes: operator by operator (sweeps + signed residual in one launch, then the gather)
@@ -1042,8 +965,8 @@ void mg_smooth_restrict_f32(int N, double L, const float *U_in, float *U_out, fl
     if (!D) return;
     {
         ProfScope ps("jacobi_stream_f32<zero,res>", N, (double)n * (12.0 * step + 4.0 + 12.0));
-        k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), nullptr, F, U_out, step, error_dev, nullptr, 0, nullptr,
-                             nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, D, -1);
+        nd.D = D;
+        k::jacobi_stream_f32(c.stream, nd);
     }
     {
         ProfScope ps("restrict_f32", N, 4.0 * N * N + 4.0 * M * M);
@@ -1072,6 +995,8 @@ void prolong_smooth_f32_impl(int Nc, const float *U_c, int N, double L, const fl
     }
     const double dx2 = spacing_sq(N, L);
     const size_t n = (size_t)N * N;
+    k::SmoothNode<float> nd{.N = N, .dx2 = (float)dx2, .inv = (float)(1.0 / dx2), .in = U_in, .F = F, .out = U_out, .steps = step,
+                            .err = error_dev};
     if (pre && (!k::stream_fusable(N) || !pt.fusable)) {
         fail(MG_ERR_UNSUPPORTED, "prolong_smooth_f32_recompute: needs the fused form (Nc=%d N=%d)", Nc, N);
         return;
@@ -1090,24 +1015,29 @@ void prolong_smooth_f32_impl(int Nc, const float *U_c, int N, double L, const fl
         }
         {
             ProfScope ps("jacobi_stream_f32", N, (double)n * 12.0 * step);
-            k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), tmp, F, U_out, step, error_dev, nullptr, 0, nullptr, nullptr,
-                                 0, nullptr);
+            nd.in = tmp;
+            k::jacobi_stream_f32(c.stream, nd);
         }
         scratch_pool().put(tmp);
         return;
     }
+    nd.coarse = U_c;
+    nd.Nc = Nc;
+    nd.pt = &pt;
     if (!pre && !U_out_wide && c.smoother == SMOOTHER_STREAM && k::tile_wanted(N) && step <= k::tile_max_steps()) {  // small levels: mg_tile_impl.h
         ProfScope ps("jacobi_tile_f32<prolong>", N, (double)n * (12.0 * step + 8.0) + 4.0 * Nc * Nc);
-        k::jacobi_tile_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), U_in, F, U_out, step, error_dev, +1, U_c, Nc, &pt, nullptr, 0, nullptr,
-                           false);
+        nd.d_sign = +1;
+        k::jacobi_tile_f32(c.stream, nd);
         return;
     }
     char name[48];
     snprintf(name, sizeof name, pre ? "jacobi_stream_f32<prolong%s,pre%d>" : "jacobi_stream_f32<prolong%s>", U_out_wide ? ",widen" : "", pre);
     ProfScope ps(name,
                  N, (double)n * (12.0 * (step + pre) + 8.0 + (U_out_wide ? 12.0 : 0.0)) + 4.0 * Nc * Nc);
-    k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), pre ? nullptr : U_in, F, U_out, step, error_dev, U_c, Nc, &pt, nullptr, 0,
-                         nullptr, nullptr, nullptr, nullptr, U_out_wide, nullptr, -1, pre, false);
+    if (pre) nd.in = nullptr;
+    nd.pre = pre;
+    nd.out_wide = U_out_wide;
+    k::jacobi_stream_f32(c.stream, nd);
 }
 }  // namespace
 
@@ -1122,8 +1052,8 @@ void smooth_restrict_f32_no_out(int N, double L, float *U_unused, float *F, int 
     const double dx2 = spacing_sq(N, L);
     const size_t n = (size_t)N * N;
     ProfScope ps("jacobi_stream_f32<restrict,noU>", N, (double)n * (12.0 * step + 4.0 + 12.0 + 4.0) + 4.0 * M * M);
-    k::jacobi_stream_f32(c.stream, N, (float)dx2, (float)(1.0 / dx2), nullptr, F, U_unused, step, error_dev, nullptr, 0, nullptr, F_c, M, &rt,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, -1, 0, true);
+    k::jacobi_stream_f32(c.stream, {.N = N, .dx2 = (float)dx2, .inv = (float)(1.0 / dx2), .F = F, .out = U_unused, .steps = step,
+                                    .err = error_dev, .Fc = F_c, .M = M, .rt = &rt, .no_out = true});
 }
 
 void prolong_smooth_f32_recompute(int Nc, const float *U_c, int N, double L, float *U_out, double *U_out_wide, const float *F, int pre,
@@ -1200,7 +1130,7 @@ void mg_doSmoothing(int N, double L, double *U, double *F, int step, double *err
             c.defer_norms = deferred;
             return;
         }
-        smooth_pp(N, L, U, tmp, F, step, error ? slot : nullptr, nullptr, +1);
+        smooth_pp(L, {.N = N, .in = U, .F = F, .out = tmp, .steps = step, .err = error ? slot : nullptr, .d_sign = +1});
         MG_HIP(hipMemcpyAsync(U, tmp, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
         scratch_pool().put(tmp);  // stream-ordered reuse: later users enqueue behind the copy
     } else if (error) {

@@ -534,9 +534,9 @@ bool try_tail(Exec &x)
     if (x.tracing) {  // described, not launched (its exact-solver state slot is assigned when the schedule is built)
         NodeOp op;
         op.kind = 2;
-        op.N = top->N;
-        op.F = top->F;
-        op.dst = top->U;
+        op.node.N = top->N;
+        op.node.F = top->F;
+        op.node.out = top->U;
         op.tail = (int)p->tails.size();
         p->tails.push_back(a);
         p->ops.push_back(op);
@@ -857,7 +857,7 @@ void reset_levels(mg_cycle_plan *p)
 // ---------------------------------------------------------------------------
 bool same_shape(const mg_cycle_plan *p, const NodeOp &a, const NodeOp &b)
 {
-    if (a.kind != b.kind || a.N != b.N) return false;
+    if (a.kind != b.kind || a.node.N != b.node.N) return false;
     if (a.kind == 2) {
         const k::TailArgs &x = p->tails[(size_t)a.tail], &y = p->tails[(size_t)b.tail];
         if (x.n_levels != y.n_levels || x.n_nodes != y.n_nodes) return false;
@@ -869,8 +869,9 @@ bool same_shape(const mg_cycle_plan *p, const NodeOp &a, const NodeOp &b)
         }
         return true;
     }
-    return a.take == b.take && a.pre == b.pre && a.no_out == b.no_out && a.d_sign == b.d_sign && (a.src == nullptr) == (b.src == nullptr) &&
-           (a.coarse == nullptr) == (b.coarse == nullptr) && (a.Fc == nullptr) == (b.Fc == nullptr) && a.Nc == b.Nc && a.M == b.M && a.L == b.L;
+    const k::SmoothNode<double> &x = a.node, &y = b.node;
+    return x.steps == y.steps && x.pre == y.pre && x.no_out == y.no_out && x.d_sign == y.d_sign && (x.in == nullptr) == (y.in == nullptr) &&
+           (x.coarse == nullptr) == (y.coarse == nullptr) && (x.Fc == nullptr) == (y.Fc == nullptr) && x.Nc == y.Nc && x.M == y.M && a.L == b.L;
 }
 
 void drop_schedule(mg_cycle_plan *p)
@@ -947,9 +948,10 @@ void build_schedule(mg_cycle_plan *p)
     };
     std::vector<int> depth(p->ops.size(), 0);
     for (size_t i = 0; i < p->ops.size(); ++i) {
-        const NodeOp &o = p->ops[i];
-        const void *in[3] = {o.F, (o.kind != 2 && o.pre == 0) ? (const void *)o.src : nullptr, o.coarse};
-        const void *out[2] = {(o.kind == 2 || !o.no_out) ? (const void *)o.dst : nullptr, o.Fc};
+        const NodeOp &op = p->ops[i];
+        const k::SmoothNode<double> &o = op.node;
+        const void *in[3] = {o.F, (op.kind != 2 && o.pre == 0) ? (const void *)o.in : nullptr, o.coarse};
+        const void *out[2] = {(op.kind == 2 || !o.no_out) ? (const void *)o.out : nullptr, o.Fc};
         int d = 0;
         for (const void *q : in)
             if (q) d = std::max(d, depth_of(wrote, q));
@@ -1000,9 +1002,9 @@ void build_schedule(mg_cycle_plan *p)
                 host.insert(host.end(), (const char *)&it, (const char *)&it + sizeof it);
                 p->last_tail = std::max(p->last_tail, o.tail);
             } else {
-                const NodeBatchItem it{o.src, o.F, o.coarse, o.dst, o.Fc};
+                const NodeBatchItem it{o.node.in, o.node.F, o.node.coarse, o.node.out, o.node.Fc};
                 host.insert(host.end(), (const char *)&it, (const char *)&it + sizeof it);
-                g.errs.push_back(o.err);
+                g.errs.push_back(o.node.err);
             }
         }
         while (host.size() % 16) host.push_back(0);
@@ -1022,7 +1024,7 @@ void build_schedule(mg_cycle_plan *p)
                 p->sched_max_batch, (double)p->pool.bytes_held() / 1048576.0);
         for (const auto &g : p->sched)
             fprintf(stderr, "   depth %2d  %-44s N=%5d x%zu\n", g.depth, p->ops[(size_t)g.first].kind == 2 ? "coarse_tail" : p->ops[(size_t)g.first].name,
-                    p->ops[(size_t)g.first].N, g.members.size());
+                    p->ops[(size_t)g.first].node.N, g.members.size());
     }
 }
 
@@ -1038,7 +1040,7 @@ void replay_schedule(mg_cycle_plan *p)
         const NodeOp &o = p->ops[(size_t)g.first];
         const int n = (int)g.members.size();
         if (o.kind == 2) {
-            ProfScope ps(n > 1 ? "coarse_tail (batch)" : "coarse_tail", o.N, 0.0);
+            ProfScope ps(n > 1 ? "coarse_tail (batch)" : "coarse_tail", o.node.N, 0.0);
             k::tail_launch(c.stream, p->tails[(size_t)o.tail], n, (const TailBatchItem *)((const char *)p->sched_items + g.items_at));
         } else if (n == 1) {
             replay_node(o, nullptr);

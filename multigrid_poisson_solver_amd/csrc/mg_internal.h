@@ -57,6 +57,9 @@ struct ProlongTable {
     // owner -- an ADDRESS ingredient -- itself instead of waiting for a table load before it can issue its coarse loads
     bool closed_form = false;
 };
+// a table's weights in the field type: the fp64 array, or its fp32 rounding (the `_f` array)
+inline const double *weights_as(double, const double *w, const float *) { return w; }
+inline const float *weights_as(float, const double *, const float *w_f) { return w_f; }
 
 // a window of grid rows held in a local array: rows [base, base+rows) of the global grid
 // (base may be negative / extend past N: those rows are never touched), of which this rank
@@ -182,11 +185,9 @@ struct SlabFusion {
     bool no_out = false;  // `-1` launch: the smoothed field is not stored
     double *out_wide = nullptr;  // fp32 fields: the result goes to this fp64 window (same geometry, exact widening) instead of U_out
 };
-void slab_smooth(int N, double L, const double *U_in, double *U_out, const double *F, int step, double *raw_norm_out,
-                 const SlabFusion &sf);
-// the same launch on fp32 fields (mixed-precision slabs): the pointers inside sf are float arrays
-void slab_smooth_f32(int N, double L, const float *U_in, float *U_out, const float *F, int step, double *raw_norm_out,
-                     const SlabFusion &sf);
+// T = float: fp32 fields (mixed-precision slabs), and the pointers inside sf are float arrays
+template <typename T>
+void slab_smooth(int N, double L, const T *U_in, T *U_out, const T *F, int step, double *raw_norm_out, const SlabFusion &sf);
 
 // RCCL transport (mg_comm.cpp)
 bool comm_ready();
@@ -221,23 +222,48 @@ struct TailBatchItem {
     double *err_dev;    // the instance's error slots (node.err_slot counts from here)
     int *gs_state;
 };
+namespace k {
+// One fused smoothing node: level 0 (zero | in | in + P(coarse)), `steps` sweeps, the error norm, optionally the d_sign-ed
+// residual of the result stored or restricted.  The launchers (below) take it whole.  A field that a launcher does not
+// honour (noted per field) keeps its default; the tile launchers refuse the ones they would ignore.  T is the field type:
+// double, or float for the _f32 launchers.
+template <typename T>
+struct SmoothNode {
+    int N = 0;
+    T dx2 = 0, inv = 0;               // h^2 and 1/h^2 in the field type
+    const T *in = nullptr;            // level-0 input (nullptr: all zero; not read when pre > 0)
+    const T *F = nullptr;
+    T *out = nullptr;                 // the smoothed field
+    int steps = 0;                    // sweeps in this launch: 1..stream_max_steps() / 1..tile_max_steps()
+    double *err = nullptr;            // device slot of the smoothing error (fp64); with fine_w its raw sum over the counted rows
+    T *D = nullptr;                   // the d_sign-ed residual of the result, stored (streaming launchers only)
+    int d_sign = -1;                  // sign of the residual in D and of the one restricted into Fc
+    const T *coarse = nullptr;        // level 0 is in + doProlongation(coarse), Nc x Nc, with the tables pt
+    int Nc = 0;
+    const ProlongTable *pt = nullptr;
+    T *Fc = nullptr;                  // the residual restricted into Fc, M x M, with the tables rt
+    int M = 0;
+    const RestrictTable *rt = nullptr;
+    // row windows of the fine arrays, of coarse and of Fc for the 1-D row-slab decomposition (nullptr: the whole grid is local)
+    const RowWindow *fine_w = nullptr, *coarse_w = nullptr, *fc_w = nullptr;
+    int pre = 0;                      // fused `1` node: in is recomputed as pre sweeps from zero on F (streaming only)
+    bool no_out = false;              // fused `-1` node: out is not stored (its `1` node recomputes it)
+    double *out_wide = nullptr;       // the result goes to this fp64 array (exact widening) instead of out (jacobi_stream_f32)
+    // the same node on batch->n instances in one launch (jacobi_stream, jacobi_tile): in/F/out/coarse/Fc above then only tell
+    // the node's shape -- which of them a node of this kind has -- and err is ignored
+    const NodeBatch *batch = nullptr;
+    // != 0.25: the weighted sweep U + (cw*t) of the residual-tolerance solver (cw = 0.25*omega; jacobi_stream, no recomputing
+    // pair); 0.25 is the reference's sweep
+    double cw = 0.25;
+};
+}  // namespace k
+
 // One fused node launch as the cycle driver's dataflow trace records it (mg_cycle.cpp: build_schedule): while
 // Context::trace is set, the fused-node entry points describe their launch here instead of enqueueing it.
 struct NodeOp {
     int kind = 0;                 // 0: streaming kernel, 1: register-tile kernel, 2: coarse tail (tail = index of its TailArgs)
-    int N = 0;
     double L = 1.0;
-    const double *src = nullptr;  // level-0 input (nullptr: zero start, or recomputed when pre > 0)
-    double *F = nullptr, *dst = nullptr;
-    int take = 0;                 // sweeps
-    double *err = nullptr;        // device slot of the smoothing error
-    int d_sign = -1;
-    const double *coarse = nullptr;
-    int Nc = 0;
-    double *Fc = nullptr;
-    int M = 0;
-    int pre = 0;
-    bool no_out = false;
+    k::SmoothNode<double> node;   // the launch (a coarse tail: N, F, out)
     int tail = -1;
     char name[48] = {0};
     double bytes = 0.0;
@@ -270,39 +296,14 @@ bool stream_fusable(int N);   // the fused prolongation / restriction stages exi
 // the recomputing fused `1` node (pre sweeps from zero redone in flight, then `steps` more) is instantiated for this pair
 // in THIS build (it depends on the prefetch depth the library was compiled with, MG_PF)
 bool stream_recompute_supported(int pre, int steps);
-// coarse != nullptr: level 0 is in + doProlongation(coarse) (tables pt).  Fc != nullptr: the
-// d_sign-ed residual of the result is restricted into Fc (M x M, tables rt).
-// fine_w / coarse_w / fc_w: row windows of the fine arrays, the coarse input and the coarse
-// output for the 1-D row-slab decomposition (nullptr = the whole grid is local).
-void jacobi_stream(hipStream_t s, int N, double dx2, double inv, const double *in, const double *F,
-                   double *out, int steps, double *err_out, double *D_out, int d_sign,
-                   const double *coarse, int Nc, const ProlongTable *pt, double *Fc, int M,
-                   const RestrictTable *rt, const RowWindow *fine_w = nullptr,
-                   const RowWindow *coarse_w = nullptr, const RowWindow *fc_w = nullptr,
-                   // pre > 0 (fused `1` node): `in` is not read, it is recomputed as `pre` sweeps from zero on F;
-                   // no_out (fused `-1` node): the smoothed field is not stored (its `1` node will recompute it)
-                   int pre = 0, bool no_out = false,
-                   // batch: the same node on batch->n instances in one launch (in/F/out/coarse/Fc above then only tell the
-                   // node's shape -- which of them a node of this kind has -- and err_out is ignored)
-                   const NodeBatch *batch = nullptr,
-                   // cw != 0.25: the weighted sweep U + (cw*t) of the residual-tolerance solver (cw = 0.25*omega, fp64, no
-                   // recomputing pair; a batch: the batched solver); 0.25 is the reference's sweep
-                   double cw = 0.25);
-// register-tile fused nodes of the small levels (mg_tile.hip / mg_tile_f32.hip): one launch = level 0 (zero | in | in +
-// P(coarse)), `steps` sweeps, the error norm, optionally the d_sign-ed residual restricted into Fc; whole grid only
+void jacobi_stream(hipStream_t s, const SmoothNode<double> &node);
+// register-tile fused nodes of the small levels (mg_tile.hip / mg_tile_f32.hip): the node in one launch, without a stored
+// residual and without the recomputing or the weighted form
 bool tile_wanted(int N);      // MG_TILE_MIN_N <= N <= MG_TILE_MAX_N
 bool tile_wanted_slab(int N); // the same for a launch on a row window (a slab of a distributed level): up to MG_TILE_SLAB_MAX_N
 int  tile_max_steps();
-// fine_w / coarse_w / fc_w: row windows as in jacobi_stream (nullptr = the whole grid is local); with a fine window the error
-// output is the raw sum over the counted rows
-void jacobi_tile(hipStream_t s, int N, double dx2, double inv, const double *in, const double *F, double *out, int steps,
-                 double *err_out, int d_sign, const double *coarse, int Nc, const ProlongTable *pt, double *Fc, int M,
-                 const RestrictTable *rt, bool no_out, const RowWindow *fine_w = nullptr, const RowWindow *coarse_w = nullptr,
-                 const RowWindow *fc_w = nullptr, const NodeBatch *batch = nullptr);   // batch: as in jacobi_stream
-void jacobi_tile_f32(hipStream_t s, int N, float dx2, float inv, const float *in, const float *F, float *out, int steps,
-                     double *err_out, int d_sign, const float *coarse, int Nc, const ProlongTable *pt, float *Fc, int M,
-                     const RestrictTable *rt, bool no_out, const RowWindow *fine_w = nullptr, const RowWindow *coarse_w = nullptr,
-                     const RowWindow *fc_w = nullptr);
+void jacobi_tile(hipStream_t s, const SmoothNode<double> &node);
+void jacobi_tile_f32(hipStream_t s, const SmoothNode<float> &node);
 void restrict_gather(hipStream_t s, int N, const double *Uf, int M, double *Uc, const RestrictTable &t, int sign);
 // Uf_out = (Uf_in ? Uf_in : 0) + P(Uc); when Uf_in == nullptr unowned fine points are left untouched
 void prolong(hipStream_t s, int N, const double *Uc, int M, const double *Uf_in, double *Uf_out, const ProlongTable &t);
@@ -325,13 +326,8 @@ void analytic_error_rows(hipStream_t s, int N, double L, const double *U, const 
                          double min_y, double *out_raw);
 void fill_uniform(hipStream_t s, double *dst, size_t n, uint64_t seed);
 void checksum(hipStream_t s, const double *src, size_t n, uint64_t *out_dev /*[2]*/);
-// fp32 instantiation of the streaming smoother (mg_stream_f32.hip): zero start or prolongation input,
-// optional restriction output; whole grid local
-void jacobi_stream_f32(hipStream_t s, int N, float dx2, float inv, const float *in, const float *F, float *out, int steps,
-                       double *err_out, const float *coarse, int Nc, const ProlongTable *pt, float *Fc, int M,
-                       const RestrictTable *rt, const RowWindow *fine_w = nullptr, const RowWindow *coarse_w = nullptr,
-                       const RowWindow *fc_w = nullptr, double *out_wide = nullptr, float *D_out = nullptr, int d_sign = -1,
-                       int pre = 0, bool no_out = false);  // pre / no_out: as in jacobi_stream
+// fp32 instantiation of the streaming smoother (mg_stream_f32.hip)
+void jacobi_stream_f32(hipStream_t s, const SmoothNode<float> &node);
 // coarse tail of a cycle in one launch (mg_tail.hip): the node slice that stays on levels N <= 64
 constexpr int TAIL_MAX_LEVELS = 6;
 constexpr int TAIL_MAX_NODES = 48;

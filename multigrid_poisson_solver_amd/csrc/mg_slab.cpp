@@ -475,10 +475,10 @@ void run(mg_slab_plan *p)
                     // the level's `1` launch recomputes it
                     sf.no_out = plan_cur.pre > 0;
                     if (p->mixed)
-                        slab_smooth_f32(cur.N, p->L, nullptr, (float *)cur.loc[i].U, (const float *)cur.loc[i].F, step,
-                                        raw_slot(p, (size_t)rec, i), sf);
+                        slab_smooth<float>(cur.N, p->L, nullptr, (float *)cur.loc[i].U, (const float *)cur.loc[i].F, step,
+                                           raw_slot(p, (size_t)rec, i), sf);
                     else
-                        slab_smooth(cur.N, p->L, nullptr, cur.loc[i].U, cur.loc[i].F, step, raw_slot(p, (size_t)rec, i), sf);
+                        slab_smooth<double>(cur.N, p->L, nullptr, cur.loc[i].U, cur.loc[i].F, step, raw_slot(p, (size_t)rec, i), sf);
                 }
                 p->levels.push_back(nxt);
                 Level &fine_lv = p->levels[p->levels.size() - 2], &next_lv = p->levels.back();
@@ -549,8 +549,8 @@ void run(mg_slab_plan *p)
                         p->top_widened = true;
                     }
                     if (p->mixed)
-                        slab_smooth_f32(fine.N, p->L, sf.pre ? nullptr : (const float *)fine.loc[i].U, (float *)fine.loc[i].D,
-                                        (const float *)fine.loc[i].F, step, raw_slot(p, (size_t)rec, i), sf);
+                        slab_smooth<float>(fine.N, p->L, sf.pre ? nullptr : (const float *)fine.loc[i].U, (float *)fine.loc[i].D,
+                                           (const float *)fine.loc[i].F, step, raw_slot(p, (size_t)rec, i), sf);
                     else
                         slab_smooth(fine.N, p->L, sf.pre ? nullptr : fine.loc[i].U, fine.loc[i].D, fine.loc[i].F, step,
                                     raw_slot(p, (size_t)rec, i), sf);

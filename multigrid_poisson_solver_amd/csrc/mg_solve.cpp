@@ -167,11 +167,10 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
         double *out = l == 0 ? s->B[0] : s->A[l], *scratch = l == 0 ? U0 : s->B[l];
         const RestrictTable &rt = restrict_table(N, M);
         if (k::stream_fusable(N) && rt.fusable) {
-            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.pre, nullptr, nullptr, -1, nullptr, 0, nullptr, s->F[l + 1], M, &rt,
-                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .Fc = s->F[l + 1], .M = M,
+                                  .rt = &rt, .cw = cw});
         } else {
-            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.pre, nullptr, nullptr, -1, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .cw = cw});
             k::residual(st, N, inv, out, F, scratch, -1);
             k::restrict_gather(st, N, scratch, M, s->F[l + 1], rt, +1);
         }
@@ -189,14 +188,13 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
         double *in = x[l], *out = l == 0 ? U0 : s->B[l];
         const ProlongTable &pt = prolong_table(Nc_l, N);
         if (k::stream_fusable(N) && pt.fusable) {
-            k::jacobi_stream(st, N, dx2, inv, in, F, out, o.post, nullptr, nullptr, +1, x[l + 1], Nc_l, &pt, nullptr, 0, nullptr,
-                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.post, .d_sign = +1,
+                                  .coarse = x[l + 1], .Nc = Nc_l, .pt = &pt, .cw = cw});
             x[l] = out;
         } else {
             // U + doProlongation(U_c) (:354, :368) into `out`, the sweeps back into `in`
             k::prolong(st, Nc_l, x[l + 1], N, in, out, pt);
-            k::jacobi_stream(st, N, dx2, inv, out, F, in, o.post, nullptr, nullptr, +1, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                             nullptr, nullptr, nullptr, 0, false, nullptr, cw);
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = out, .F = F, .out = in, .steps = o.post, .d_sign = +1, .cw = cw});
             x[l] = in;
         }
     }

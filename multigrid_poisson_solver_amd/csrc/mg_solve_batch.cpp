@@ -135,13 +135,16 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
         const NodeBatchItem &it = h[(size_t)t * mb];
         const NodeBatch nb = node(t);
         const RestrictTable &rt = restrict_table(N, M);
+        k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
+                                 .out = (double *)it.out, .steps = o.pre, .batch = &nb, .cw = cw};
         if (down_fused(s, l)) {
-            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.pre, nullptr, nullptr,
-                             -1, nullptr, 0, nullptr, (double *)it.Fc, M, &rt, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            nd.Fc = (double *)it.Fc;
+            nd.M = M;
+            nd.rt = &rt;
+            k::jacobi_stream(st, nd);
             launches += 1;
         } else {
-            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.pre, nullptr, nullptr,
-                             -1, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            k::jacobi_stream(st, nd);
             k::residual_batch(st, n, N, inv, d + (size_t)(t + 1) * mb, -1);
             k::restrict_batch(st, n, N, M, d + (size_t)(t + 2) * mb, rt, +1);
             launches += 3;
@@ -160,14 +163,17 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
         const NodeBatchItem &it = h[(size_t)t * mb];
         const NodeBatch nb = node(t);
         const ProlongTable &pt = prolong_table(Nc_l, N);
+        k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
+                                 .out = (double *)it.out, .steps = o.post, .d_sign = +1, .batch = &nb, .cw = cw};
         if (up_fused(s, l)) {
-            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.post, nullptr, nullptr,
-                             +1, (const double *)it.coarse, Nc_l, &pt, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            nd.coarse = (const double *)it.coarse;
+            nd.Nc = Nc_l;
+            nd.pt = &pt;
+            k::jacobi_stream(st, nd);
             launches += 1;
         } else {
             k::prolong_add_batch(st, n, Nc_l, N, d + (size_t)(t + 1) * mb, pt);
-            k::jacobi_stream(st, N, dx2, inv, (const double *)it.in, (const double *)it.F, (double *)it.out, o.post, nullptr, nullptr,
-                             +1, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, false, &nb, cw);
+            k::jacobi_stream(st, nd);
             launches += 2;
             copy = l == 0;   // the result is in B[0], not in the caller's U
         }

@@ -69,17 +69,6 @@ namespace MG_REAL_NS {
 
 typedef MG_REAL real_t;
 
-// host-built transfer tables in the field type (weights) -- see mg_tables.cpp
-struct StreamTables {
-    const int *p_orow = nullptr, *p_ocol = nullptr;
-    const real_t *p_rhi = nullptr, *p_rlo = nullptr, *p_chi = nullptr, *p_clo = nullptr;
-    real_t c_dx = 0, c_dx_rcp = 0;
-    bool p_cols4_ok = false;   // ProlongTable::fusable4
-    const int *r_inv = nullptr;
-    const real_t *r_w = nullptr, *r_wf = nullptr;
-};
-
-
 constexpr int PF_DEFAULT = 2;    // rows of U and F in flight per lane (FIFO of 2*PF slots)
 #ifndef MG_WAVES_PER_WG
 #define MG_WAVES_PER_WG 4        // (experiment switch: scripts/build_variant.sh -DMG_WAVES_PER_WG=1|2|8)
@@ -1304,29 +1293,26 @@ void launch_steps(hipStream_t s, const StreamParams &p, double *err_out)
 }
 
 
-// entry point of this instantiation: same contract as k::jacobi_stream (mg_internal.h) in the
-// field type real_t; tb carries the tables the fused stages need
-inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, const real_t *F, real_t *out, int steps,
-                double *err_out, real_t *D_out, int d_sign, const real_t *coarse, int Nc, real_t *Fc, int M,
-                const StreamTables &tb, const RowWindow *fine_w, const RowWindow *coarse_w, const RowWindow *fc_w,
-                double *out_wide = nullptr, int pre = 0, bool no_out = false, const NodeBatch *batch = nullptr,
-                double cw = 0.25)
+// entry point of this instantiation: k::jacobi_stream (mg_internal.h) in the field type real_t
+inline void run(hipStream_t s, const SmoothNode<real_t> &nd)
 {
-    if (batch && (fine_w || coarse_w || fc_w || D_out || out_wide || batch->n < 1)) {
+    const int N = nd.N, steps = nd.steps, pre = nd.pre;
+    const RowWindow *fine_w = nd.fine_w;
+    if (nd.batch && (fine_w || nd.coarse_w || nd.fc_w || nd.D || nd.out_wide || nd.batch->n < 1)) {
         fail(MG_ERR_ARG, "jacobi_stream: a batch of instances runs whole grids without a stored residual");
         return;
     }
-    if (pre != 0 && !(recompute_instantiated(pre, steps) && coarse && !Fc)) {
+    if (pre != 0 && !(recompute_instantiated(pre, steps) && nd.coarse && !nd.Fc)) {
         fail(MG_ERR_ARG, "jacobi_stream: recomputed pre-smoothing exists for pre + steps <= 6 sweeps of the fused `1` node (pre=%d steps=%d)", pre, steps);
         return;
     }
     // (a batch of weighted nodes: the batched solver, mg_solve_batch.cpp -- the kernel body takes every instance's arrays,
     // `in` included, from the table; slab windows are refused above for every batch)
-    if (cw != 0.25 && (pre != 0 || sizeof(real_t) != 8)) {
+    if (nd.cw != 0.25 && (pre != 0 || sizeof(real_t) != 8)) {
         fail(MG_ERR_ARG, "jacobi_stream: the weighted sweep runs fp64 nodes that store and re-read U");
         return;
     }
-    if (pre != 0 && D_out) {
+    if (pre != 0 && nd.D) {
         fail(MG_ERR_ARG, "jacobi_stream: the recomputing `1` node forms the error norm only, it stores no residual");
         return;
     }
@@ -1334,29 +1320,29 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
         fail(MG_ERR_ARG, "jacobi_stream: %d sweeps per launch (1..%d)", steps, MAX_S);
         return;
     }
-    if ((coarse || Fc) && (N < 4 || N % 2 != 0)) {
+    if ((nd.coarse || nd.Fc) && (N < 4 || N % 2 != 0)) {
         fail(MG_ERR_ARG, "jacobi_stream: fused transfer stages need an even grid size (N=%d)", N);
         return;
     }
     StreamParams p = {};
-    if (batch) {
-        p.batch = batch->dev;
-        p.n_batch = batch->n;
-        p.err_outs = batch->err_outs;
+    if (nd.batch) {
+        p.batch = nd.batch->dev;
+        p.n_batch = nd.batch->n;
+        p.err_outs = nd.batch->err_outs;
     }
     p.N = N;
-    p.dx2 = dx2;
-    p.inv = inv;
-    p.in = in;
-    p.F = F;
-    p.out = out;
-    p.out_wide = out_wide;
+    p.dx2 = nd.dx2;
+    p.inv = nd.inv;
+    p.in = nd.in;
+    p.F = nd.F;
+    p.out = nd.out;
+    p.out_wide = nd.out_wide;
     p.pre = pre;
-    p.no_out = no_out ? 1 : 0;
-    p.cw = (real_t)cw;
-    p.wt = cw != 0.25 ? 1 : 0;   // (0.25: the unweighted instantiations, the same bits: the product with 0.25 is exact)
-    p.D = D_out;
-    p.d_sign = d_sign;
+    p.no_out = nd.no_out ? 1 : 0;
+    p.cw = (real_t)nd.cw;
+    p.wt = nd.cw != 0.25 ? 1 : 0;   // (0.25: the unweighted instantiations, the same bits: the product with 0.25 is exact)
+    p.D = nd.D;
+    p.d_sign = nd.d_sign;
     p.row_base = fine_w ? fine_w->base : 0;
     p.rows_local = fine_w ? fine_w->rows : N;
     p.own_y0 = fine_w ? fine_w->own_lo : 0;
@@ -1365,37 +1351,39 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
     p.norm_y1 = fine_w && fine_w->norm_lo >= 0 ? fine_w->norm_hi : p.own_y1;
     p.raw_norm = fine_w ? 1 : 0;
     static const int cols4_min = [] { const char *e = getenv("MG_F32_COLS4_MIN_N"); return e ? atoi(e) : 8192; }();  // (measured: a gain only where the launch is bandwidth-bound, N >= 8192)
-    p.cols4 = (sizeof(real_t) == 4 && N % 4 == 0 && N >= cols4_min && (!coarse || tb.p_cols4_ok)) ? 1 : 0;
+    p.cols4 = (sizeof(real_t) == 4 && N % 4 == 0 && N >= cols4_min && (!nd.coarse || nd.pt->fusable4)) ? 1 : 0;
     static const int nt_min = [] { const char *e = getenv("MG_NT_MIN_N"); return e ? atoi(e) : 8192; }();
     p.nt_min_n = nt_min;
-    if (coarse) {
-        p.coarse_base = coarse_w ? coarse_w->base : 0;
-        p.coarse_rows = coarse_w ? coarse_w->rows : Nc;
-        p.coarse = coarse;
-        p.Nc = Nc;
-        p.p_orow = tb.p_orow;
-        p.p_ocol = tb.p_ocol;
-        p.p_rhi = tb.p_rhi;
-        p.p_rlo = tb.p_rlo;
-        p.p_chi = tb.p_chi;
-        p.p_clo = tb.p_clo;
-        p.c_dx = tb.c_dx;
-        p.c_dx_rcp = tb.c_dx_rcp;
+    if (nd.coarse) {
+        const ProlongTable &pt = *nd.pt;
+        p.coarse_base = nd.coarse_w ? nd.coarse_w->base : 0;
+        p.coarse_rows = nd.coarse_w ? nd.coarse_w->rows : nd.Nc;
+        p.coarse = nd.coarse;
+        p.Nc = nd.Nc;
+        p.p_orow = pt.owner_row;
+        p.p_ocol = pt.owner_col;
+        p.p_rhi = weights_as(real_t(), pt.row_hi, pt.row_hi_f);
+        p.p_rlo = weights_as(real_t(), pt.row_lo, pt.row_lo_f);
+        p.p_chi = weights_as(real_t(), pt.col_hi, pt.col_hi_f);
+        p.p_clo = weights_as(real_t(), pt.col_lo, pt.col_lo_f);
+        p.c_dx = (real_t)pt.c_dx;
+        p.c_dx_rcp = (real_t)1 / p.c_dx;  // IEEE division on the host: correctly rounded
     }
-    if (Fc) {
-        p.fc_base = fc_w ? fc_w->base : 0;
-        p.fc_rows = fc_w ? fc_w->rows : M;
-        p.Fc = Fc;
-        p.M = M;
-        p.r_inv = tb.r_inv;
-        p.r_w = tb.r_w;
-        p.r_wf = tb.r_wf;
+    if (nd.Fc) {
+        const RestrictTable &rt = *nd.rt;
+        p.fc_base = nd.fc_w ? nd.fc_w->base : 0;
+        p.fc_rows = nd.fc_w ? nd.fc_w->rows : nd.M;
+        p.Fc = nd.Fc;
+        p.M = nd.M;
+        p.r_inv = rt.inv;
+        p.r_w = weights_as(real_t(), rt.w, rt.w_f);
+        p.r_wf = weights_as(real_t(), rt.inv_w, rt.inv_w_f);
     }
     switch (steps) {
-        case 1: launch_steps<1>(s, p, err_out); break;
-        case 2: launch_steps<2>(s, p, err_out); break;
-        case 3: launch_steps<3>(s, p, err_out); break;
-        default: launch_steps<4>(s, p, err_out); break;
+        case 1: launch_steps<1>(s, p, nd.err); break;
+        case 2: launch_steps<2>(s, p, nd.err); break;
+        case 3: launch_steps<3>(s, p, nd.err); break;
+        default: launch_steps<4>(s, p, nd.err); break;
     }
 }
 

@@ -26,30 +26,7 @@ bool tile_wanted_slab(int N)
 }
 int tile_max_steps() { return f64::tile::MAX_S; }
 
-void jacobi_tile(hipStream_t s, int N, double dx2, double inv, const double *in, const double *F, double *out, int steps,
-                 double *err_out, int d_sign, const double *coarse, int Nc, const ProlongTable *pt, double *Fc, int M,
-                 const RestrictTable *rt, bool no_out, const RowWindow *fine_w, const RowWindow *coarse_w, const RowWindow *fc_w,
-                 const NodeBatch *batch)
-{
-    f64::tile::Tables tb;
-    if (coarse) {
-        tb.p_orow = pt->owner_row;
-        tb.p_ocol = pt->owner_col;
-        tb.p_rhi = pt->row_hi;
-        tb.p_rlo = pt->row_lo;
-        tb.p_chi = pt->col_hi;
-        tb.p_clo = pt->col_lo;
-        tb.c_dx = pt->c_dx;
-        tb.c_dx_rcp = 1.0 / pt->c_dx;  // IEEE division on the host: correctly rounded
-        tb.p_closed = pt->closed_form;
-    }
-    if (Fc) {
-        tb.r_inv = rt->inv;
-        tb.r_w = rt->w;
-        tb.r_wf = rt->inv_w;
-    }
-    f64::tile::run(s, N, dx2, inv, in, F, out, steps, err_out, d_sign, coarse, Nc, Fc, M, tb, no_out, fine_w, coarse_w, fc_w, batch);
-}
+void jacobi_tile(hipStream_t s, const SmoothNode<double> &node) { f64::tile::run(s, node); }
 
 }  // namespace k
 }  // namespace mg

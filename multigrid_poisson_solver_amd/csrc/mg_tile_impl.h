@@ -465,25 +465,19 @@ void launch_steps(hipStream_t s, const TileParams &p, double *err_out, bool raw_
     }
 }
 
-struct Tables {
-    const int *p_orow = nullptr, *p_ocol = nullptr;
-    const real_t *p_rhi = nullptr, *p_rlo = nullptr, *p_chi = nullptr, *p_clo = nullptr;
-    real_t c_dx = 0, c_dx_rcp = 0;
-    bool p_closed = false;   // ProlongTable::closed_form
-    const int *r_inv = nullptr;
-    const real_t *r_w = nullptr, *r_wf = nullptr;
-};
-
 constexpr int MAX_S = 4;
 
-// one fused node on the whole grid: same contract as the streaming kernel's entry point without row windows, without a
-// stored residual and without the recomputing form (the caller routes those to the streaming kernel)
-inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, const real_t *F, real_t *out, int steps, double *err_out,
-                int d_sign, const real_t *coarse, int Nc, real_t *Fc, int M, const Tables &tb, bool no_out,
-                const RowWindow *fine_w = nullptr, const RowWindow *coarse_w = nullptr, const RowWindow *fc_w = nullptr,
-                const NodeBatch *batch = nullptr)
+// entry point of this instantiation: k::jacobi_tile (mg_internal.h) in the field type real_t.  The caller routes a stored
+// residual and the recomputing and weighted forms to the streaming kernel.
+inline void run(hipStream_t s, const SmoothNode<real_t> &nd)
 {
-    if (batch && (fine_w || coarse_w || fc_w || batch->n < 1)) {
+    const int N = nd.N, steps = nd.steps;
+    const RowWindow *fine_w = nd.fine_w;
+    if (nd.D || nd.pre || nd.out_wide || nd.cw != 0.25) {
+        fail(MG_ERR_ARG, "jacobi_tile: no stored residual, no recomputing or weighted form");
+        return;
+    }
+    if (nd.batch && (fine_w || nd.coarse_w || nd.fc_w || nd.batch->n < 1)) {
         fail(MG_ERR_ARG, "jacobi_tile: a batch of instances runs whole grids");
         return;
     }
@@ -491,24 +485,24 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
         fail(MG_ERR_ARG, "jacobi_tile: %d sweeps on N=%d (1..%d sweeps, N >= 8)", steps, N, MAX_S);
         return;
     }
-    if (coarse && Fc) {
+    if (nd.coarse && nd.Fc) {
         fail(MG_ERR_ARG, "jacobi_tile: a node either prolongs or restricts");
         return;
     }
     TileParams p = {};
-    if (batch) {
-        p.batch = batch->dev;
-        p.n_batch = batch->n;
-        p.err_outs = batch->err_outs;
+    if (nd.batch) {
+        p.batch = nd.batch->dev;
+        p.n_batch = nd.batch->n;
+        p.err_outs = nd.batch->err_outs;
     }
     p.N = N;
-    p.dx2 = dx2;
-    p.inv = inv;
-    p.in = in;
-    p.F = F;
-    p.out = out;
-    p.no_out = no_out ? 1 : 0;
-    p.d_sign = d_sign;
+    p.dx2 = nd.dx2;
+    p.inv = nd.inv;
+    p.in = nd.in;
+    p.F = nd.F;
+    p.out = nd.out;
+    p.no_out = nd.no_out ? 1 : 0;
+    p.d_sign = nd.d_sign;
     p.row_base = fine_w ? fine_w->base : 0;
     p.rows_local = fine_w ? fine_w->rows : N;
     p.own_y0 = fine_w ? fine_w->own_lo : 0;
@@ -516,37 +510,39 @@ inline void run(hipStream_t s, int N, real_t dx2, real_t inv, const real_t *in, 
     p.norm_y0 = fine_w && fine_w->norm_lo >= 0 ? fine_w->norm_lo : p.own_y0;
     p.norm_y1 = fine_w && fine_w->norm_lo >= 0 ? fine_w->norm_hi : p.own_y1;
     p.coarse_rows = 1;
-    if (coarse) {
-        p.coarse_base = coarse_w ? coarse_w->base : 0;
-        p.coarse_rows = coarse_w ? coarse_w->rows : Nc;
-        p.coarse = coarse;
-        p.Nc = Nc;
-        p.p_orow = tb.p_orow;
-        p.p_ocol = tb.p_ocol;
-        p.p_rhi = tb.p_rhi;
-        p.p_rlo = tb.p_rlo;
-        p.p_chi = tb.p_chi;
-        p.p_clo = tb.p_clo;
-        p.c_dx = tb.c_dx;
-        p.c_dx_rcp = tb.c_dx_rcp;
+    if (nd.coarse) {
+        const ProlongTable &pt = *nd.pt;
+        p.coarse_base = nd.coarse_w ? nd.coarse_w->base : 0;
+        p.coarse_rows = nd.coarse_w ? nd.coarse_w->rows : nd.Nc;
+        p.coarse = nd.coarse;
+        p.Nc = nd.Nc;
+        p.p_orow = pt.owner_row;
+        p.p_ocol = pt.owner_col;
+        p.p_rhi = weights_as(real_t(), pt.row_hi, pt.row_hi_f);
+        p.p_rlo = weights_as(real_t(), pt.row_lo, pt.row_lo_f);
+        p.p_chi = weights_as(real_t(), pt.col_hi, pt.col_hi_f);
+        p.p_clo = weights_as(real_t(), pt.col_lo, pt.col_lo_f);
+        p.c_dx = (real_t)pt.c_dx;
+        p.c_dx_rcp = (real_t)1 / p.c_dx;  // IEEE division on the host: correctly rounded
         static const bool no_closed = getenv("MG_TILE_NO_CLOSED_FORM") != nullptr;   // A/B switch
-        p.own_closed = (tb.p_closed && !no_closed && N <= 4096) ? 1 : 0;
+        p.own_closed = (pt.closed_form && !no_closed && N <= 4096) ? 1 : 0;
         p.own_rcp = 1.0f / (float)(N - 1);
     }
-    if (Fc) {
-        p.fc_base = fc_w ? fc_w->base : 0;
-        p.Fc = Fc;
-        p.M = M;
-        p.r_inv = tb.r_inv;
-        p.r_w = tb.r_w;
-        p.r_wf = tb.r_wf;
+    if (nd.Fc) {
+        const RestrictTable &rt = *nd.rt;
+        p.fc_base = nd.fc_w ? nd.fc_w->base : 0;
+        p.Fc = nd.Fc;
+        p.M = nd.M;
+        p.r_inv = rt.inv;
+        p.r_w = weights_as(real_t(), rt.w, rt.w_f);
+        p.r_wf = weights_as(real_t(), rt.inv_w, rt.inv_w_f);
     }
     const bool raw_norm = fine_w != nullptr;
     switch (steps) {
-        case 1: launch_steps<1>(s, p, err_out, raw_norm); break;
-        case 2: launch_steps<2>(s, p, err_out, raw_norm); break;
-        case 3: launch_steps<3>(s, p, err_out, raw_norm); break;
-        default: launch_steps<4>(s, p, err_out, raw_norm); break;
+        case 1: launch_steps<1>(s, p, nd.err, raw_norm); break;
+        case 2: launch_steps<2>(s, p, nd.err, raw_norm); break;
+        case 3: launch_steps<3>(s, p, nd.err, raw_norm); break;
+        default: launch_steps<4>(s, p, nd.err, raw_norm); break;
     }
 }
 
