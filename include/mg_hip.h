@@ -61,10 +61,15 @@ void    mg_pool_trim(void);
 size_t  mg_pool_bytes(void);
 void    mg_upload(double *dev, const double *host, size_t n_doubles);   /* synchronous */
 void    mg_download(double *host, const double *dev, size_t n_doubles); /* synchronous */
+/* Memory contract of every entry point that takes a device array (tests/test_memory_contract_gpu.py holds each call to
+ * it inside guard bands): a call writes the arrays it is documented to write and nothing else -- not one byte before or
+ * after them -- and only reads the others.  `const` arguments are read only; for the non-const pointers of the drop-in
+ * signatures the comment at the prototype says which are read only.  The one input a call may overwrite is U_in of
+ * mg_smooth_pp.  Arrays need the alignment of mg_alloc's blocks at most (16 bytes is what the solvers demand). */
 void    mg_copy(double *dst_dev, const double *src_dev, size_t n_doubles);
 /* memset(U, 0, N*N*8): src/MG_solver_CPU.cpp:213,256 */
 void    mg_fill_zero(double *dev, size_t n_doubles);
-/* D[i] = -D[i] for all N*N entries: the driver's own loop, src/MG_solver_CPU.cpp:277-280 */
+/* D[i] = -D[i] (in place) for all N*N entries: the driver's own loop, src/MG_solver_CPU.cpp:277-280 */
 void    mg_negate(int N, double *D);
 
 /* ------------------------------------------------------------------------- */
@@ -92,19 +97,20 @@ void mg_analyticError(int N, double L, const double *U, double min_x, double min
 /* ------------------------------------------------------------------------- */
 /* the six operators: src/MG_solver_CPU.cpp:23-28 (same order, same arguments)  */
 /* ------------------------------------------------------------------------- */
-/* :554-564 */
+/* :554-564.  U and F are read only; every element of D is written (the rim: zero) */
 void mg_getResidual(int N, double L, double *U, double *F, double *D);
-/* :566-571 */
+/* :566-571: U1 += U2.  U2 is read only */
 void mg_doGridAddition(int N, double *U1, double *U2);
 /* :573-625.  error is a HOST pointer (as in the reference, where it points into the
- * ListNode); the call returns after the value is written.  NULL = not wanted. */
+ * ListNode); the call returns after the value is written.  NULL = not wanted.  U is smoothed in place, F is read only. */
 void mg_doSmoothing(int N, double L, double *U, double *F, int step, double *error);
 /* :627-638, option 1 = red-black Gauss-Seidel :952-1066.  option 0 (dense inverse) is
- * refused with the message of src/MG_solver_GPU.cu:1286-1289. */
+ * refused with the message of src/MG_solver_GPU.cu:1286-1289.  U is written (whatever it held is ignored: the solve starts
+ * from zero), F is read only. */
 void mg_doExactSolver(int N, double L, double *U, double *F, double target_error, int option);
-/* :640-680 */
+/* :640-680.  U_f is read only; every element of U_c is written */
 void mg_doRestriction(int N, double *U_f, int M, double *U_c);
-/* :682-724 */
+/* :682-724.  U_c is read only; the points of U_f that no coarse cell owns keep their values */
 void mg_doProlongation(int N, double *U_c, int M, double *U_f);
 
 /* ------------------------------------------------------------------------- */
@@ -115,20 +121,22 @@ void mg_doProlongation(int N, double *U_c, int M, double *U_f);
  * (the driver's memset of src/MG_solver_CPU.cpp:256 folded into the first sweep).
  * error_dev (device pointer or NULL) receives doSmoothing's error; D_out (device
  * pointer or NULL) receives getResidual(U_out) times d_sign (+1 or -1: the driver's
- * sign flip :277-280 folded in). */
+ * sign flip :277-280 folded in).  F is read only. */
 void mg_smooth_pp(int N, double L, const double *U_in, double *U_out, double *F, int step,
                   double *error_dev, double *D_out, int d_sign);
 /* one "-1" node of the driver (:259-287): U_out = smooth^step(U_in or 0), then
- * F_c = doRestriction(N, -getResidual(U_out), M) -- one pass over HBM when fusable */
+ * F_c = doRestriction(N, -getResidual(U_out), M) -- one pass over HBM when fusable.  U_in and F are read only (when
+ * several launches are needed the partner of U_out is engine scratch, not U_in). */
 void mg_smooth_restrict(int N, double L, const double *U_in, double *U_out, double *F, int step,
                         double *error_dev, int M, double *F_c);
-/* one "1" node of the driver (:353-416): U_out = smooth^step(U_in + doProlongation(Nc, U_c, N)) */
+/* one "1" node of the driver (:353-416): U_out = smooth^step(U_in + doProlongation(Nc, U_c, N)).  U_c, U_in and F are
+ * read only. */
 void mg_prolong_smooth(int Nc, const double *U_c, int N, double L, const double *U_in, double *U_out,
                        double *F, int step, double *error_dev);
 /* mixed-precision mode (README.md:269-270 of the reference: "single
  * precision" GPU kernels): the two fused nodes with every array and every arithmetic operation
  * in fp32 (norms in fp64).  Zero start only for the "-1" node; 1..4 steps.  Even N with a nested
- * coarse size runs as ONE launch, anything else operator by operator (same results). */
+ * coarse size runs as ONE launch, anything else operator by operator (same results).  F (and U_c, U_in) are read only. */
 void   mg_smooth_restrict_f32(int N, double L, const float *U_in, float *U_out, float *F, int step,
                               double *error_dev, int M, float *F_c);
 void   mg_prolong_smooth_f32(int Nc, const float *U_c, int N, double L, const float *U_in, float *U_out,

@@ -55,6 +55,7 @@ void *Pool::get(size_t bytes)
         void *p = it->second;
         free_.erase(it);
         live_[p] = bytes;
+        if (poison_) poison_block(p, bytes);
         return p;
     }
     void *p = nullptr;
@@ -66,7 +67,24 @@ void *Pool::get(size_t bytes)
     }
     held_ += bytes;
     live_[p] = bytes;
+    if (poison_) poison_block(p, bytes);
     return p;
+}
+
+bool pool_poison_wanted()
+{
+    const char *e = getenv("MG_POOL_POISON");
+    return e && strcmp(e, "0") != 0;
+}
+
+void poison_block(void *p, size_t bytes)
+{
+    if (!p) return;
+    hipStream_t s = ctx().stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+    if (cs != hipStreamCaptureStatusNone) return;
+    (void)MG_HIP(hipMemsetAsync(p, 0xFF, bytes, s));
 }
 
 void Pool::put(void *p)
@@ -272,7 +290,11 @@ double node_profile(const char *kernel, const k::SmoothNode<double> &nd, char (&
 // One smoothing node on the whole grid: nd.steps sweeps from nd.in (nullptr: zero) into nd.out, in one fused launch or
 // several.  The fused transfer stages (streaming smoother only) go to the first launch (coarse: level 0 = in + P(coarse))
 // and the last (Fc: restriction of the signed residual); so do the error and a stored residual (D).  dx2 / inv are set here.
-void smooth_pp(double L, k::SmoothNode<double> nd)
+// Several launches ping-pong between nd.out and a partner array.  Every call site says which: INPUT_IS_PARTNER -- nd.in is
+// overwritten (mg_smooth_pp's documented clobber, and callers whose input is their own scratch) -- or KEEP_INPUT -- nd.in
+// is only read, the partner comes from the scratch pool.
+enum PingPong { KEEP_INPUT, INPUT_IS_PARTNER };
+void smooth_pp(double L, k::SmoothNode<double> nd, PingPong pp)
 {
     Context &c = ctx();
     hipStream_t s = c.stream;
@@ -320,7 +342,7 @@ void smooth_pp(double L, k::SmoothNode<double> nd)
     int launches = (step + smax - 1) / smax;
     if (launches % 2 == 0 && step > launches) launches += 1;
     const bool needs_copy = (launches % 2 == 0);  // only smax == 1 with an even step
-    double *partner = const_cast<double *>(nd.in);
+    double *partner = pp == INPUT_IS_PARTNER ? const_cast<double *>(nd.in) : nullptr;
     bool own_partner = false;
     if ((launches > 1 && !partner) || needs_copy) {
         partner = (double *)scratch_pool().get(n * sizeof(double));
@@ -418,7 +440,7 @@ void smooth_restrict_no_out(int N, double L, double *U_unused, double *F, int st
         fail(MG_ERR_UNSUPPORTED, "smooth_restrict_no_out: N=%d M=%d step=%d is not a fused `-1` node", N, M, step);
         return;
     }
-    smooth_pp(L, {.N = N, .F = F, .out = U_unused, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt, .no_out = true});
+    smooth_pp(L, {.N = N, .F = F, .out = U_unused, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt, .no_out = true}, KEEP_INPUT);
 }
 
 void prolong_smooth_recompute(int Nc, const double *U_c, int N, double L, double *U_out, double *F, int pre, int step, double *error_dev)
@@ -428,7 +450,7 @@ void prolong_smooth_recompute(int Nc, const double *U_c, int N, double L, double
         return;
     }
     smooth_pp(L, {.N = N, .F = F, .out = U_out, .steps = step, .err = error_dev, .d_sign = +1, .coarse = U_c, .Nc = Nc,
-                  .pt = &prolong_table(Nc, N), .pre = pre});
+                  .pt = &prolong_table(Nc, N), .pre = pre}, KEEP_INPUT);
 }
 
 // One launch for n recorded instances of the same fused node (the independent visits of a level, mg_cycle.cpp); the
@@ -858,7 +880,7 @@ void mg_smooth_pp(int N, double L, const double *U_in, double *U_out, double *F,
         fail(MG_ERR_ARG, "mg_smooth_pp: U_out must differ from U_in");
         return;
     }
-    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D_out, .d_sign = d_sign < 0 ? -1 : +1});
+    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D_out, .d_sign = d_sign < 0 ? -1 : +1}, INPUT_IS_PARTNER);
 }
 
 // pre-smoothing + getResidual + sign flip + doRestriction of one "-1" node
@@ -877,14 +899,14 @@ void mg_smooth_restrict(int N, double L, const double *U_in, double *U_out, doub
     const RestrictTable &rt = restrict_table(N, M);
     if (!rt.lo) return;
     if (step > 0 && c.smoother != SMOOTHER_SIMPLE && k::stream_fusable(N) && rt.fusable) {
-        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt});
+        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .Fc = F_c, .M = M, .rt = &rt}, KEEP_INPUT);
         return;
     }
     // operator by operator, D in pool scratch
     const size_t n = (size_t)N * N;
     double *D = (double *)scratch_pool().get(n * sizeof(double));
     if (!D) return;
-    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D});
+    smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .D = D}, KEEP_INPUT);
     {
         ProfScope ps("restrict", N, 8.0 * N * N + 8.0 * M * M);
         k::restrict_gather(c.stream, N, D, M, F_c, rt, +1);
@@ -908,7 +930,7 @@ void mg_prolong_smooth(int Nc, const double *U_c, int N, double L, const double 
     const ProlongTable &pt = prolong_table(Nc, N);
     if (!pt.owner_row) return;
     if (step > 0 && c.smoother != SMOOTHER_SIMPLE && k::stream_fusable(N) && pt.fusable) {
-        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .d_sign = +1, .coarse = U_c, .Nc = Nc, .pt = &pt});
+        smooth_pp(L, {.N = N, .in = U_in, .F = F, .out = U_out, .steps = step, .err = error_dev, .d_sign = +1, .coarse = U_c, .Nc = Nc, .pt = &pt}, KEEP_INPUT);
         return;
     }
     {
@@ -916,11 +938,11 @@ void mg_prolong_smooth(int Nc, const double *U_c, int N, double L, const double 
         k::prolong(c.stream, Nc, U_c, N, U_in, U_out, pt);
     }
     if (step > 0) {
-        // U_out now holds U + P; sweep it through U_in (clobbered) and back
+        // U_out now holds U + P; sweep it into scratch and copy back (U_in is only read)
         const size_t n = (size_t)N * N;
         double *tmp = (double *)scratch_pool().get(n * sizeof(double));
         if (!tmp) return;
-        smooth_pp(L, {.N = N, .in = U_out, .F = F, .out = tmp, .steps = step, .err = error_dev, .d_sign = +1});
+        smooth_pp(L, {.N = N, .in = U_out, .F = F, .out = tmp, .steps = step, .err = error_dev, .d_sign = +1}, INPUT_IS_PARTNER);
         MG_HIP(hipMemcpyAsync(U_out, tmp, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
         scratch_pool().put(tmp);
     }
@@ -1130,7 +1152,7 @@ void mg_doSmoothing(int N, double L, double *U, double *F, int step, double *err
             c.defer_norms = deferred;
             return;
         }
-        smooth_pp(L, {.N = N, .in = U, .F = F, .out = tmp, .steps = step, .err = error ? slot : nullptr, .d_sign = +1});
+        smooth_pp(L, {.N = N, .in = U, .F = F, .out = tmp, .steps = step, .err = error ? slot : nullptr, .d_sign = +1}, INPUT_IS_PARTNER);
         MG_HIP(hipMemcpyAsync(U, tmp, n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
         scratch_pool().put(tmp);  // stream-ordered reuse: later users enqueue behind the copy
     } else if (error) {

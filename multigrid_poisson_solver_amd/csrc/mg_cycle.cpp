@@ -1082,6 +1082,7 @@ mg_cycle_plan *mg_cycle_load(const char *path, int flags)
         return nullptr;
     }
     mg_cycle_plan *p = new mg_cycle_plan;
+    p->pool.poison(pool_poison_wanted());   // MG_POOL_POISON: every array the plan's pool hands out starts as NaN
     p->flags = flags;
     p->path = path;
     if (!(f >> p->L >> p->min_x >> p->min_y >> p->con_step >> p->con_N >> p->N_max >> p->N_min)) {

@@ -86,13 +86,22 @@ public:
     // release_parked() -- called when the schedule is dropped.
     void park(bool on) { park_ = on; }
     void release_parked();
+    // MG_POOL_POISON (tests): every block handed out -- fresh or recycled -- is filled with all-ones bytes (a NaN in fp64
+    // and in fp32) on the engine's stream first, so that a consumed read of memory nobody wrote shows in the result.
+    // Not while that stream is being captured: the fill must not become part of a graph.
+    void poison(bool on) { poison_ = on; }
 private:
     std::multimap<size_t, void *> free_;   // size -> block
     std::map<void *, size_t> live_;        // block -> size
     std::vector<std::pair<size_t, void *>> parked_;
     bool park_ = false;
+    bool poison_ = false;
     size_t held_ = 0;
 };
+// env MG_POOL_POISON is set (and not "0"): read when a cycle plan or a solver is created
+bool pool_poison_wanted();
+// all-ones bytes over a device block, enqueued on the engine's stream (skipped while that stream is being captured)
+void poison_block(void *p, size_t bytes);
 
 // STREAM_ONLY: the streaming kernel also for a bare single sweep of a large grid (which STREAM hands to the
 // one-row-per-block pair kernel): lets the bench report the S = 1 streaming kernel's own rate

@@ -269,6 +269,8 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
         const size_t n = (size_t)s->sizes[l] * s->sizes[l];
         ok = dev_alloc(&s->B[l], n);
         if (ok && l > 0) ok = dev_alloc(&s->A[l], n) && dev_alloc(&s->F[l], n);
+        if (ok && pool_poison_wanted())   // MG_POOL_POISON: no level array starts from what hipMalloc happened to return
+            for (double *a : {s->A[l], s->B[l], s->F[l]}) poison_block(a, n * sizeof(double));
     }
     for (int l = 0; l + 1 < nl && ok; ++l) {   // the transfer tables, built once here
         const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
@@ -279,6 +281,8 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
          MG_HIP(hipHostMalloc((void **)&s->host_state, 4 * sizeof(int), hipHostMallocDefault)) &&
          MG_HIP(hipEventCreate(&s->ev_begin)) && MG_HIP(hipEventCreate(&s->ev_end)) &&
          MG_HIP(hipEventCreateWithFlags(&s->ev_norm, hipEventDisableTiming));
+    if (ok && pool_poison_wanted()) poison_block(s->part, k::resnorm_partials(N) * sizeof(double));
+    ok = ok && MG_HIP(hipStreamSynchronize(ctx().stream));   // (the fills ran on the engine's stream; a solve may run on another)
     ok = ok && MG_HIP(hipMemset(s->dev_scal, 0, 4 * sizeof(double))) && MG_HIP(hipMemset(s->gs_state, 0, 4 * sizeof(int)));
     if (!ok) {
         release(s);

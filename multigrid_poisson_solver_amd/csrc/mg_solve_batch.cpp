@@ -261,6 +261,8 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
         const size_t bytes = s->pitch[l] * max_batch * sizeof(double);
         ok = MG_HIP(hipMalloc((void **)&s->B[l], bytes));
         if (ok && l > 0) ok = MG_HIP(hipMalloc((void **)&s->A[l], bytes)) && MG_HIP(hipMalloc((void **)&s->F[l], bytes));
+        if (ok && pool_poison_wanted())   // MG_POOL_POISON: no level array starts from what hipMalloc happened to return
+            for (double *a : {s->A[l], s->B[l], s->F[l]}) poison_block(a, bytes);
     }
     for (int l = 0; l + 1 < nl && ok; ++l) {
         const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
@@ -275,6 +277,8 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
          MG_HIP(hipHostMalloc((void **)&s->host_tab, tab_bytes, hipHostMallocDefault)) &&
          MG_HIP(hipEventCreate(&s->ev_begin)) && MG_HIP(hipEventCreate(&s->ev_end)) &&
          MG_HIP(hipEventCreateWithFlags(&s->ev_sync, hipEventDisableTiming));
+    if (ok && pool_poison_wanted()) poison_block(s->part, k::resnorm_partials(N) * max_batch * sizeof(double));
+    ok = ok && MG_HIP(hipStreamSynchronize(ctx().stream));   // (the fills ran on the engine's stream; a solve may run on another)
     ok = ok && MG_HIP(hipMemset(s->dev_rb, 0, rb_bytes(max_batch)));
     if (!ok) {
         release(s);
