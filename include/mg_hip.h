@@ -350,7 +350,18 @@ void mg_slab_destroy(mg_slab_plan *plan);
  * coarse_atol = tol is the reference's exact solve).  Residual, restriction, prolongation, addition and the sign flip
  * are the reference operators.  U (in/out): initial guess whose rim carries the Dirichlet values; the rim of F is
  * ignored.  On N = 2^k and 2^k + 1 hierarchies the rim comes back bit-identical; on other sizes the reference's
- * prolongation may move rim points by rounding (about 1e-14 seen). */
+ * prolongation may move rim points by rounding (about 1e-14 seen).
+ * shift (sigma >= 0, finite) makes it the screened equation  Laplace(U) - sigma*U = F  on every level (coarse levels are
+ * rediscretised with the same sigma): the equation of an implicit time step, sigma = 1/(nu*dt), F = -u_old/(nu*dt).
+ * Per level of size N_l the host forms in fp64, each operation rounded once, dx2 = (L/(N_l-1))^2, inv = 1/dx2,
+ * d = 4 + shift*dx2, q = 1/d, c = omega*q (4, 0.25, 0.25*omega at shift = 0).  Bracket b(U) = (((U[r+1] + U[r-1]) +
+ * U[c+1]) + U[c-1]) - d*U with the product rounded before the subtraction; sweep U <- U + c*(b(U) - dx2*F); residual (the
+ * restricted quantity and the stopping norm) inv*b(U) - F; coarse update q*(left + right + down + up - dx2*F) with error
+ * metric sum|inv*b(U) - F| / (N-2)^2.  The transfer operators, the tolerances and the results keep their definitions.
+ * shift = 0 is the Poisson solve above bit for bit, through the same kernels; a negative shift (the indefinite Helmholtz
+ * problem) is refused with MG_ERR_ARG.
+ * ABI: `shift` was appended to mg_solve_opts in version 0.2; a caller compiled against the 0.1 header passes a shorter
+ * struct and must be recompiled (mg_version() tells the two apart). */
 typedef struct mg_solve_opts {
     int    pre, post;          /* sweeps per level on the way down / up, 1..4 */
     int    N_min;              /* coarsest size bound, 3..32 */
@@ -359,6 +370,7 @@ typedef struct mg_solve_opts {
     int    coarse_max_iters;   /* >= 1; reaching it is reported (coarse_capped), not fatal */
     double rtol, atol;         /* stopping rule on the L2 residual */
     int    max_cycles;         /* >= 0 */
+    double shift;              /* sigma of Laplace(U) - sigma*U = F, finite and >= 0; 0: the Poisson equation (LAST field) */
 } mg_solve_opts;
 
 #define MG_SOLVE_CONVERGED      0
@@ -377,7 +389,8 @@ typedef struct mg_solve_result {
 
 typedef struct mg_solver mg_solver;
 
-/* V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, coarse_atol 0, coarse_max_iters 10000, rtol 1e-10, atol 0, 50 cycles.
+/* V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, coarse_atol 0, coarse_max_iters 10000, rtol 1e-10, atol 0, 50 cycles,
+ * shift 0.
  * rtol is relative to ||F||: on large grids the fp64 rounding of inv*(star - 4U) (inv = 1/dx^2) puts a floor under the
  * reachable residual -- about 8e-10 relative at N = 8192 on the getSource problem -- so a default solve there runs all
  * max_cycles and returns MG_SOLVE_NOT_CONVERGED; ask for rtol >= 1e-9 at that size. */

@@ -48,7 +48,7 @@ _dptr = C.POINTER(C.c_double)
 class SolveOpts(C.Structure):
     _fields_ = [("pre", C.c_int), ("post", C.c_int), ("N_min", C.c_int), ("omega", C.c_double), ("coarse_rtol", C.c_double),
                 ("coarse_atol", C.c_double), ("coarse_max_iters", C.c_int), ("rtol", C.c_double), ("atol", C.c_double),
-                ("max_cycles", C.c_int)]
+                ("max_cycles", C.c_int), ("shift", C.c_double)]
 
 
 class SolveResult(C.Structure):
@@ -778,7 +778,10 @@ def solve_opts(**opts):
     """mg_solve_opts: the library's defaults (V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, rtol 1e-10, 50 cycles) with
     the named fields replaced.  rtol is relative to ||F||; large grids have an fp64 rounding floor above 1e-10 (about
     8e-10 at N = 8192 on the getSource problem): there a default solve runs all max_cycles and reports not converged,
-    so pass rtol=1e-9 or more at that size."""
+    so pass rtol=1e-9 or more at that size.
+    shift (sigma, default 0, finite and >= 0) solves the screened equation  Laplace(U) - sigma*U = F  on every level
+    instead (include/mg_hip.h gives the per-level constants); 0 is the Poisson solve bit for bit.  An implicit time step
+    of u_t = nu*Laplace(u) is one such solve with sigma = 1/(nu*dt) and F = -u_old/(nu*dt)."""
     o = SolveOpts()
     lib().mg_solve_opts_default(C.byref(o))
     names = {f for f, _ in SolveOpts._fields_}
@@ -792,7 +795,8 @@ def solve_opts(**opts):
 class Solver:
     """Residual-tolerance solver of include/mg_hip.h: V(pre, post) cycles with a weighted Jacobi smoother and a
     relative coarse target, on a caller's F and Dirichlet rim, until ||F - AU||_2 <= max(rtol*||F||_2, atol).  Every
-    level array is allocated here; solve() allocates nothing on the device."""
+    level array is allocated here; solve() allocates nothing on the device.  With shift=sigma > 0 the operator is
+    A U = Laplace(U) - sigma*U (solve_opts); an implicit time step has sigma = 1/(nu*dt), F = -u_old/(nu*dt)."""
 
     def __init__(self, N, L=1.0, **opts):
         self.N, self.L = int(N), float(L)
@@ -873,7 +877,8 @@ def _is_torch(a):
 def solve(F, U=None, L=1.0, **opts):
     """Solve the Poisson problem A U = F on the N x N grid of F (Dirichlet values on U's rim) to the residual
     tolerance; returns (U, info).  See Solver, and solve_opts for the defaults (the default rtol of 1e-10 is below the
-    rounding floor of large grids: about 8e-10 at N = 8192)."""
+    rounding floor of large grids: about 8e-10 at N = 8192).  shift=sigma > 0 solves Laplace(U) - sigma*U = F, the
+    equation of an implicit time step: sigma = 1/(nu*dt), F = -u_old/(nu*dt)."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:
@@ -897,7 +902,9 @@ class BatchSolver:
     """Batched residual-tolerance solver of include/mg_hip.h: up to max_batch problems of size N with one set of options
     (see solve_opts) in one call, every instance bit-identical to a Solver solve of it alone (U, history, cycles, status).
     An instance stops once it meets its own tolerance; one cycle is one launch per node over all active instances.
-    Every level array for max_batch instances is allocated here; solve() allocates nothing on the device."""
+    Every level array for max_batch instances is allocated here; solve() allocates nothing on the device.  shift=sigma
+    (one value for the whole batch) solves Laplace(U) - sigma*U = F: the many same-size solves of implicit time stepping,
+    sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt)."""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -1042,7 +1049,8 @@ class BatchSolver:
 def solve_batched(F, U=None, L=1.0, **opts):
     """Solve B Poisson problems of one size to the residual tolerance in one batched call; returns (U, infos).  F: [B, N, N]
     (or a list, or one (N, N) F shared by every instance when U gives B), U: the initial guesses with their Dirichlet rims
-    (None: zero).  See BatchSolver for the accepted types and solve_opts for the defaults."""
+    (None: zero).  See BatchSolver for the accepted types and solve_opts for the defaults.  shift=sigma solves
+    Laplace(U) - sigma*U = F for every instance: one implicit time step of B fields, sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt)."""
     Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
     if U is None:
         B = 1 if shared else len(Fs)

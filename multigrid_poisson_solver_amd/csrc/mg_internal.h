@@ -264,6 +264,17 @@ struct SmoothNode {
     // != 0.25: the weighted sweep U + (cw*t) of the residual-tolerance solver (cw = 0.25*omega; jacobi_stream, no recomputing
     // pair); 0.25 is the reference's sweep
     double cw = 0.25;
+    // shifted: the screened operator of the residual-tolerance solver (mg_solve_opts.shift != 0): the centre coefficient of
+    // the bracket is dc = 4 + shift*dx2 (product rounded, then subtracted) in the sweeps and in the residual stage, and cw
+    // is omega/dc; always a weighted instantiation
+    double dc = 4.0;
+    bool shifted = false;
+};
+// centre coefficient d = 4 + shift*dx2 and q = 1/d of one level of the screened operator (mg_solve.cpp: LevelConsts) for
+// the solver's operator-by-operator kernels; on = false (shift == 0): the unshifted kernels, d and q are not looked at
+struct Shifted {
+    bool on = false;
+    double d = 4.0, q = 0.25;
 };
 }  // namespace k
 
@@ -285,7 +296,8 @@ namespace k {
 // one Jacobi sweep in correction form, in -> out (in == nullptr: all zero)
 void jacobi_simple(hipStream_t s, int N, double dx2, const double *in, const double *F, double *out);
 // D = sign * (inv*(star - 4U) - F), rim sign*0
-void residual(hipStream_t s, int N, double inv, const double *U, const double *F, double *D, int sign);
+// (sh.on: the bracket's centre term is sh.d*U, the residual-tolerance solver's screened operator)
+void residual(hipStream_t s, int N, double inv, const double *U, const double *F, double *D, int sign, const Shifted &sh = {});
 // doSmoothing's error: *out = (S+S)/N/N, S = sum over (row+col) even interior of |inv*star-F|
 void smoothing_error(hipStream_t s, int N, double inv, const double *U, const double *F, double *out);
 // second stage of doSmoothing's error: *out = (sum+sum)/N/N over n per-block partials
@@ -380,26 +392,29 @@ void gauss_seidel_blocks_launch(hipStream_t s, int N, double h2, double inv, dou
 int  gs_single_workgroup_max_n();
 // residual-tolerance solver (mg_solve_kernels.hip, driven by mg_solve.cpp)
 // one weighted Jacobi sweep U = U_old + cw*(star - 4 U_old - dx^2 F), cw = 0.25*omega, rim kept (in == nullptr: all zero)
-void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out);
+// sh.on: the bracket's centre term is sh.d*U_old (rounded, then subtracted) and cw = omega*sh.q
+void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out, const Shifted &sh = {});
 // *out = sqrt(sum over interior points of d^2), d = inv*(star - 4U) - F (U == nullptr: d = F); part holds at least
 // resnorm_partials(N) doubles; the partials are summed in a fixed order (bit-reproducible)
 size_t resnorm_partials(int N);
-void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out);
+void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out, const Shifted &sh = {});
 // red-black Gauss-Seidel from zero to err <= max(atol, rtol*err0) (err0: the metric at U = 0), 1 ... max_iters iterations,
 // one workgroup; state[1] = iterations, state[2] = 1 when the cap ended it above the target; err_out[0..1] = err0, err
 constexpr int GS_RELATIVE_MAX_N = 64;
 bool gs_relative_fits(int N);
+// sh.on: update sh.q*(... - h^2 F), error metric with the centre term sh.d*U
 void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double atol, double rtol,
-                           int max_iters, int *state, double *err_out);
+                           int max_iters, int *state, double *err_out, const Shifted &sh = {});
 // the same kernels on n instances of one size in ONE launch each (batched solver, mg_solve_batch.cpp): items[i] (device
 // memory) holds instance i's arrays, each instance runs exactly the code and the partition of its single-instance form.
 // resnorm_batch: in = U (has_u), F; out[i] = its norm, its partials at part + i*resnorm_partials(N)
-void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out);
+void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out,
+                   const Shifted &sh = {});
 // out = U, F; instance i's state at state + 4i (no err_out)
 void gauss_seidel_relative_batch(hipStream_t s, int n, int N, double h2, double inv, const NodeBatchItem *items, double atol,
-                                 double rtol, int max_iters, int *state);
+                                 double rtol, int max_iters, int *state, const Shifted &sh = {});
 // residual (in = U, F, out = D), restriction N -> M (in -> out), out = in + prolongation of coarse (N -> M), copy in -> out
-void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign);
+void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign, const Shifted &sh = {});
 void restrict_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const RestrictTable &t, int sign);
 void prolong_add_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const ProlongTable &t);
 void copy_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items);
@@ -407,11 +422,19 @@ void copy_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items);
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
 bool solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o);
+// the constants of one level, formed once at creation in fp64, each operation rounded once and in this order (include/mg_hip.h):
+// dx2 = (L/(N-1))^2, inv = 1/dx2, d = 4 + shift*dx2, q = 1/d, c = omega*q -- 4, 0.25 and 0.25*omega exactly at shift = 0
+struct LevelConsts {
+    double dx2, inv, d, q, c;
+    k::Shifted sh;   // {shift != 0, d, q}
+};
+std::vector<LevelConsts> solve_level_consts(const std::vector<int> &sizes, double L, const mg_solve_opts &o);
 // the arrays of one instance's hierarchy (level 0: the caller's F and U, only B[0] is used)
 struct SolveLevels {
     const std::vector<int> *sizes;
     double L;
     const mg_solve_opts *o;
+    const std::vector<LevelConsts> *lc;
     std::vector<double *> A, B, F;
     int *gs_state;
     double *gs_err;   // may be nullptr

@@ -159,8 +159,12 @@ __global__ __launch_bounds__(TB) void k_jacobi_pair_rows(int N, double dx2, cons
 
 // ---------------------------------------------------------------- residual
 // src/MG_solver_CPU.cpp:554-564 (and the driver's sign flip :277-280 when sign < 0)
-__global__ __launch_bounds__(TB) void k_residual(int N, double inv, const double *__restrict__ U,
-                                                 const double *__restrict__ F, double *__restrict__ D, int sign)
+// (SH: the screened operator of the residual-tolerance solver, mg_solve_opts.shift != 0: the centre term is dc*U, rounded
+// and then subtracted; SH = false is the reference's expression, dc is not looked at.  The shifted forms are kernels of
+// their own, `_sh`: an unshifted run launches what it always launched)
+template <bool SH>
+__device__ __forceinline__ void residual_body(int N, double inv, const double *__restrict__ U, const double *__restrict__ F,
+                                              double *__restrict__ D, int sign, double dc)
 {
     const int c = blockIdx.x * TB + threadIdx.x;
     if (c >= N) return;
@@ -171,15 +175,31 @@ __global__ __launch_bounds__(TB) void k_residual(int N, double inv, const double
         if (r >= N) return;
         const size_t p = (size_t)r * N + c;
         double v = 0.0;
-        if (!rim(r, c, N)) v = inv * star_minus4(U, p, N) - F[p];
+        if (!rim(r, c, N)) {
+            if constexpr (SH) v = inv * (U[p + N] + U[p - N] + U[p + 1] + U[p - 1] - dc * U[p]) - F[p];
+            else v = inv * star_minus4(U, p, N) - F[p];
+        }
         D[p] = sign < 0 ? -v : v;
     }
 }
 
+__global__ __launch_bounds__(TB) void k_residual(int N, double inv, const double *__restrict__ U,
+                                                 const double *__restrict__ F, double *__restrict__ D, int sign)
+{
+    residual_body<false>(N, inv, U, F, D, sign, 4.0);
+}
+
+__global__ __launch_bounds__(TB) void k_residual_sh(int N, double inv, double dc, const double *__restrict__ U,
+                                                    const double *__restrict__ F, double *__restrict__ D, int sign)
+{
+    residual_body<true>(N, inv, U, F, D, sign, dc);
+}
+
 // getResidual on large even grids: 16 B per lane, PR rows per thread with a rolling window of three row pairs (every row of U
 // read once), F and D through non-temporal accesses -- the shape of k_jacobi_pair_rows.  Same expression (star_minus4's order).
-__global__ __launch_bounds__(TB) void k_residual_pairs(int N, double inv, const double *__restrict__ U,
-                                                       const double *__restrict__ F, double *__restrict__ D, int sign)
+template <bool SH>
+__device__ __forceinline__ void residual_pairs_body(int N, double inv, const double *__restrict__ U, const double *__restrict__ F,
+                                                    double *__restrict__ D, int sign, double dc)
 {
     const int c = 2 * (blockIdx.x * TB + threadIdx.x);
     const int r0 = blockIdx.y * PR;
@@ -200,14 +220,26 @@ __global__ __launch_bounds__(TB) void k_residual_pairs(int N, double inv, const 
         if (r > 0 && r < N - 1) {
             const double left = U[(size_t)r * N + cl], right = U[(size_t)r * N + cr];
             const double2_k f = __builtin_nontemporal_load(reinterpret_cast<const double2_k *>(F + p));
-            if (c > 0) v.x = inv * (down.x + up.x + mid.y + left - 4 * mid.x) - f.x;
-            if (c + 1 < N - 1) v.y = inv * (down.y + up.y + right + mid.x - 4 * mid.y) - f.y;
+            if (c > 0) v.x = inv * (down.x + up.x + mid.y + left - (SH ? dc * mid.x : 4 * mid.x)) - f.x;
+            if (c + 1 < N - 1) v.y = inv * (down.y + up.y + right + mid.x - (SH ? dc * mid.y : 4 * mid.y)) - f.y;
         }
         if (sign < 0) v = -v;
         __builtin_nontemporal_store(v, reinterpret_cast<double2_k *>(D + p));
         up = mid;
         mid = down;
     }
+}
+
+__global__ __launch_bounds__(TB) void k_residual_pairs(int N, double inv, const double *__restrict__ U,
+                                                       const double *__restrict__ F, double *__restrict__ D, int sign)
+{
+    residual_pairs_body<false>(N, inv, U, F, D, sign, 4.0);
+}
+
+__global__ __launch_bounds__(TB) void k_residual_pairs_sh(int N, double inv, double dc, const double *__restrict__ U,
+                                                          const double *__restrict__ F, double *__restrict__ D, int sign)
+{
+    residual_pairs_body<true>(N, inv, U, F, D, sign, dc);
 }
 
 // ---------------------------------------------------------------- smoothing error
@@ -849,8 +881,14 @@ void jacobi_simple(hipStream_t s, int N, double dx2, const double *in, const dou
     else hipLaunchKernelGGL(k_jacobi_simple<true>, g, dim3(TB), 0, s, N, dx2, in, F, out);
 }
 
-void residual(hipStream_t s, int N, double inv, const double *U, const double *F, double *D, int sign)
+void residual(hipStream_t s, int N, double inv, const double *U, const double *F, double *D, int sign, const Shifted &sh)
 {
+    if (sh.on) {
+        if (N % 2 == 0 && N >= big_grid_min())
+            hipLaunchKernelGGL(k_residual_pairs_sh, dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR), dim3(TB), 0, s, N, inv, sh.d, U, F, D, sign);
+        else hipLaunchKernelGGL(k_residual_sh, grid_rows(N, ROWS_PB), dim3(TB), 0, s, N, inv, sh.d, U, F, D, sign);
+        return;
+    }
     if (N % 2 == 0 && N >= big_grid_min()) {
         hipLaunchKernelGGL(k_residual_pairs, dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR), dim3(TB), 0, s, N, inv, U, F, D, sign);
         return;

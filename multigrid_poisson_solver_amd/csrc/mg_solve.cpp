@@ -16,6 +16,7 @@ struct mg_solver {
     double L = 1.0;
     mg_solve_opts o{};
     std::vector<int> sizes;                  // N, N/2, ... >= N_min
+    std::vector<LevelConsts> lc;             // per level: spacing, centre coefficient, weight
     std::vector<double *> A, B, F;           // per level (level 0: only B, the scratch field beside the caller's U)
     double *part = nullptr;                  // norm partials
     double *dev_scal = nullptr;              // [4]: residual norm, reference norm, coarse err0, coarse err
@@ -55,6 +56,8 @@ bool opts_ok(const char *who, int N, double L, const mg_solve_opts &o)
         return false;
     }
     if (o.max_cycles < 0) { fail(MG_ERR_ARG, "%s: max_cycles = %d < 0", who, o.max_cycles); return false; }
+    // (a negative shift is the indefinite Helmholtz problem: not what this smoother solves)
+    if (!(o.shift >= 0.0) || !finite(o.shift)) { fail(MG_ERR_ARG, "%s: shift = %g must be finite and >= 0", who, o.shift); return false; }
     return true;
 }
 
@@ -96,40 +99,41 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
     const std::vector<int> &sizes = *lv.sizes;
     const int nl = (int)sizes.size();
     int launches = 0;
-    const double cw = 0.25 * o.omega;
+    const std::vector<LevelConsts> &lc = *lv.lc;
     std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
     for (int l = 0; l + 1 < nl; ++l) {
         const int N = sizes[l], M = sizes[l + 1];
-        const double dx2 = spacing_sq(N, lv.L);
+        const double dx2 = lc[l].dx2, cw = lc[l].c;
+        const k::Shifted &sh = lc[l].sh;
         const double *F = l == 0 ? F0 : lv.F[l];
         double *cur = l == 0 ? U0 : lv.A[l], *other = lv.B[l];
         int sweeps = o.pre;
         if (l > 0) {   // memset(U, 0) (:256) folded into the first sweep
-            k::wjacobi(st, N, dx2, cw, nullptr, F, cur);
+            k::wjacobi(st, N, dx2, cw, nullptr, F, cur, sh);
             ++launches;
             --sweeps;
         }
         for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi(st, N, dx2, cw, cur, F, other);
+            k::wjacobi(st, N, dx2, cw, cur, F, other, sh);
             ++launches;
             std::swap(cur, other);
         }
         // D = -getResidual(U) (:268, :277-280) into the free field, F_c = doRestriction(D) (:287)
-        k::residual(st, N, 1.0 / dx2, cur, F, other, -1);
+        k::residual(st, N, lc[l].inv, cur, F, other, -1, sh);
         k::restrict_gather(st, N, other, M, lv.F[l + 1], restrict_table(N, M), +1);
         launches += 2;
         x[l] = cur;
         y[l] = other;
     }
     const int Nc = sizes[nl - 1];
-    const double h2 = spacing_sq(Nc, lv.L);
-    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, lv.A[nl - 1], lv.F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
-                             lv.gs_state, lv.gs_err);
+    k::gauss_seidel_relative(st, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, lv.A[nl - 1], lv.F[nl - 1], o.coarse_atol, o.coarse_rtol,
+                             o.coarse_max_iters, lv.gs_state, lv.gs_err, lc[nl - 1].sh);
     ++launches;
     x[nl - 1] = lv.A[nl - 1];
     for (int l = nl - 2; l >= 0; --l) {
         const int N = sizes[l], Nc_l = sizes[l + 1];
-        const double dx2 = spacing_sq(N, lv.L);
+        const double dx2 = lc[l].dx2, cw = lc[l].c;
+        const k::Shifted &sh = lc[l].sh;
         const double *F = l == 0 ? F0 : lv.F[l];
         double *cur = x[l], *other = y[l];
         // U = U + doProlongation(U_c) (:354, :368) into the free field
@@ -137,7 +141,7 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
         ++launches;
         std::swap(cur, other);
         for (int i = 0; i < o.post; ++i) {
-            k::wjacobi(st, N, dx2, cw, cur, F, other);
+            k::wjacobi(st, N, dx2, cw, cur, F, other, sh);
             ++launches;
             std::swap(cur, other);
         }
@@ -157,44 +161,47 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 {
     const mg_solve_opts &o = s->o;
     const int nl = (int)s->sizes.size();
-    const double cw = 0.25 * o.omega;
+    const std::vector<LevelConsts> &lc = s->lc;
     std::vector<double *> x(nl);   // per level: the field holding the pre-smoothed iterate, then the result
     for (int l = 0; l + 1 < nl; ++l) {
         const int N = s->sizes[l], M = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
+        const bool shifted = lc[l].sh.on;
         const double *F = l == 0 ? F0 : s->F[l];
         const double *in = l == 0 ? U0 : nullptr;   // coarser levels: memset(U, 0) (:256) folded into the first sweep
         double *out = l == 0 ? s->B[0] : s->A[l], *scratch = l == 0 ? U0 : s->B[l];
         const RestrictTable &rt = restrict_table(N, M);
         if (k::stream_fusable(N) && rt.fusable) {
             k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .Fc = s->F[l + 1], .M = M,
-                                  .rt = &rt, .cw = cw});
+                                  .rt = &rt, .cw = cw, .dc = dc, .shifted = shifted});
         } else {
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .cw = cw});
-            k::residual(st, N, inv, out, F, scratch, -1);
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .cw = cw, .dc = dc,
+                                  .shifted = shifted});
+            k::residual(st, N, inv, out, F, scratch, -1, lc[l].sh);
             k::restrict_gather(st, N, scratch, M, s->F[l + 1], rt, +1);
         }
         x[l] = out;
     }
     const int Nc = s->sizes[nl - 1];
-    const double h2 = spacing_sq(Nc, s->L);
-    k::gauss_seidel_relative(st, Nc, h2, 1.0 / h2, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
-                             s->gs_state, s->dev_scal + 2);
+    k::gauss_seidel_relative(st, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol,
+                             o.coarse_max_iters, s->gs_state, s->dev_scal + 2, lc[nl - 1].sh);
     x[nl - 1] = s->A[nl - 1];
     for (int l = nl - 2; l >= 0; --l) {
         const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
+        const bool shifted = lc[l].sh.on;
         const double *F = l == 0 ? F0 : s->F[l];
         double *in = x[l], *out = l == 0 ? U0 : s->B[l];
         const ProlongTable &pt = prolong_table(Nc_l, N);
         if (k::stream_fusable(N) && pt.fusable) {
             k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.post, .d_sign = +1,
-                                  .coarse = x[l + 1], .Nc = Nc_l, .pt = &pt, .cw = cw});
+                                  .coarse = x[l + 1], .Nc = Nc_l, .pt = &pt, .cw = cw, .dc = dc, .shifted = shifted});
             x[l] = out;
         } else {
             // U + doProlongation(U_c) (:354, :368) into `out`, the sweeps back into `in`
             k::prolong(st, Nc_l, x[l + 1], N, in, out, pt);
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = out, .F = F, .out = in, .steps = o.post, .d_sign = +1, .cw = cw});
+            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = out, .F = F, .out = in, .steps = o.post, .d_sign = +1, .cw = cw,
+                                  .dc = dc, .shifted = shifted});
             x[l] = in;
         }
     }
@@ -204,14 +211,14 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 {
     if (ctx().smoother == SMOOTHER_SIMPLE)
-        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0);
+        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0);
     else vcycle_fused(s, st, F0, U0);
 }
 
 // enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
-    k::resnorm(st, s->N, 1.0 / spacing_sq(s->N, s->L), U0, F0, s->part, s->dev_scal + slot);
+    k::resnorm(st, s->N, s->lc[0].inv, U0, F0, s->part, s->dev_scal + slot, s->lc[0].sh);
 }
 
 bool read_back(mg_solver *s, hipStream_t st)
@@ -225,6 +232,23 @@ bool read_back(mg_solver *s, hipStream_t st)
 }  // namespace
 
 bool mg::solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o) { return opts_ok(who, N, L, o); }
+
+std::vector<LevelConsts> mg::solve_level_consts(const std::vector<int> &sizes, double L, const mg_solve_opts &o)
+{
+    std::vector<LevelConsts> lc;
+    for (int N : sizes) {
+        LevelConsts c;
+        c.dx2 = spacing_sq(N, L);
+        c.inv = 1.0 / c.dx2;
+        const double sd = o.shift * c.dx2;
+        c.d = 4.0 + sd;
+        c.q = 1.0 / c.d;
+        c.c = o.omega * c.q;
+        c.sh = k::Shifted{o.shift != 0.0, c.d, c.q};
+        lc.push_back(c);
+    }
+    return lc;
+}
 
 extern "C" {
 
@@ -241,6 +265,7 @@ void mg_solve_opts_default(mg_solve_opts *o)
     o->rtol = 1e-10;
     o->atol = 0.0;
     o->max_cycles = 50;
+    o->shift = 0.0;
 }
 
 mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
@@ -256,6 +281,7 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
     s->o = o;
     for (int n = N; n >= o.N_min; n /= 2) s->sizes.push_back(n);   // mg_cycle_load's halving sizes (con_N = 1)
     const int nl = (int)s->sizes.size();
+    s->lc = solve_level_consts(s->sizes, L, o);
     if (!k::gs_relative_fits(s->sizes[nl - 1])) {   // (N_min <= 32 keeps the coarsest level below 64)
         fail(MG_ERR_UNSUPPORTED, "mg_solver_create: coarsest level %d does not fit the coarse solver", s->sizes[nl - 1]);
         release(s);

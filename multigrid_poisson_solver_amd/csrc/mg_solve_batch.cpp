@@ -20,6 +20,7 @@ struct mg_batch_solver {
     int max_batch = 0;
     mg_solve_opts o{};
     std::vector<int> sizes;                  // N, N/2, ... >= N_min
+    std::vector<LevelConsts> lc;             // per level: spacing, centre coefficient, weight (mg_solver's)
     std::vector<size_t> pitch;               // doubles from one instance's level array to the next one's
     std::vector<double *> A, B, F;           // per level, max_batch instances each (level 0: only B)
     double *part = nullptr;                  // norm partials, resnorm_partials(N) per instance
@@ -31,12 +32,6 @@ struct mg_batch_solver {
 };
 
 namespace {
-
-double spacing_sq(int N, double L)
-{
-    const double dx = L / (double)(N - 1);
-    return dx * dx;
-}
 
 size_t rb_bytes(int mb) { return (size_t)mb * (2 * sizeof(double) + 4 * sizeof(int)); }
 double *rb_res(void *rb) { return static_cast<double *>(rb); }
@@ -124,19 +119,20 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
 {
     const mg_solve_opts &o = s->o;
     const int nl = (int)s->sizes.size(), mb = s->max_batch;
-    const double cw = 0.25 * o.omega;
+    const std::vector<LevelConsts> &lc = s->lc;
     const NodeBatchItem *h = s->host_tab, *d = s->dev_tab;   // (slot 0 of a host table: the shape of a node)
     auto node = [&](int t) { return NodeBatch{n, d + (size_t)t * mb, nullptr}; };
     int launches = 0;
     for (int l = 0; l + 1 < nl; ++l) {
         const int N = s->sizes[l], M = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c;
         const int t = t_down(l);
         const NodeBatchItem &it = h[(size_t)t * mb];
         const NodeBatch nb = node(t);
         const RestrictTable &rt = restrict_table(N, M);
         k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
-                                 .out = (double *)it.out, .steps = o.pre, .batch = &nb, .cw = cw};
+                                 .out = (double *)it.out, .steps = o.pre, .batch = &nb, .cw = cw, .dc = lc[l].d,
+                                 .shifted = lc[l].sh.on};
         if (down_fused(s, l)) {
             nd.Fc = (double *)it.Fc;
             nd.M = M;
@@ -145,26 +141,26 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
             launches += 1;
         } else {
             k::jacobi_stream(st, nd);
-            k::residual_batch(st, n, N, inv, d + (size_t)(t + 1) * mb, -1);
+            k::residual_batch(st, n, N, inv, d + (size_t)(t + 1) * mb, -1, lc[l].sh);
             k::restrict_batch(st, n, N, M, d + (size_t)(t + 2) * mb, rt, +1);
             launches += 3;
         }
     }
     const int Nc = s->sizes[nl - 1];
-    const double h2 = spacing_sq(Nc, s->L);
-    k::gauss_seidel_relative_batch(st, n, Nc, h2, 1.0 / h2, d + (size_t)t_gs(nl) * mb, o.coarse_atol, o.coarse_rtol,
-                                   o.coarse_max_iters, rb_state(s->dev_rb, mb));
+    k::gauss_seidel_relative_batch(st, n, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, d + (size_t)t_gs(nl) * mb, o.coarse_atol,
+                                   o.coarse_rtol, o.coarse_max_iters, rb_state(s->dev_rb, mb), lc[nl - 1].sh);
     launches += 1;
     bool copy = false;
     for (int l = nl - 2; l >= 0; --l) {
         const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
-        const double dx2 = spacing_sq(N, s->L), inv = 1.0 / dx2;
+        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c;
         const int t = t_up(nl, l);
         const NodeBatchItem &it = h[(size_t)t * mb];
         const NodeBatch nb = node(t);
         const ProlongTable &pt = prolong_table(Nc_l, N);
         k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
-                                 .out = (double *)it.out, .steps = o.post, .d_sign = +1, .batch = &nb, .cw = cw};
+                                 .out = (double *)it.out, .steps = o.post, .d_sign = +1, .batch = &nb, .cw = cw,
+                                 .dc = lc[l].d, .shifted = lc[l].sh.on};
         if (up_fused(s, l)) {
             nd.coarse = (const double *)it.coarse;
             nd.Nc = Nc_l;
@@ -193,7 +189,7 @@ int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int
     int launches = 0;
     for (size_t j = 0; j < act.size(); ++j) {
         const int i = act[j];
-        SolveLevels lv{&s->sizes, s->L, &s->o, {}, {}, {}, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr};
+        SolveLevels lv{&s->sizes, s->L, &s->o, &s->lc, {}, {}, {}, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr};
         for (int l = 0; l < nl; ++l) {
             lv.A.push_back(level(s, s->A, l, i));
             lv.B.push_back(level(s, s->B, l, i));
@@ -206,7 +202,7 @@ int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int
 
 int norms(mg_batch_solver *s, hipStream_t st, int n, bool has_u, double *out)
 {
-    k::resnorm_batch(st, n, s->N, 1.0 / spacing_sq(s->N, s->L), has_u, s->dev_tab, s->part, out);
+    k::resnorm_batch(st, n, s->N, s->lc[0].inv, has_u, s->dev_tab, s->part, out, s->lc[0].sh);
     return 2;
 }
 
@@ -245,6 +241,7 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
     s->o = o;
     for (int n = N; n >= o.N_min; n /= 2) s->sizes.push_back(n);   // mg_solver_create's hierarchy
     const int nl = (int)s->sizes.size();
+    s->lc = solve_level_consts(s->sizes, L, o);
     if (!k::gs_relative_fits(s->sizes[nl - 1])) {
         fail(MG_ERR_UNSUPPORTED, "mg_batch_solver_create: coarsest level %d does not fit the coarse solver", s->sizes[nl - 1]);
         release(s);

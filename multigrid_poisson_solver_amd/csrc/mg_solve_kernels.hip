@@ -58,6 +58,23 @@ __device__ __forceinline__ double star_minus4(const double *__restrict__ A, size
     return A[p + N] + A[p - N] + A[p + 1] + A[p - 1] - 4 * A[p];
 }
 
+// The screened operator (mg_solve_opts.shift != 0): the centre coefficient is d = 4 + shift*dx^2 instead of 4.  The
+// product d*U is rounded, then subtracted (-ffp-contract=off), in the same place of the same sum.  Every kernel below is
+// a shared __forceinline__ body with a template parameter SH: SH = false is the expression as it always was (d is not
+// looked at), SH = true lives in kernels of their own (`_sh`), so that an unshifted solve launches what it always launched.
+template <bool SH>
+__device__ __forceinline__ double centre(double u, double d)
+{
+    if constexpr (SH) return d * u;
+    else return 4 * u;
+}
+template <bool SH>
+__device__ __forceinline__ double star_minus(const double *__restrict__ A, size_t p, int N, double d)
+{
+    if constexpr (SH) return A[p + N] + A[p - N] + A[p + 1] + A[p - 1] - d * A[p];
+    else return star_minus4(A, p, N);
+}
+
 template <bool NT>
 __device__ __forceinline__ double2_s load_f(const double *p)
 {
@@ -68,9 +85,9 @@ __device__ __forceinline__ double2_s load_f(const double *p)
 // ---------------------------------------------------------------- weighted Jacobi, one sweep
 // U = U_old + c*t, t = star(U_old) - 4 U_old - dx^2 F, c = 0.25*omega (formed on the host).  At omega = 1 the product
 // with 0.25 is exact and this is doSmoothing's sweep bit for bit.  Rim points keep their value.
-template <bool ZERO_IN>
-__global__ __launch_bounds__(TB) void k_wjacobi(int N, double dx2, double cw, const double *__restrict__ in,
-                                                const double *__restrict__ F, double *__restrict__ out)
+template <bool ZERO_IN, bool SH>
+__device__ __forceinline__ void wjacobi_body(int N, double dx2, double cw, double d, const double *__restrict__ in,
+                                             const double *__restrict__ F, double *__restrict__ out)
 {
     const int c = blockIdx.x * TB + threadIdx.x;
     if (c >= N) return;
@@ -86,17 +103,31 @@ __global__ __launch_bounds__(TB) void k_wjacobi(int N, double dx2, double cw, co
             v = rim(r, c, N) ? 0.0 : 0.0 + cw * (0.0 - dx2 * F[p]);
         } else {
             v = in[p];
-            if (!rim(r, c, N)) v = v + cw * (star_minus4(in, p, N) - dx2 * F[p]);
+            if (!rim(r, c, N)) v = v + cw * (star_minus<SH>(in, p, N, d) - dx2 * F[p]);
         }
         out[p] = v;
     }
 }
 
+template <bool ZERO_IN>
+__global__ __launch_bounds__(TB) void k_wjacobi(int N, double dx2, double cw, const double *__restrict__ in,
+                                                const double *__restrict__ F, double *__restrict__ out)
+{
+    wjacobi_body<ZERO_IN, false>(N, dx2, cw, 4.0, in, F, out);
+}
+
+template <bool ZERO_IN>
+__global__ __launch_bounds__(TB) void k_wjacobi_sh(int N, double dx2, double cw, double d, const double *__restrict__ in,
+                                                   const double *__restrict__ F, double *__restrict__ out)
+{
+    wjacobi_body<ZERO_IN, true>(N, dx2, cw, d, in, F, out);
+}
+
 // the same sweep on even N >= PAIR_MIN_N with 16 B per lane and PR rows per thread (the shape of k_jacobi_pair_rows):
 // every row of `in` is read once, its outer neighbours are single doubles (L1 hits of the neighbouring lanes' pairs)
-template <bool NT>
-__global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double cw, const double *__restrict__ in,
-                                                      const double *__restrict__ F, double *__restrict__ out)
+template <bool NT, bool SH>
+__device__ __forceinline__ void wjacobi_pairs_body(int N, double dx2, double cw, double d, const double *__restrict__ in,
+                                                   const double *__restrict__ F, double *__restrict__ out)
 {
     const int c = 2 * (blockIdx.x * TB + threadIdx.x);
     const int r0 = blockIdx.y * PR;
@@ -117,11 +148,11 @@ __global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double 
             const double2_s f = load_f<NT>(F + p);
             if (c > 0) {
                 const double w = in[p - 1];
-                o.x = ctr.x + cw * (up.x + dn.x + ctr.y + w - 4 * ctr.x - dx2 * f.x);
+                o.x = ctr.x + cw * (up.x + dn.x + ctr.y + w - centre<SH>(ctr.x, d) - dx2 * f.x);
             }
             if (c + 1 < N - 1) {
                 const double e = in[p + 2];
-                o.y = ctr.y + cw * (up.y + dn.y + e + ctr.x - 4 * ctr.y - dx2 * f.y);
+                o.y = ctr.y + cw * (up.y + dn.y + e + ctr.x - centre<SH>(ctr.y, d) - dx2 * f.y);
             }
         }
         if (NT) __builtin_nontemporal_store(o, reinterpret_cast<double2_s *>(out + p));
@@ -131,13 +162,27 @@ __global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double 
     }
 }
 
+template <bool NT>
+__global__ __launch_bounds__(TB) void k_wjacobi_pairs(int N, double dx2, double cw, const double *__restrict__ in,
+                                                      const double *__restrict__ F, double *__restrict__ out)
+{
+    wjacobi_pairs_body<NT, false>(N, dx2, cw, 4.0, in, F, out);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(TB) void k_wjacobi_pairs_sh(int N, double dx2, double cw, double d, const double *__restrict__ in,
+                                                         const double *__restrict__ F, double *__restrict__ out)
+{
+    wjacobi_pairs_body<NT, true>(N, dx2, cw, d, in, F, out);
+}
+
 // ---------------------------------------------------------------- residual L2 norm
 // per-block partial sums of d^2 over interior points, d = inv*(star - 4U) - F (getResidual's value, :560);
 // HAS_U = false: U == 0, d = -F (the reference norm ||F||).  Nothing but the partials is written.
 // (the bodies are shared with the batched forms: the same partition into partials for every instance)
-template <bool HAS_U>
+template <bool HAS_U, bool SH = false>
 __device__ __forceinline__ void resnorm_body(int N, double inv, const double *__restrict__ U, const double *__restrict__ F,
-                                             double *__restrict__ part)
+                                             double *__restrict__ part, double dc = 4.0)
 {
     const int c = blockIdx.x * TB + threadIdx.x;
     const int r0 = blockIdx.y * ROWS_PB;
@@ -148,7 +193,7 @@ __device__ __forceinline__ void resnorm_body(int N, double inv, const double *__
             const int r = r0 + k;
             if (r < N && !rim(r, c, N)) {
                 const size_t p = (size_t)r * N + c;
-                const double d = HAS_U ? inv * star_minus4(U, p, N) - F[p] : F[p];
+                const double d = HAS_U ? inv * star_minus<SH>(U, p, N, dc) - F[p] : F[p];
                 acc += d * d;
             }
         }
@@ -166,9 +211,9 @@ __global__ __launch_bounds__(TB) void k_resnorm(int N, double inv, const double 
 
 // even N >= PAIR_MIN_N: 16 B per lane, PR rows per thread with a rolling window of three row pairs (every row of U read
 // once), F through 16-byte (non-temporal from NT_MIN_N on) loads -- 16 B of HBM traffic per point
-template <bool HAS_U, bool NT>
+template <bool HAS_U, bool NT, bool SH = false>
 __device__ __forceinline__ void resnorm_pairs_body(int N, double inv, const double *__restrict__ U,
-                                                   const double *__restrict__ F, double *__restrict__ part)
+                                                   const double *__restrict__ F, double *__restrict__ part, double dc = 4.0)
 {
     const int c = 2 * (blockIdx.x * TB + threadIdx.x);
     const int r0 = blockIdx.y * PR;
@@ -196,8 +241,8 @@ __device__ __forceinline__ void resnorm_pairs_body(int N, double inv, const doub
                 double2_s d = f;
                 if (HAS_U) {
                     const double left = U[(size_t)r * N + cl], right = U[(size_t)r * N + cr];
-                    d.x = inv * (down.x + up.x + mid.y + left - 4 * mid.x) - f.x;
-                    d.y = inv * (down.y + up.y + right + mid.x - 4 * mid.y) - f.y;
+                    d.x = inv * (down.x + up.x + mid.y + left - centre<SH>(mid.x, dc)) - f.x;
+                    d.y = inv * (down.y + up.y + right + mid.x - centre<SH>(mid.y, dc)) - f.y;
                 }
                 if (c > 0) acc += d.x * d.x;
                 if (c + 1 < N - 1) acc += d.y * d.y;
@@ -215,6 +260,20 @@ __global__ __launch_bounds__(TB) void k_resnorm_pairs(int N, double inv, const d
                                                       const double *__restrict__ F, double *__restrict__ part)
 {
     resnorm_pairs_body<HAS_U, NT>(N, inv, U, F, part);
+}
+
+// the screened operator's norm (U given: the reference norm ||F|| has no operator in it)
+__global__ __launch_bounds__(TB) void k_resnorm_sh(int N, double inv, double dc, const double *__restrict__ U,
+                                                   const double *__restrict__ F, double *__restrict__ part)
+{
+    resnorm_body<true, true>(N, inv, U, F, part, dc);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(TB) void k_resnorm_pairs_sh(int N, double inv, double dc, const double *__restrict__ U,
+                                                         const double *__restrict__ F, double *__restrict__ part)
+{
+    resnorm_pairs_body<true, NT, true>(N, inv, U, F, part, dc);
 }
 
 // second stage: *out = sqrt(sum of the n partials), one block in a fixed order (run-to-run reproducible)
@@ -249,6 +308,22 @@ __global__ __launch_bounds__(TB) void k_resnorm_pairs_b(int N, double inv, const
                                   part + blockIdx.z * n);
 }
 
+__global__ __launch_bounds__(TB) void k_resnorm_sh_b(int N, double inv, double dc, const NodeBatchItem *__restrict__ items,
+                                                     double *__restrict__ part, size_t n)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    resnorm_body<true, true>(N, inv, static_cast<const double *>(it.in), static_cast<const double *>(it.F), part + blockIdx.z * n, dc);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(TB) void k_resnorm_pairs_sh_b(int N, double inv, double dc, const NodeBatchItem *__restrict__ items,
+                                                           double *__restrict__ part, size_t n)
+{
+    const NodeBatchItem &it = items[blockIdx.z];
+    resnorm_pairs_body<true, NT, true>(N, inv, static_cast<const double *>(it.in), static_cast<const double *>(it.F),
+                                       part + blockIdx.z * n, dc);
+}
+
 // out[i] = sqrt(sum of instance i's n partials): one block per instance, each the single-instance finish
 __global__ __launch_bounds__(1024) void k_resnorm_finish_b(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
@@ -261,9 +336,12 @@ __global__ __launch_bounds__(1024) void k_resnorm_finish_b(const double *__restr
 // is max(atol, rtol*err0) with err0 the same metric at U = 0 (sum|F| / (N-2)^2), evaluated here from F before the
 // first iteration; at least one iteration, at most max_iters.  state[1] = iterations, state[2] = 1 when the cap ended
 // the solve above the target, state[3] = bits of nothing (kept zero).  *err_out (when given) = err0, final err.
+// SH: update q*(...) with q = 1/d, the error metric's centre term d*U (the unshifted form: 0.25 and 4)
+template <bool SH = false>
 __device__ __forceinline__ void gs_relative_body(int N, double h2, double inv, double *__restrict__ Ug,
                                                  const double *__restrict__ Fg, double atol, double rtol, int max_iters,
-                                                 int *__restrict__ state, double *__restrict__ err_out)
+                                                 int *__restrict__ state, double *__restrict__ err_out, double dc = 4.0,
+                                                 double qc = 0.25)
 {
     extern __shared__ __align__(16) double lds[];
     __shared__ double s_val;
@@ -291,7 +369,7 @@ __device__ __forceinline__ void gs_relative_body(int N, double h2, double inv, d
             for (int p = threadIdx.x; p < n; p += blockDim.x) {
                 const int r = p / N, c = p - r * N;
                 if (!rim(r, c, N) && ((r + c) & 1) == colour)
-                    U[p] = 0.25 * (U[p - 1] + U[p + 1] + U[p + N] + U[p - N] - h2 * F[p]);
+                    U[p] = (SH ? qc : 0.25) * (U[p - 1] + U[p + 1] + U[p + N] + U[p - N] - h2 * F[p]);
             }
             __syncthreads();
         }
@@ -300,7 +378,7 @@ __device__ __forceinline__ void gs_relative_body(int N, double h2, double inv, d
         for (int p = threadIdx.x; p < n; p += blockDim.x) {
             const int r = p / N, c = p - r * N;
             if (!rim(r, c, N))
-                acc = acc + fabs(inv * (U[p + N] + U[p - N] + U[p + 1] + U[p - 1] - 4 * U[p]) - F[p]);
+                acc = acc + fabs(inv * (U[p + N] + U[p - N] + U[p + 1] + U[p - 1] - centre<SH>(U[p], dc)) - F[p]);
         }
         s = block_sum(acc);
         if (threadIdx.x == 0) s_val = s / denom;
@@ -338,10 +416,27 @@ __global__ __launch_bounds__(1024) void k_gs_relative_b(int N, double h2, double
                      state + 4 * blockIdx.x, nullptr);
 }
 
+__global__ __launch_bounds__(1024) void k_gs_relative_sh(int N, double h2, double inv, double dc, double qc, double *__restrict__ Ug,
+                                                         const double *__restrict__ Fg, double atol, double rtol,
+                                                         int max_iters, int *__restrict__ state, double *__restrict__ err_out)
+{
+    gs_relative_body<true>(N, h2, inv, Ug, Fg, atol, rtol, max_iters, state, err_out, dc, qc);
+}
+
+__global__ __launch_bounds__(1024) void k_gs_relative_sh_b(int N, double h2, double inv, double dc, double qc,
+                                                           const NodeBatchItem *__restrict__ items, double atol, double rtol,
+                                                           int max_iters, int *__restrict__ state)
+{
+    const NodeBatchItem &it = items[blockIdx.x];
+    gs_relative_body<true>(N, h2, inv, static_cast<double *>(it.out), static_cast<const double *>(it.F), atol, rtol, max_iters,
+                           state + 4 * blockIdx.x, nullptr, dc, qc);
+}
+
 // ---------------------------------------------------------------- transfer operators of the non-fusable levels, batched
 // The expressions of k_residual, k_restrict<double> and k_prolong<true, double> (mg_kernels.hip), one point per lane;
 // instance blockIdx.z of items[].  residual: in = U, F, out = D.
-__global__ __launch_bounds__(TB) void k_residual_b(int N, double inv, const NodeBatchItem *__restrict__ items, int sign)
+template <bool SH>
+__device__ __forceinline__ void residual_b_body(int N, double inv, const NodeBatchItem *__restrict__ items, int sign, double dc)
 {
     const NodeBatchItem &it = items[blockIdx.z];
     const double *__restrict__ U = static_cast<const double *>(it.in);
@@ -356,9 +451,19 @@ __global__ __launch_bounds__(TB) void k_residual_b(int N, double inv, const Node
         if (r >= N) return;
         const size_t p = (size_t)r * N + c;
         double v = 0.0;
-        if (!rim(r, c, N)) v = inv * star_minus4(U, p, N) - F[p];
+        if (!rim(r, c, N)) v = inv * star_minus<SH>(U, p, N, dc) - F[p];
         D[p] = sign < 0 ? -v : v;
     }
+}
+
+__global__ __launch_bounds__(TB) void k_residual_b(int N, double inv, const NodeBatchItem *__restrict__ items, int sign)
+{
+    residual_b_body<false>(N, inv, items, sign, 4.0);
+}
+
+__global__ __launch_bounds__(TB) void k_residual_sh_b(int N, double inv, double dc, const NodeBatchItem *__restrict__ items, int sign)
+{
+    residual_b_body<true>(N, inv, items, sign, dc);
 }
 
 // restriction N -> M (doRestriction, :656-678): in = fine field, out = coarse field
@@ -425,8 +530,16 @@ inline dim3 grid_pairs(int N) { return dim3((N / 2 + TB - 1) / TB, (N + PR - 1) 
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
-void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out)
+void wjacobi(hipStream_t s, int N, double dx2, double cw, const double *in, const double *F, double *out, const Shifted &sh)
 {
+    if (sh.on) {   // the same choice of form, the screened bracket
+        const double d = sh.d;
+        if (!in) hipLaunchKernelGGL(k_wjacobi_sh<true>, grid_rows(N), dim3(TB), 0, s, N, dx2, cw, d, in, F, out);
+        else if (use_pairs(N) && N >= NT_MIN_N) hipLaunchKernelGGL(k_wjacobi_pairs_sh<true>, grid_pairs(N), dim3(TB), 0, s, N, dx2, cw, d, in, F, out);
+        else if (use_pairs(N)) hipLaunchKernelGGL(k_wjacobi_pairs_sh<false>, grid_pairs(N), dim3(TB), 0, s, N, dx2, cw, d, in, F, out);
+        else hipLaunchKernelGGL(k_wjacobi_sh<false>, grid_rows(N), dim3(TB), 0, s, N, dx2, cw, d, in, F, out);
+        return;
+    }
     if (!in) {
         hipLaunchKernelGGL(k_wjacobi<true>, grid_rows(N), dim3(TB), 0, s, N, dx2, cw, in, F, out);
         return;
@@ -445,10 +558,17 @@ size_t resnorm_partials(int N)
     return (size_t)g.x * g.y;
 }
 
-void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out)
+void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F, double *part, double *out, const Shifted &sh)
 {
     const size_t np = resnorm_partials(N);
-    if (use_pairs(N)) {
+    if (sh.on && U) {
+        if (use_pairs(N)) {
+            if (N >= NT_MIN_N) hipLaunchKernelGGL(k_resnorm_pairs_sh<true>, grid_pairs(N), dim3(TB), 0, s, N, inv, sh.d, U, F, part);
+            else hipLaunchKernelGGL(k_resnorm_pairs_sh<false>, grid_pairs(N), dim3(TB), 0, s, N, inv, sh.d, U, F, part);
+        } else {
+            hipLaunchKernelGGL(k_resnorm_sh, grid_rows(N), dim3(TB), 0, s, N, inv, sh.d, U, F, part);
+        }
+    } else if (use_pairs(N)) {
         const dim3 g = grid_pairs(N);
         const bool nt = N >= NT_MIN_N;
         if (U) {
@@ -468,21 +588,33 @@ void resnorm(hipStream_t s, int N, double inv, const double *U, const double *F,
 bool gs_relative_fits(int N) { return N >= 3 && N < GS_RELATIVE_MAX_N; }
 
 void gauss_seidel_relative(hipStream_t s, int N, double h2, double inv, double *U, const double *F, double atol,
-                           double rtol, int max_iters, int *state, double *err_out)
+                           double rtol, int max_iters, int *state, double *err_out, const Shifted &sh)
 {
     const size_t n = (size_t)N * N;
     const size_t lds = 2 * n * sizeof(double);
     int threads = (int)((n + 63) / 64 * 64);
     if (threads > 1024) threads = 1024;
     // (N <= 63: at most 63 KiB of U and F, inside the default 64 KiB of dynamic LDS)
+    if (sh.on) {
+        hipLaunchKernelGGL(k_gs_relative_sh, dim3(1), dim3(threads), lds, s, N, h2, inv, sh.d, sh.q, U, F, atol, rtol, max_iters, state,
+                           err_out);
+        return;
+    }
     hipLaunchKernelGGL(k_gs_relative, dim3(1), dim3(threads), lds, s, N, h2, inv, U, F, atol, rtol, max_iters, state, err_out);
 }
 
 // ------------------------------------------------------------------ batched launchers (mg_solve_batch.cpp)
-void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out)
+void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const NodeBatchItem *items, double *part, double *out,
+                   const Shifted &sh)
 {
     const size_t np = resnorm_partials(N);
-    if (use_pairs(N)) {
+    if (sh.on && has_u) {
+        dim3 g = use_pairs(N) ? grid_pairs(N) : grid_rows(N);
+        g.z = n;
+        if (!use_pairs(N)) hipLaunchKernelGGL(k_resnorm_sh_b, g, dim3(TB), 0, s, N, inv, sh.d, items, part, np);
+        else if (N >= NT_MIN_N) hipLaunchKernelGGL(k_resnorm_pairs_sh_b<true>, g, dim3(TB), 0, s, N, inv, sh.d, items, part, np);
+        else hipLaunchKernelGGL(k_resnorm_pairs_sh_b<false>, g, dim3(TB), 0, s, N, inv, sh.d, items, part, np);
+    } else if (use_pairs(N)) {
         dim3 g = grid_pairs(N);
         g.z = n;
         const bool nt = N >= NT_MIN_N;
@@ -503,19 +635,28 @@ void resnorm_batch(hipStream_t s, int n, int N, double inv, bool has_u, const No
 }
 
 void gauss_seidel_relative_batch(hipStream_t s, int n, int N, double h2, double inv, const NodeBatchItem *items, double atol,
-                                 double rtol, int max_iters, int *state)
+                                 double rtol, int max_iters, int *state, const Shifted &sh)
 {
     const size_t cells = (size_t)N * N;
     int threads = (int)((cells + 63) / 64 * 64);
     if (threads > 1024) threads = 1024;
+    if (sh.on) {
+        hipLaunchKernelGGL(k_gs_relative_sh_b, dim3(n), dim3(threads), 2 * cells * sizeof(double), s, N, h2, inv, sh.d, sh.q, items,
+                           atol, rtol, max_iters, state);
+        return;
+    }
     hipLaunchKernelGGL(k_gs_relative_b, dim3(n), dim3(threads), 2 * cells * sizeof(double), s, N, h2, inv, items, atol, rtol,
                        max_iters, state);
 }
 
-void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign)
+void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items, int sign, const Shifted &sh)
 {
     dim3 g = grid_rows(N);
     g.z = n;
+    if (sh.on) {
+        hipLaunchKernelGGL(k_residual_sh_b, g, dim3(TB), 0, s, N, inv, sh.d, items, sign);
+        return;
+    }
     hipLaunchKernelGGL(k_residual_b, g, dim3(TB), 0, s, N, inv, items, sign);
 }
 

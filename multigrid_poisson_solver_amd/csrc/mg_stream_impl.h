@@ -145,6 +145,11 @@ struct StreamParams {
     // 0.25*omega formed on the host, product and sum rounded separately.  Last, so that the other fields keep their offsets.
     real_t cw;
     int wt;                     // (host side only: launch the WT instantiation)
+    // SH instantiations (the screened operator of the same solver, mg_solve_opts.shift != 0): the centre coefficient of the
+    // bracket, dc = 4 + shift*dx2 formed on the host, in the sweeps and in the residual stage; cw is then omega/dc.
+    // Wave-uniform: it stays in a scalar register pair and enters the v_mul_f64 as its scalar operand.
+    real_t dc;
+    int sh;                     // (host side only: launch the SH instantiation)
 };
 
 
@@ -367,7 +372,17 @@ __device__ __forceinline__ Row<COLS> ring_unpack(const typename RingVec<COLS>::f
 #define MG_WPE_UP 2   // (3 = 168 VGPRs: the allocator spills 15-27 dwords, and a spill reload drains the load queue: 580 us)   waves per SIMD the allocator is asked to make room for in the LDS-ring form of the `1` node
 #endif
 
-template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false>
+// `a - d*u`, the bracket's centre term: SH = false is minus4 (one fma, exact product with 4); SH = true rounds the
+// product with the level's centre coefficient and then subtracts it (-ffp-contract=off keeps the two apart), which is
+// what a numpy restatement computes
+template <bool SH>
+__device__ __forceinline__ real_t minus_centre(real_t a, real_t u, real_t dc)
+{
+    if constexpr (SH) return a - dc * u;
+    else return minus4(a, u);
+}
+
+template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false, bool SH = false>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(LdsRing<COLS, PRE>::value ? MG_WPE_UP : WavesPerSimd<S, COLS, IN, RESTRICT, PRE>::min)))
 void k_jacobi_stream(const StreamParams p)
 {
@@ -381,6 +396,7 @@ void k_jacobi_stream(const StreamParams p)
     // read here, 8 B per point less to write there, for PRE more sweeps of arithmetic in a kernel that waits for memory.
     static_assert(PRE == 0 || (IN == IN_PROLONG && !RESTRICT), "recomputed pre-smoothing belongs to the fused `1` node");
     static_assert(!WT || (PRE == 0 && sizeof(real_t) == 8), "the weighted sweep: fp64 nodes that store and re-read U");
+    static_assert(!SH || WT, "the screened operator is a form of the weighted sweep");
     constexpr int L = S + PRE;                         // levels of the pipeline
     constexpr bool LDSR = LdsRing<COLS, PRE>::value;   // F rows in LDS (dx2*F for the sweeps, one column of F for the norm)
     constexpr bool HALF = LDSR;                        // norm-only residual stage: one column per row
@@ -467,6 +483,7 @@ void k_jacobi_stream(const StreamParams p)
     }
     const bool lane_loads = col_in[0] && col_in[COLS - 1];  // COLS == 2: N even, xl even
     const real_t dx2 = p.dx2, inv = p.inv;
+    const real_t dc = SH ? p.dc : real_t(4.0);
     const bool want_res = RESTRICT || p.D != nullptr || p.part != nullptr;
     // clamped column of this lane's loads (lanes left/right of the grid re-read a valid pair); lane offsets in
     // bytes, see load_row
@@ -890,7 +907,7 @@ void k_jacobi_stream(const StreamParams p)
                     const real_t e = j == COLS - 1 ? east_last : c.v[j < COLS - 1 ? j + 1 : 0];
                     // src/MG_solver_CPU.cpp:590: U += 0.25*(U[i+1]+U[i-1]+U[j+1]+U[j-1] - 4U - dx^2 F)
                     // `- 4*U` through one fma: 4*U is exact, so fma(-4, U, a) is the same bits as a - 4*U (one VALU op less)
-                    const real_t t4 = minus4(nw.v[j] + so.v[j] + e + w, c.v[j]) - g.v[j];
+                    const real_t t4 = minus_centre<SH>(nw.v[j] + so.v[j] + e + w, c.v[j], dc) - g.v[j];
                     // `U + 0.25*t` through one fma as well: the product with a power of two is exact, so the fused form
                     // rounds once exactly like the sum does; with q = 0 on the rim (row or column) the point keeps its
                     // value, which replaces the rim selects
@@ -996,7 +1013,7 @@ void k_jacobi_stream(const StreamParams p)
                 for (int j = 0; j < COLS; ++j) {
                     const real_t w = j == 0 ? west0 : c.v[j > 0 ? j - 1 : 0];
                     const real_t e = j == COLS - 1 ? east_last : c.v[j < COLS - 1 ? j + 1 : 0];
-                    const real_t r = inv * minus4(nw.v[j] + so.v[j] + e + w, c.v[j]) - f.v[j];
+                    const real_t r = inv * minus_centre<SH>(nw.v[j] + so.v[j] + e + w, c.v[j], dc) - f.v[j];
                     if constexpr (RESTRICT) {
                         d.v[j] = r * hi_bits_and(ms[j], inner);  // sign flip :277-280 and the zero rim in one exact product
                     } else {
@@ -1089,13 +1106,13 @@ void k_jacobi_stream(const StreamParams p)
 // One launch: tile the grid for ONE resident round of workgroups (measured occupancy of
 // this instantiation x CUs) where the grid is large enough, never fewer than 8 rows per
 // chunk (each chunk re-reads 2(S+1) halo rows), then the fixed-order error reduction.
-template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false>
+template <int S, int COLS, int IN, bool RESTRICT, int PF = PF_DEFAULT, bool NT = false, int PRE = 0, bool WT = false, bool SH = false>
 void launch_k(hipStream_t s, StreamParams p, double *err_out)
 {
     static int blocks_per_cu = 0;
     if (blocks_per_cu == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT>, 64 * WAVES_PER_WG, 0) != hipSuccess || n < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT, SH>, 64 * WAVES_PER_WG, 0) != hipSuccess || n < 1) {
             (void)hipGetLastError();
             n = 2;
         }
@@ -1147,7 +1164,7 @@ void launch_k(hipStream_t s, StreamParams p, double *err_out)
     }
     p.part_stride = (int)n_part;
     const int grid = ((p.n_blocks + 7) / 8) * 8;   // (a multiple of 8: with x fastest in the dispatch order, x & 7 stays the XCD of a workgroup for every y)
-    hipLaunchKernelGGL((k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT>), dim3(grid, nb), dim3(64 * WAVES_PER_WG), 0, s, p);
+    hipLaunchKernelGGL((k_jacobi_stream<S, COLS, IN, RESTRICT, PF, NT, PRE, WT, SH>), dim3(grid, nb), dim3(64 * WAVES_PER_WG), 0, s, p);
 #ifdef MG_STREAM_TRACE
     {
         long long t[4];
@@ -1227,20 +1244,26 @@ void launch_variant(hipStream_t s, const StreamParams &p, double *err_out)
     }
     if constexpr (sizeof(real_t) == 8) {
         if (p.wt) {   // the weighted sweep: the zero / load / fused restriction / fused prolongation forms, no recomputing pair
-            if (p.N % 2 != 0) {
-                if (zero) launch_k<S, 1, IN_ZERO, false, PF, false, 0, true>(s, p, err_out);
-                else launch_k<S, 1, IN_LOAD, false, PF, false, 0, true>(s, p, err_out);
-            } else if (restrict_out) {
-                if (zero) launch_k<S, 2, IN_ZERO, true, (PF == 2 && S <= 3 ? MG_PF_DOWN : PF), false, 0, true>(s, p, err_out);
-                else launch_k<S, 2, IN_LOAD, true, PF, false, 0, true>(s, p, err_out);
-            } else if (prolong_in) {
-                if (p.pre != 0) fail(MG_ERR_UNSUPPORTED, "jacobi_stream: no recomputing `1` node for the weighted sweep");
-                else if (nt) launch_k<S, 2, IN_PROLONG, false, PF, true, 0, true>(s, p, err_out);
-                else launch_k<S, 2, IN_PROLONG, false, PF, false, 0, true>(s, p, err_out);
-            } else {
-                if (zero) launch_k<S, 2, IN_ZERO, false, PF, false, 0, true>(s, p, err_out);
-                else launch_k<S, 2, IN_LOAD, false, PF, false, 0, true>(s, p, err_out);
-            }
+            // (SH: the same families once more with the screened bracket, picked only when the solver's shift is not zero)
+            auto weighted = [&](auto sh_tag) {
+                constexpr bool SH = decltype(sh_tag)::value;
+                if (p.N % 2 != 0) {
+                    if (zero) launch_k<S, 1, IN_ZERO, false, PF, false, 0, true, SH>(s, p, err_out);
+                    else launch_k<S, 1, IN_LOAD, false, PF, false, 0, true, SH>(s, p, err_out);
+                } else if (restrict_out) {
+                    if (zero) launch_k<S, 2, IN_ZERO, true, (PF == 2 && S <= 3 ? MG_PF_DOWN : PF), false, 0, true, SH>(s, p, err_out);
+                    else launch_k<S, 2, IN_LOAD, true, PF, false, 0, true, SH>(s, p, err_out);
+                } else if (prolong_in) {
+                    if (p.pre != 0) fail(MG_ERR_UNSUPPORTED, "jacobi_stream: no recomputing `1` node for the weighted sweep");
+                    else if (nt) launch_k<S, 2, IN_PROLONG, false, PF, true, 0, true, SH>(s, p, err_out);
+                    else launch_k<S, 2, IN_PROLONG, false, PF, false, 0, true, SH>(s, p, err_out);
+                } else {
+                    if (zero) launch_k<S, 2, IN_ZERO, false, PF, false, 0, true, SH>(s, p, err_out);
+                    else launch_k<S, 2, IN_LOAD, false, PF, false, 0, true, SH>(s, p, err_out);
+                }
+            };
+            if (p.sh) weighted(std::true_type{});
+            else weighted(std::false_type{});
             return;
         }
     }
@@ -1308,7 +1331,7 @@ inline void run(hipStream_t s, const SmoothNode<real_t> &nd)
     }
     // (a batch of weighted nodes: the batched solver, mg_solve_batch.cpp -- the kernel body takes every instance's arrays,
     // `in` included, from the table; slab windows are refused above for every batch)
-    if (nd.cw != 0.25 && (pre != 0 || sizeof(real_t) != 8)) {
+    if ((nd.cw != 0.25 || nd.shifted) && (pre != 0 || sizeof(real_t) != 8)) {
         fail(MG_ERR_ARG, "jacobi_stream: the weighted sweep runs fp64 nodes that store and re-read U");
         return;
     }
@@ -1341,6 +1364,10 @@ inline void run(hipStream_t s, const SmoothNode<real_t> &nd)
     p.no_out = nd.no_out ? 1 : 0;
     p.cw = (real_t)nd.cw;
     p.wt = nd.cw != 0.25 ? 1 : 0;   // (0.25: the unweighted instantiations, the same bits: the product with 0.25 is exact)
+    if (nd.shifted) {               // the screened operator: its own instantiations of the weighted families, whatever cw is
+        p.dc = (real_t)nd.dc;
+        p.sh = p.wt = 1;
+    }
     p.D = nd.D;
     p.d_sign = nd.d_sign;
     p.row_base = fine_w ? fine_w->base : 0;

@@ -3,6 +3,7 @@ omega 0.8, instance i solves F_i = (1 + i/B) * getSource from U = 0 (random F re
 1025^2; getSource converges there in about 10 cycles).  For B in {1, 8, 64} at N = 257 and N = 1025: ms per batched
 cycle (steady state), total ms to rtol 1e-10, the same B problems solved one after another with Solver, and the
 throughput ratio; B = 1 at N = 8192 (getSource, rtol 1e-9) against Solver.  Times are hipEvent times of whole calls.
+--shift SIGMA: every solver solves Laplace(U) - SIGMA*U = F (mg_solve_opts.shift), the workload of implicit time stepping.
 Prints one JSON line."""
 import argparse
 import json
@@ -14,6 +15,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import multigrid_poisson_solver_amd as mg  # noqa: E402
+
+
+SHIFT = {}   # the options every solver of this run gets on top of its own (--shift)
 
 
 def problems(N, B):
@@ -32,7 +36,7 @@ def reset(probs):
 
 
 def batched_ms(N, probs, reps, **opts):
-    bs = mg.BatchSolver(N, 1.0, max_batch=len(probs), **opts)
+    bs = mg.BatchSolver(N, 1.0, max_batch=len(probs), **SHIFT, **opts)
     best, infos = None, None
     for _ in range(reps + 1):   # (the first call warms up)
         reset(probs)
@@ -44,7 +48,7 @@ def batched_ms(N, probs, reps, **opts):
 
 
 def sequential_ms(N, probs, reps, **opts):
-    s = mg.Solver(N, 1.0, **opts)
+    s = mg.Solver(N, 1.0, **SHIFT, **opts)
     best, cycles = None, 0
     for _ in range(reps + 1):
         reset(probs)
@@ -71,7 +75,9 @@ def main():
     ap.add_argument("--sizes", default="257,1025")
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--big", type=int, default=8192)
+    ap.add_argument("--shift", type=float, default=0.0)
     a = ap.parse_args()
+    SHIFT.update(dict(shift=a.shift) if a.shift != 0.0 else {})
     mg.init(0)
     rows = []
     for N in [int(x) for x in a.sizes.split(",")]:
@@ -95,9 +101,9 @@ def main():
         probs = problems(N, 1)
         F, U, zero = probs[0]
         cyc_b, cyc_s, tot_b, tot_s = [], [], [], []
-        bs = {k: mg.BatchSolver(N, 1.0, max_batch=1, rtol=0.0, atol=0.0, max_cycles=k) for k in (2, 6)}
-        ss = {k: mg.Solver(N, 1.0, rtol=0.0, atol=0.0, max_cycles=k) for k in (2, 6)}
-        bconv, sconv = mg.BatchSolver(N, 1.0, max_batch=1, rtol=1e-9), mg.Solver(N, 1.0, rtol=1e-9)
+        bs = {k: mg.BatchSolver(N, 1.0, max_batch=1, rtol=0.0, atol=0.0, max_cycles=k, **SHIFT) for k in (2, 6)}
+        ss = {k: mg.Solver(N, 1.0, rtol=0.0, atol=0.0, max_cycles=k, **SHIFT) for k in (2, 6)}
+        bconv, sconv = mg.BatchSolver(N, 1.0, max_batch=1, rtol=1e-9, **SHIFT), mg.Solver(N, 1.0, rtol=1e-9, **SHIFT)
         for _ in range(2 * a.reps + 1):
             t = {}
             for k in (2, 6):
@@ -119,7 +125,7 @@ def main():
         big = dict(N=N, B=1, rtol=1e-9, batched_cycle_ms=round(cb, 4), solver_cycle_ms=round(cs, 4), cycle_ratio=round(cb / cs, 4),
                    batched_total_ms=round(min(tot_b[1:]), 3), solver_total_ms=round(min(tot_s[1:]), 3), cycles=ib["cycles"],
                    solver_cycles=isv["cycles"], converged=ib["converged"], same_history=ib["history"] == isv["history"])
-    out = dict(metric="solve_batched", pre=3, post=3, omega=0.8, rows=rows, big=big)
+    out = dict(metric="solve_batched", pre=3, post=3, omega=0.8, shift=a.shift, rows=rows, big=big)
     print(json.dumps(out), flush=True)
     mg.finalize()
 
