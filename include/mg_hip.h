@@ -361,7 +361,33 @@ void mg_slab_destroy(mg_slab_plan *plan);
  * shift = 0 is the Poisson solve above bit for bit, through the same kernels; a negative shift (the indefinite Helmholtz
  * problem) is refused with MG_ERR_ARG.
  * ABI: `shift` was appended to mg_solve_opts in version 0.2; a caller compiled against the 0.1 header passes a shorter
- * struct and must be recompiled (mg_version() tells the two apart). */
+ * struct and must be recompiled (mg_version() tells the two apart).
+ *
+ * fmg (full-multigrid start; 0 = none: everything above, bit for bit, through the same launches; n in 1..8 = n V-cycles
+ * per coarse level during the ascent; anything else is refused with MG_ERR_ARG).  With fmg >= 1 a solve whose start does
+ * not already meet the tolerance first replaces the INTERIOR of U by the FMG guess -- the interior the caller passed is
+ * ignored, the rim is the Dirichlet data and is not written by the pass -- and then runs the cycle loop above.  history[0]
+ * and res0 stay the norm of the caller's start, the pass is not counted in `cycles` (with max_cycles = 0 the pass still runs
+ * and res stays res0); a start that meets the tolerance runs nothing and leaves U untouched.  Levels l = 0 (finest) ..
+ * last are the hierarchy's sizes N_l.  The pass:
+ *  1. F_0 = F, F_{l+1} = doRestriction(N_l, F_l, N_{l+1}).
+ *  2. Rim data g_0 = the rim of U (four edges: row 0, row N-1, column 0, column N-1); each edge of g_{l+1} is the edge of
+ *     g_l sampled at the N_{l+1} coarse points with the 1-D table mg_cubic_table(N_l -> N_{l+1}) (mg_fmg.h) in the order
+ *     ((w0*s0 + w1*s1) + w2*s2) + w3*s3, corners included (they are end points of the edges: t = 0 and t = N_l - 1).
+ *  3. Coarsest level: r = -getResidual(rim_only(g_last), F_last) (the field with g_last on its rim and +0 inside; with
+ *     shift, the screened residual), e = the coarse solve of A e = r from zero with coarse_rtol / coarse_atol /
+ *     coarse_max_iters as in a cycle (it reads no rim value of r), u_last = e inside, g_last on the rim.
+ *  4. For l = last-1 .. 0: the interior of u_l = mg_prolongCubic(u_{l+1}) (rim included as data), the rim of u_l = g_l (at
+ *     l = 0 the caller's rim, untouched); for l >= 1 then `fmg` cycles as above started at level l from u_l on F_l (level l
+ *     keeps its field, the levels below start from zero; the constants of every level, shift included, are the solve's).
+ *     Level 0 gets no cycle inside the pass: the cycle loop follows.
+ * A coarse solve of the pass that stops at its cap sets coarse_capped like one of a cycle.  The option needs
+ * about N^2/3 more doubles of device memory (the F_l of the coarse levels; the g_l and the tables are O(N)), allocated at
+ * creation when fmg >= 1.
+ * mg_batch_solver_create refuses fmg != 0 with MG_ERR_ARG: the batched pass is not built yet.
+ * ABI: `fmg` (version 0.2.1) sits in the alignment hole between max_cycles and shift: the size of the struct and the offset
+ * of every 0.2 field are unchanged, shift stays the last field, and mg_solve_opts_default() of this library sets fmg = 0
+ * in the struct of a caller compiled against the 0.2 header. */
 typedef struct mg_solve_opts {
     int    pre, post;          /* sweeps per level on the way down / up, 1..4 */
     int    N_min;              /* coarsest size bound, 3..32 */
@@ -370,6 +396,7 @@ typedef struct mg_solve_opts {
     int    coarse_max_iters;   /* >= 1; reaching it is reported (coarse_capped), not fatal */
     double rtol, atol;         /* stopping rule on the L2 residual */
     int    max_cycles;         /* >= 0 */
+    int    fmg;                /* full-multigrid start: 0 = off, 1..8 = V-cycles per coarse level of the ascent */
     double shift;              /* sigma of Laplace(U) - sigma*U = F, finite and >= 0; 0: the Poisson equation (LAST field) */
 } mg_solve_opts;
 
@@ -390,7 +417,7 @@ typedef struct mg_solve_result {
 typedef struct mg_solver mg_solver;
 
 /* V(3,3), omega 0.8, N_min 8, coarse_rtol 1e-2, coarse_atol 0, coarse_max_iters 10000, rtol 1e-10, atol 0, 50 cycles,
- * shift 0.
+ * shift 0, fmg 0.
  * rtol is relative to ||F||: on large grids the fp64 rounding of inv*(star - 4U) (inv = 1/dx^2) puts a floor under the
  * reachable residual -- about 8e-10 relative at N = 8192 on the getSource problem -- so a default solve there runs all
  * max_cycles and returns MG_SOLVE_NOT_CONVERGED; ask for rtol >= 1e-9 at that size. */
@@ -438,4 +465,8 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 #ifdef __cplusplus
 }
 #endif
+
+/* the building blocks of the full-multigrid start (mg_solve_opts.fmg): mg_cubic_table, mg_prolongCubic */
+#include "mg_fmg.h"
+
 #endif /* MG_HIP_H */

@@ -48,7 +48,7 @@ _dptr = C.POINTER(C.c_double)
 class SolveOpts(C.Structure):
     _fields_ = [("pre", C.c_int), ("post", C.c_int), ("N_min", C.c_int), ("omega", C.c_double), ("coarse_rtol", C.c_double),
                 ("coarse_atol", C.c_double), ("coarse_max_iters", C.c_int), ("rtol", C.c_double), ("atol", C.c_double),
-                ("max_cycles", C.c_int), ("shift", C.c_double)]
+                ("max_cycles", C.c_int), ("fmg", C.c_int), ("shift", C.c_double)]   # (fmg fills the hole before shift)
 
 
 class SolveResult(C.Structure):
@@ -120,6 +120,12 @@ ABI = {
     "mg_profile_begin": (None, [_i]), "mg_profile_sample": (None, [_i]), "mg_profile_end": (_i, [C.POINTER(ProfileEntry), _i]),
 }
 
+# the symbols include/mg_fmg.h declares (the full-multigrid start's building blocks); a library without them -- an older
+# build named by MG_LIB for an A/B run -- still loads, cubic_table() / prolongCubic() then raise
+ABI_FMG = {
+    "mg_cubic_table": (None, [_i, _i, _vp, _vp]), "mg_prolongCubic": (None, [_i, _vp, _i, _vp]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -177,6 +183,10 @@ def load_library(path=None):
         fn.restype, fn.argtypes = res, args
     if missing:
         raise MGError(f"{path} does not export: {missing}")
+    for name, (res, args) in ABI_FMG.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
 
@@ -492,6 +502,25 @@ def prolongation_table(N, M, axis):
     return owner, hi, lo
 
 
+def cubic_table(N_src, N_dst):
+    """mg_cubic_table: (base[N_dst], w[N_dst, 4]) of the 1-D cubic interpolation from N_src to N_dst points (the table of
+    the full-multigrid start, solve_opts(fmg=...)); host only."""
+    base = np.empty(N_dst, dtype=np.int32)
+    w = np.empty((N_dst, 4), dtype=np.float64)
+    if not hasattr(load_library(), "mg_cubic_table"):
+        raise MGError(f"{LIB_PATH} does not export mg_cubic_table (a build without the fmg option)")
+    load_library().mg_cubic_table(N_src, N_dst, base.ctypes.data, w.ctypes.data)
+    return base, w
+
+
+def prolongCubic(N_src, U_c, N_dst, U_f):
+    """mg_prolongCubic on DeviceGrids: the interior of U_f = bicubic interpolation of U_c; the rim of U_f is not written."""
+    if not hasattr(lib(), "mg_prolongCubic"):
+        raise MGError(f"{LIB_PATH} does not export mg_prolongCubic (a build without the fmg option)")
+    lib().mg_prolongCubic(N_src, U_c.ptr, N_dst, U_f.ptr)
+    _check()
+
+
 def profile_begin(min_N=0, every=1):
     lib().mg_profile_sample(int(every))
     lib().mg_profile_begin(int(min_N))
@@ -781,7 +810,11 @@ def solve_opts(**opts):
     so pass rtol=1e-9 or more at that size.
     shift (sigma, default 0, finite and >= 0) solves the screened equation  Laplace(U) - sigma*U = F  on every level
     instead (include/mg_hip.h gives the per-level constants); 0 is the Poisson solve bit for bit.  An implicit time step
-    of u_t = nu*Laplace(u) is one such solve with sigma = 1/(nu*dt) and F = -u_old/(nu*dt)."""
+    of u_t = nu*Laplace(u) is one such solve with sigma = 1/(nu*dt) and F = -u_old/(nu*dt).
+    fmg (default 0 = off; 1..8) gives the solve a full-multigrid start: unless the start already meets the tolerance, the
+    interior of U is first replaced by the coarsest level's solution interpolated upwards with cubic interpolation and
+    fmg V-cycles per coarse level (the interior passed in is ignored, the rim is the boundary data), then the cycles
+    run: 2-5 cycles to rtol 1e-9 instead of 8-11 from a cold start.  Solver only: BatchSolver refuses fmg != 0."""
     o = SolveOpts()
     lib().mg_solve_opts_default(C.byref(o))
     names = {f for f, _ in SolveOpts._fields_}
@@ -796,7 +829,8 @@ class Solver:
     """Residual-tolerance solver of include/mg_hip.h: V(pre, post) cycles with a weighted Jacobi smoother and a
     relative coarse target, on a caller's F and Dirichlet rim, until ||F - AU||_2 <= max(rtol*||F||_2, atol).  Every
     level array is allocated here; solve() allocates nothing on the device.  With shift=sigma > 0 the operator is
-    A U = Laplace(U) - sigma*U (solve_opts); an implicit time step has sigma = 1/(nu*dt), F = -u_old/(nu*dt)."""
+    A U = Laplace(U) - sigma*U (solve_opts); an implicit time step has sigma = 1/(nu*dt), F = -u_old/(nu*dt).
+    fmg=n (1..8) starts every solve from a full-multigrid guess instead of U's interior (solve_opts)."""
 
     def __init__(self, N, L=1.0, **opts):
         self.N, self.L = int(N), float(L)
@@ -878,7 +912,8 @@ def solve(F, U=None, L=1.0, **opts):
     """Solve the Poisson problem A U = F on the N x N grid of F (Dirichlet values on U's rim) to the residual
     tolerance; returns (U, info).  See Solver, and solve_opts for the defaults (the default rtol of 1e-10 is below the
     rounding floor of large grids: about 8e-10 at N = 8192).  shift=sigma > 0 solves Laplace(U) - sigma*U = F, the
-    equation of an implicit time step: sigma = 1/(nu*dt), F = -u_old/(nu*dt)."""
+    equation of an implicit time step: sigma = 1/(nu*dt), F = -u_old/(nu*dt).  fmg=1 starts from a full-multigrid guess
+    (U then only supplies the rim)."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:
@@ -904,7 +939,7 @@ class BatchSolver:
     An instance stops once it meets its own tolerance; one cycle is one launch per node over all active instances.
     Every level array for max_batch instances is allocated here; solve() allocates nothing on the device.  shift=sigma
     (one value for the whole batch) solves Laplace(U) - sigma*U = F: the many same-size solves of implicit time stepping,
-    sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt)."""
+    sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt).  fmg != 0 (the full-multigrid start of Solver) is refused here."""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)

@@ -615,7 +615,7 @@ int mg_source_is_bit_identical(void)
     if (!require_ready("mg_source_is_bit_identical")) return 0;
     return source_selfcheck() ? 1 : 0;
 }
-const char *mg_version(void) { return "mgpoisson-hip 0.2 (gfx950)"; }
+const char *mg_version(void) { return "mgpoisson-hip 0.2.1 (gfx950)"; }
 
 // ------------------------------------------------------------------ memory
 double *mg_alloc(size_t n)
@@ -1272,6 +1272,15 @@ void mg_restriction_table(int N, int M, int *lo, double *w) { build_restriction_
 void mg_prolongation_table(int N, int M, int axis, int *owner, double *w_hi, double *w_lo)
 {
     build_prolongation_table(N, M, axis, owner, w_hi, w_lo);
+}
+
+void mg_cubic_table(int N_src, int N_dst, int *base, double *w)
+{
+    if (N_src < 2 || N_dst < 2 || !base || !w) {
+        fail(MG_ERR_ARG, "mg_cubic_table: N_src = %d, N_dst = %d (at least 2 points each) or a NULL table", N_src, N_dst);
+        return;
+    }
+    build_cubic_table(N_src, N_dst, base, w);
 }
 
 // ------------------------------------------------------------------ synthetic data

@@ -178,6 +178,8 @@ const ProlongTable &prolong_table(int N, int M);
 // host-side builders (exact reference expressions)
 void build_restriction_table(int N, int M, int *lo, double *w);
 void build_prolongation_table(int N, int M, int axis, int *owner, double *w_hi, double *w_lo);
+// mg_cubic_table (include/mg_hip.h): long double from the integers, rounded once
+void build_cubic_table(int N_src, int N_dst, int *base, double *w);
 bool restriction_table_in_bounds(int N, int M, const int *lo);
 
 // getSource (src/MG_solver_CPU.cpp:468-493) for grid rows [row_lo, row_hi) evaluated on the host
@@ -418,6 +420,25 @@ void residual_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem
 void restrict_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const RestrictTable &t, int sign);
 void prolong_add_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const ProlongTable &t);
 void copy_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items);
+// full-multigrid start of the residual-tolerance solver (mg_fmg_kernels.hip, driven by mg_solve.cpp: fmg_start).
+// CubicTable: mg_cubic_table(N_src -> N_dst) in device memory, base[N_dst] and w[N_dst][4]; one table serves rows and columns.
+struct CubicTable {
+    int N_src = 0, N_dst = 0;
+    int *base = nullptr;
+    double *w = nullptr;
+};
+// the block tiling of prolong_cubic holds every source window of this table (checked on the host when the table is made)
+bool cubic_table_fits(int N_src, int N_dst, const int *base_host);
+// interior of Uf (N_dst x N_dst) = bicubic interpolation of Uc (N_src x N_src, rim included as data); the rim of Uf is not written
+void prolong_cubic(hipStream_t s, const CubicTable &t, const double *Uc, double *Uf);
+// the rim of an N x N array as four edges g[0..4N): row 0, row N-1, column 0, column N-1
+void rim_extract(hipStream_t s, int N, const double *U, double *g);
+// the edges of the coarse rim sampled from the fine edges with the 1-D table t (fine -> coarse), corners included
+void rim_sample(hipStream_t s, const CubicTable &t, const double *g_f, double *g_c);
+// rim of U = g; zero_interior: the interior is set to +0 (rim_only), otherwise it is not written
+void rim_fill(hipStream_t s, int N, const double *g, double *U, bool zero_interior);
+// *acc = 1 when gs_state[2] (the coarse solve ended at its cap) is set
+void flag_or(hipStream_t s, const int *gs_state, int *acc);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
@@ -440,7 +461,8 @@ struct SolveLevels {
     double *gs_err;   // may be nullptr
 };
 // one V(pre, post) cycle operator by operator (MG_SMOOTHER=simple); returns the kernel launches it enqueued
-int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0);
+// top: the level the cycle starts at, from the non-zero field U0 on the source F0 (both of size sizes[top]; 0: a solve's cycle)
+int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0, int top = 0);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

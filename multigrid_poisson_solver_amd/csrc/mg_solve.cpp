@@ -25,6 +25,12 @@ struct mg_solver {
     int *host_state = nullptr;               // pinned [4]
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_norm = nullptr;
     std::vector<double> history;
+    // full-multigrid start (o.fmg >= 1; nothing of it is allocated otherwise)
+    std::vector<double *> FF;                // per level l >= 1: F_l, the restricted source
+    std::vector<double *> G;                 // per level: the rim data g_l as four edges, 4*N_l
+    std::vector<k::CubicTable> up, down;     // per level l < last: N_{l+1} -> N_l (prolongation), N_l -> N_{l+1} (rim sampling)
+    int *fmg_capped = nullptr;               // device: some coarse solve of the pass ended at its cap
+    int *host_fmg_capped = nullptr;          // pinned
 };
 
 namespace {
@@ -58,6 +64,7 @@ bool opts_ok(const char *who, int N, double L, const mg_solve_opts &o)
     if (o.max_cycles < 0) { fail(MG_ERR_ARG, "%s: max_cycles = %d < 0", who, o.max_cycles); return false; }
     // (a negative shift is the indefinite Helmholtz problem: not what this smoother solves)
     if (!(o.shift >= 0.0) || !finite(o.shift)) { fail(MG_ERR_ARG, "%s: shift = %g must be finite and >= 0", who, o.shift); return false; }
+    if (o.fmg < 0 || o.fmg > 8) { fail(MG_ERR_ARG, "%s: fmg = %d outside [0, 8]", who, o.fmg); return false; }
     return true;
 }
 
@@ -72,6 +79,15 @@ void release(mg_solver *s)
     for (double *p : s->A) if (p) (void)hipFree(p);
     for (double *p : s->B) if (p) (void)hipFree(p);
     for (double *p : s->F) if (p) (void)hipFree(p);
+    for (double *p : s->FF) if (p) (void)hipFree(p);
+    for (double *p : s->G) if (p) (void)hipFree(p);
+    for (auto *v : {&s->up, &s->down})
+        for (k::CubicTable &t : *v) {
+            if (t.base) (void)hipFree(t.base);
+            if (t.w) (void)hipFree(t.w);
+        }
+    if (s->fmg_capped) (void)hipFree(s->fmg_capped);
+    if (s->host_fmg_capped) (void)hipHostFree(s->host_fmg_capped);
     if (s->part) (void)hipFree(s->part);
     if (s->dev_scal) (void)hipFree(s->dev_scal);
     if (s->gs_state) (void)hipFree(s->gs_state);
@@ -89,11 +105,29 @@ bool dev_alloc(T **p, size_t n)
     return MG_HIP(hipMalloc((void **)p, n * sizeof(T)));
 }
 
+// mg_cubic_table(N_src -> N_dst) in device memory; false when it does not fit prolong_cubic's tiling (needed: the
+// prolongation tables) or on a HIP error
+bool make_cubic_table(int N_src, int N_dst, bool for_prolongation, k::CubicTable *t)
+{
+    std::vector<int> base((size_t)N_dst);
+    std::vector<double> w(4 * (size_t)N_dst);
+    build_cubic_table(N_src, N_dst, base.data(), w.data());
+    if (for_prolongation && !k::cubic_table_fits(N_src, N_dst, base.data())) {
+        fail(MG_ERR_UNSUPPORTED, "cubic prolongation %d -> %d: the source windows do not fit the kernel's tiles", N_src, N_dst);
+        return false;
+    }
+    t->N_src = N_src;
+    t->N_dst = N_dst;
+    return dev_alloc(&t->base, base.size()) && dev_alloc(&t->w, w.size()) &&
+           MG_HIP(hipMemcpy(t->base, base.data(), base.size() * sizeof(int), hipMemcpyHostToDevice)) &&
+           MG_HIP(hipMemcpy(t->w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
 }  // namespace
 
-// one V(pre, post) cycle from the caller's U (level 0 keeps its guess; coarser levels start from zero), operator by
+// one V(pre, post) cycle from the caller's U (level `top` keeps its guess; coarser levels start from zero), operator by
 // operator: one launch per sweep (MG_SMOOTHER=simple, and the yardstick of the fused cycle below); the launches it enqueued
-int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0)
+int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0, int top)
 {
     const mg_solve_opts &o = *lv.o;
     const std::vector<int> &sizes = *lv.sizes;
@@ -101,14 +135,14 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
     int launches = 0;
     const std::vector<LevelConsts> &lc = *lv.lc;
     std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
-    for (int l = 0; l + 1 < nl; ++l) {
+    for (int l = top; l + 1 < nl; ++l) {
         const int N = sizes[l], M = sizes[l + 1];
         const double dx2 = lc[l].dx2, cw = lc[l].c;
         const k::Shifted &sh = lc[l].sh;
-        const double *F = l == 0 ? F0 : lv.F[l];
-        double *cur = l == 0 ? U0 : lv.A[l], *other = lv.B[l];
+        const double *F = l == top ? F0 : lv.F[l];
+        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
         int sweeps = o.pre;
-        if (l > 0) {   // memset(U, 0) (:256) folded into the first sweep
+        if (l > top) {   // memset(U, 0) (:256) folded into the first sweep
             k::wjacobi(st, N, dx2, cw, nullptr, F, cur, sh);
             ++launches;
             --sweeps;
@@ -130,11 +164,11 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
                              o.coarse_max_iters, lv.gs_state, lv.gs_err, lc[nl - 1].sh);
     ++launches;
     x[nl - 1] = lv.A[nl - 1];
-    for (int l = nl - 2; l >= 0; --l) {
+    for (int l = nl - 2; l >= top; --l) {
         const int N = sizes[l], Nc_l = sizes[l + 1];
         const double dx2 = lc[l].dx2, cw = lc[l].c;
         const k::Shifted &sh = lc[l].sh;
-        const double *F = l == 0 ? F0 : lv.F[l];
+        const double *F = l == top ? F0 : lv.F[l];
         double *cur = x[l], *other = y[l];
         // U = U + doProlongation(U_c) (:354, :368) into the free field
         k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
@@ -147,7 +181,7 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
         }
         x[l] = cur;
     }
-    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)sizes[0] * sizes[0] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
     return launches;
 }
 
@@ -157,19 +191,20 @@ namespace {
 // launch (all pre sweeps + the restricted residual) and one `1` launch (prolongation-add + all post sweeps) where the
 // transfer stages fuse (even N, nested tables), the sweeps in one launch and the transfers operator by operator elsewhere.
 // Level 0: the `-1` node reads the caller's U and stores into B[0]; U is free until the `1` node writes the result there.
-void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+// top > 0 (the full-multigrid start): the cycle starts at that level from the field U0 on the source F0 in the same way.
+void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top)
 {
     const mg_solve_opts &o = s->o;
     const int nl = (int)s->sizes.size();
     const std::vector<LevelConsts> &lc = s->lc;
     std::vector<double *> x(nl);   // per level: the field holding the pre-smoothed iterate, then the result
-    for (int l = 0; l + 1 < nl; ++l) {
+    for (int l = top; l + 1 < nl; ++l) {
         const int N = s->sizes[l], M = s->sizes[l + 1];
         const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
         const bool shifted = lc[l].sh.on;
-        const double *F = l == 0 ? F0 : s->F[l];
-        const double *in = l == 0 ? U0 : nullptr;   // coarser levels: memset(U, 0) (:256) folded into the first sweep
-        double *out = l == 0 ? s->B[0] : s->A[l], *scratch = l == 0 ? U0 : s->B[l];
+        const double *F = l == top ? F0 : s->F[l];
+        const double *in = l == top ? U0 : nullptr;   // coarser levels: memset(U, 0) (:256) folded into the first sweep
+        double *out = l == top ? s->B[l] : s->A[l], *scratch = l == top ? U0 : s->B[l];
         const RestrictTable &rt = restrict_table(N, M);
         if (k::stream_fusable(N) && rt.fusable) {
             k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .Fc = s->F[l + 1], .M = M,
@@ -186,12 +221,12 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
     k::gauss_seidel_relative(st, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol,
                              o.coarse_max_iters, s->gs_state, s->dev_scal + 2, lc[nl - 1].sh);
     x[nl - 1] = s->A[nl - 1];
-    for (int l = nl - 2; l >= 0; --l) {
+    for (int l = nl - 2; l >= top; --l) {
         const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
         const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
         const bool shifted = lc[l].sh.on;
-        const double *F = l == 0 ? F0 : s->F[l];
-        double *in = x[l], *out = l == 0 ? U0 : s->B[l];
+        const double *F = l == top ? F0 : s->F[l];
+        double *in = x[l], *out = l == top ? U0 : s->B[l];
         const ProlongTable &pt = prolong_table(Nc_l, N);
         if (k::stream_fusable(N) && pt.fusable) {
             k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.post, .d_sign = +1,
@@ -205,14 +240,51 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0)
             x[l] = in;
         }
     }
-    if (x[0] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[0], (size_t)s->N * s->N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)s->sizes[top] * s->sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
 
-void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
     if (ctx().smoother == SMOOTHER_SIMPLE)
-        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0);
-    else vcycle_fused(s, st, F0, U0);
+        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0,
+                                  top);
+    else vcycle_fused(s, st, F0, U0, top);
+}
+
+// The full-multigrid start (include/mg_hip.h, mg_solve_opts.fmg): the interior of U0 becomes the FMG guess, its rim is
+// read only.  u_l lives in A[l] (the caller's U at l = 0), which a cycle started at level l treats as a solve treats the
+// caller's U; A[l+1], B[l+1] and F[l+1] are free again by then (u_{l+1} has been interpolated).  Launches: nl-1 restrictions,
+// 1 + (nl-1) rim launches, 5 for the coarsest level, then per level the prolongation, and below level 0 the rim, fmg cycles
+// started there and the cap flag.
+void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
+{
+    const mg_solve_opts &o = s->o;
+    const int nl = (int)s->sizes.size(), last = nl - 1;
+    const std::vector<LevelConsts> &lc = s->lc;
+    (void)MG_HIP(hipMemsetAsync(s->fmg_capped, 0, sizeof(int), st));
+    for (int l = 0; l < last; ++l)
+        k::restrict_gather(st, s->sizes[l], l == 0 ? F0 : s->FF[l], s->sizes[l + 1], s->FF[l + 1],
+                           restrict_table(s->sizes[l], s->sizes[l + 1]), +1);
+    k::rim_extract(st, s->N, U0, s->G[0]);
+    for (int l = 0; l < last; ++l) k::rim_sample(st, s->down[l], s->G[l], s->G[l + 1]);
+    const int Nc = s->sizes[last];
+    k::rim_fill(st, Nc, s->G[last], s->B[last], true);
+    k::residual(st, Nc, lc[last].inv, s->B[last], s->FF[last], s->F[last], -1, lc[last].sh);
+    k::gauss_seidel_relative(st, Nc, lc[last].dx2, lc[last].inv, s->A[last], s->F[last], o.coarse_atol, o.coarse_rtol,
+                             o.coarse_max_iters, s->gs_state, s->dev_scal + 2, lc[last].sh);
+    k::rim_fill(st, Nc, s->G[last], s->A[last], false);
+    k::flag_or(st, s->gs_state, s->fmg_capped);
+    for (int l = last - 1; l >= 0; --l) {
+        double *u = l == 0 ? U0 : s->A[l];
+        k::prolong_cubic(st, s->up[l], s->A[l + 1], u);
+        if (l == 0) break;
+        k::rim_fill(st, s->sizes[l], s->G[l], u, false);
+        for (int c = 0; c < o.fmg; ++c) {
+            vcycle(s, st, s->FF[l], u, l);
+            k::flag_or(st, s->gs_state, s->fmg_capped);
+        }
+    }
+    (void)MG_HIP(hipMemcpyAsync(s->host_fmg_capped, s->fmg_capped, sizeof(int), hipMemcpyDeviceToHost, st));
 }
 
 // enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
@@ -266,6 +338,7 @@ void mg_solve_opts_default(mg_solve_opts *o)
     o->atol = 0.0;
     o->max_cycles = 50;
     o->shift = 0.0;
+    o->fmg = 0;
 }
 
 mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
@@ -308,6 +381,27 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
          MG_HIP(hipEventCreate(&s->ev_begin)) && MG_HIP(hipEventCreate(&s->ev_end)) &&
          MG_HIP(hipEventCreateWithFlags(&s->ev_norm, hipEventDisableTiming));
     if (ok && pool_poison_wanted()) poison_block(s->part, k::resnorm_partials(N) * sizeof(double));
+    if (ok && o.fmg >= 1) {   // the arrays and tables of the full-multigrid start
+        s->FF.assign(nl, nullptr);
+        s->G.assign(nl, nullptr);
+        s->up.resize(nl - 1);
+        s->down.resize(nl - 1);
+        for (int l = 0; l < nl && ok; ++l) {
+            const size_t n = (size_t)s->sizes[l] * s->sizes[l];
+            ok = dev_alloc(&s->G[l], 4 * (size_t)s->sizes[l]);
+            if (ok && l > 0) ok = dev_alloc(&s->FF[l], n);
+            if (ok && pool_poison_wanted()) {
+                poison_block(s->G[l], 4 * (size_t)s->sizes[l] * sizeof(double));
+                poison_block(s->FF[l], n * sizeof(double));
+            }
+        }
+        for (int l = 0; l + 1 < nl && ok; ++l)
+            ok = make_cubic_table(s->sizes[l + 1], s->sizes[l], true, &s->up[l]) &&
+                 make_cubic_table(s->sizes[l], s->sizes[l + 1], false, &s->down[l]);
+        ok = ok && dev_alloc(&s->fmg_capped, 1) &&
+             MG_HIP(hipHostMalloc((void **)&s->host_fmg_capped, sizeof(int), hipHostMallocDefault));
+        if (ok) *s->host_fmg_capped = 0;
+    }
     ok = ok && MG_HIP(hipStreamSynchronize(ctx().stream));   // (the fills ran on the engine's stream; a solve may run on another)
     ok = ok && MG_HIP(hipMemset(s->dev_scal, 0, 4 * sizeof(double))) && MG_HIP(hipMemset(s->gs_state, 0, 4 * sizeof(int)));
     if (!ok) {
@@ -351,6 +445,11 @@ int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_r
     r.res0 = res;
     s->history.push_back(res);
     const double tol = std::fmax(o.rtol * r.ref_norm, o.atol);
+    const bool fmg = o.fmg >= 1 && !(res <= tol);
+    if (fmg) {
+        fmg_start(s, st, F_dev, U_dev);
+        if (o.max_cycles == 0 && !read_back(s, st)) return finish(MG_ERR_HIP);   // (the loop's read-back otherwise)
+    }
     while (!(res <= tol) && r.cycles < o.max_cycles) {
         vcycle(s, st, F_dev, U_dev);
         norm(s, st, F_dev, U_dev, 0);
@@ -363,9 +462,31 @@ int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_r
     if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return finish(MG_ERR_HIP);
     float ms = 0.0f;
     if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) r.device_ms = ms;
+    if (fmg && *s->host_fmg_capped) r.coarse_capped = 1;
     r.res = res;
     r.converged = res <= tol ? 1 : 0;
     return finish(r.converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED);
+}
+
+void mg_prolongCubic(int N_src, const double *U_c, int N_dst, double *U_f)
+{
+    if (!require_ready("mg_prolongCubic")) return;
+    if (N_src < 3 || N_dst < 3 || !U_c || !U_f) {
+        fail(MG_ERR_ARG, "mg_prolongCubic: N_src = %d, N_dst = %d (at least 3 each) or a NULL array", N_src, N_dst);
+        return;
+    }
+    if (((uintptr_t)U_c | (uintptr_t)U_f) % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_prolongCubic: U_c and U_f must be 16-byte aligned");
+        return;
+    }
+    // (the solver keeps its tables from creation on; this entry point builds the one it needs and lets go of it)
+    k::CubicTable t;
+    if (make_cubic_table(N_src, N_dst, true, &t)) {
+        k::prolong_cubic(ctx().stream, t, U_c, U_f);
+        (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+    }
+    if (t.base) (void)hipFree(t.base);
+    if (t.w) (void)hipFree(t.w);
 }
 
 void mg_solver_destroy(mg_solver *s)

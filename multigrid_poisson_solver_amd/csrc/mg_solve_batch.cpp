@@ -230,6 +230,10 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
     mg_solve_opts_default(&o);
     if (opts) o = *opts;
     if (!solve_opts_ok("mg_batch_solver_create", N, L, o)) return nullptr;
+    if (o.fmg != 0) {   // (the batched full-multigrid pass is not built: refused, never ignored)
+        fail(MG_ERR_ARG, "mg_batch_solver_create: fmg = %d is not supported by the batched solver (use mg_solver_create)", o.fmg);
+        return nullptr;
+    }
     if (max_batch < 1 || max_batch > 65535) {
         fail(MG_ERR_ARG, "mg_batch_solver_create: max_batch = %d outside [1, 65535]", max_batch);
         return nullptr;

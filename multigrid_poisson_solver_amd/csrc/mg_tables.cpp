@@ -82,6 +82,36 @@ void build_prolongation_table(int N, int M, int axis, int *owner, double *w_hi, 
     }
 }
 
+// mg_cubic_table: destination point i sits at t = i*(N_src-1)/(N_dst-1) in source index units; the m = min(4, N_src) nodes
+// base .. base+m-1 with base = clamp(floor(t) - 1, 0, N_src - m) carry the Lagrange weights at t.  Every factor t - x_j is
+// the integer i*(N_src-1) - x_j*(N_dst-1) over N_dst-1, so a weight is ONE long double division of two exact integers
+// (the numerator below 2^63 for every size an int holds a grid of), rounded once more to fp64.
+void build_cubic_table(int N_src, int N_dst, int *base, double *w)
+{
+    const int m = N_src < 4 ? N_src : 4;
+    const long long P = N_src - 1, Q = N_dst > 1 ? N_dst - 1 : 1;
+    for (int i = 0; i < N_dst; ++i) {
+        const long long num = (long long)i * P;   // t = num / Q
+        long long b = num / Q - 1;
+        if (b > N_src - m) b = N_src - m;
+        if (b < 0) b = 0;
+        base[i] = (int)b;
+        for (int k = 0; k < 4; ++k) w[4 * (size_t)i + k] = 0.0;
+        for (int k = 0; k < m; ++k) {
+            long double n = 1.0L, d = 1.0L;
+            bool zero = false;
+            for (int j = 0; j < m; ++j) {
+                if (j == k) continue;
+                const long long f = num - (b + j) * Q;   // (t - x_j) * Q
+                if (f == 0) zero = true;
+                n *= (long double)f;
+                d *= (long double)((long long)(k - j) * Q);
+            }
+            w[4 * (size_t)i + k] = zero ? 0.0 : (double)(n / d);
+        }
+    }
+}
+
 namespace {
 template <typename T>
 T *upload(const std::vector<T> &v)
