@@ -468,5 +468,7 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 
 /* the building blocks of the full-multigrid start (mg_solve_opts.fmg): mg_cubic_table, mg_prolongCubic */
 #include "mg_fmg.h"
+/* time stepping of the heat equation over the solvers (theta-scheme): mg_heat_rhs, mg_heat_stepper_* */
+#include "mg_heat.h"
 
 #endif /* MG_HIP_H */

@@ -61,6 +61,16 @@ class BatchSolveStats(C.Structure):
     _fields_ = [("cycles", C.c_int), ("launches", C.c_int), ("device_ms", C.c_double)]
 
 
+class HeatOpts(C.Structure):
+    _fields_ = [("nu", C.c_double), ("dt", C.c_double), ("theta", C.c_double), ("solve", SolveOpts)]
+
+
+class HeatResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("steps", C.c_int), ("cycles", C.c_int), ("coarse_capped", C.c_int),
+                ("res", C.c_double), ("ref_norm", C.c_double), ("device_ms", C.c_double), ("n_steps", C.c_int),
+                ("cycles_per_step", C.POINTER(C.c_int))]
+
+
 MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED = 0, -1
 
 # every symbol include/mg_hip.h declares: name -> (restype, argtypes)
@@ -126,6 +136,17 @@ ABI_FMG = {
     "mg_cubic_table": (None, [_i, _i, _vp, _vp]), "mg_prolongCubic": (None, [_i, _vp, _i, _vp]),
 }
 
+# the symbols include/mg_heat.h declares (theta-scheme time stepping of the heat equation over the solvers); bound like
+# ABI_FMG: a library without them still loads, heat_rhs() / HeatStepper then raise
+ABI_HEAT = {
+    "mg_heat_opts_default": (None, [C.POINTER(HeatOpts)]),
+    "mg_heat_rhs": (None, [_i, _d, _d, _d, _d, _vp, _vp, _vp]),
+    "mg_heat_stepper_create": (_vp, [_i, _d, _i, C.POINTER(HeatOpts)]),
+    "mg_heat_stepper_step": (_i, [_vp, _i, _vp, _vp, _i, C.POINTER(HeatResult)]),
+    "mg_heat_stepper_sigma": (_d, [_vp]),
+    "mg_heat_stepper_destroy": (None, [_vp]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -183,7 +204,7 @@ def load_library(path=None):
         fn.restype, fn.argtypes = res, args
     if missing:
         raise MGError(f"{path} does not export: {missing}")
-    for name, (res, args) in ABI_FMG.items():
+    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -933,6 +954,22 @@ def _instances(X, what):
     raise MGError(f"{what}: expected [B, N, N], (N, N) or a list of (N, N) arrays, got shape {tuple(X.shape)}")
 
 
+def _staged(ts, share, nn, dev):
+    """device addresses of the torch tensors ts (nn doubles each), through a staging buffer of pitch nn + 1 when one of them
+    is not 16-byte aligned; share: every entry of ts is the same tensor.  Returns (addresses, buffer or None)."""
+    import torch
+    if all(t.data_ptr() % 16 == 0 for t in ts):
+        return [t.data_ptr() for t in ts], None
+    if share:
+        buf = torch.empty((1, nn + 1), dtype=torch.float64, device=dev)
+        buf[0, :nn].copy_(ts[0].reshape(-1))
+        return [buf.data_ptr()] * len(ts), buf
+    buf = torch.empty((len(ts), nn + 1), dtype=torch.float64, device=dev)
+    for i, t in enumerate(ts):
+        buf[i, :nn].copy_(t.reshape(-1))
+    return [buf[i].data_ptr() for i in range(len(ts))], buf
+
+
 class BatchSolver:
     """Batched residual-tolerance solver of include/mg_hip.h: up to max_batch problems of size N with one set of options
     (see solve_opts) in one call, every instance bit-identical to a Solver solve of it alone (U, history, cycles, status).
@@ -1004,21 +1041,8 @@ class BatchSolver:
         stream = torch.cuda.current_stream(dev)
         nn, B = N * N, len(Us)
 
-        def staged(ts, share):
-            """device addresses of ts, through a staging buffer of pitch N*N + 1 when one of them is not 16-byte aligned"""
-            if all(t.data_ptr() % 16 == 0 for t in ts):
-                return [t.data_ptr() for t in ts], None
-            if share:
-                buf = torch.empty((1, nn + 1), dtype=torch.float64, device=dev)
-                buf[0, :nn].copy_(ts[0].reshape(-1))
-                return [buf.data_ptr()] * len(ts), buf
-            buf = torch.empty((len(ts), nn + 1), dtype=torch.float64, device=dev)
-            for i, t in enumerate(ts):
-                buf[i, :nn].copy_(t.reshape(-1))
-            return [buf[i].data_ptr() for i in range(len(ts))], buf
-
-        F_ptrs, Fbuf = staged(Fs, shared)
-        U_ptrs, Ubuf = staged(Us, False)
+        F_ptrs, Fbuf = _staged(Fs, shared, nn, dev)
+        U_ptrs, Ubuf = _staged(Us, False, nn, dev)
         prev = _lib.mg_get_stream()
         _lib.mg_set_stream(stream.cuda_stream)
         try:
@@ -1097,3 +1121,166 @@ def solve_batched(F, U=None, L=1.0, **opts):
         return s.solve(F, U)
     finally:
         s.close()
+
+
+def _need_heat(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the heat stepper)")
+
+
+def heat_opts(nu=1.0, dt=1.0, theta=1.0, **opts):
+    """mg_heat_opts: the scheme's nu, dt, theta and the solve options of every step (solve_opts; shift must stay 0, the
+    stepper sets it to sigma = 1/(theta*nu*dt))."""
+    _need_heat("mg_heat_opts_default")
+    o = HeatOpts()
+    lib().mg_heat_opts_default(C.byref(o))
+    o.nu, o.dt, o.theta = float(nu), float(dt), float(theta)
+    o.solve = solve_opts(**opts)
+    return o
+
+
+def heat_rhs(N, L, nu, dt, theta, U, Q=None, F=None):
+    """mg_heat_rhs on DeviceGrids: F = -(sigma*U) - ((1 - theta)/theta)*Laplace_h(U) - Q/(theta*nu) on the interior,
+    sigma = 1/(theta*nu*dt), +0 on the rim -- the right-hand side of one theta-scheme step of u_t = nu*Laplace(u) + q as the
+    screened equation Laplace(u+) - sigma*u+ = F (include/mg_heat.h fixes the evaluation order; theta = 1 reads no
+    neighbour).  Q = None: no source.  F = None: a new DeviceGrid.  U and Q are read only; returns F."""
+    _need_heat("mg_heat_rhs")
+    if F is None:
+        F = DeviceGrid((N, N))
+    _lib.mg_heat_rhs(int(N), float(L), float(nu), float(dt), float(theta), U.ptr, Q.ptr if Q is not None else None, F.ptr)
+    _check()
+    return F
+
+
+class HeatStepper:
+    """Time stepper of include/mg_heat.h: the theta-scheme (theta = 1 backward Euler, 0.5 Crank-Nicolson) for
+    u_t = nu*Laplace(u) + q on the N x N grid of the solvers, Dirichlet values on the rim of U.  One step is one launch of
+    the right-hand-side kernel (heat_rhs) over all instances and one solve of Laplace(u+) - sigma*u+ = F with
+    sigma = 1/(theta*nu*dt) (the attribute .sigma), started from U itself -- u_old is the warm start.  k steps equal, bit for
+    bit, k times {heat_rhs, Solver(shift=sigma).solve} on each instance.  max_batch = 1 steps through a Solver (fmg=n works
+    as there), max_batch > 1 through a BatchSolver (which refuses fmg != 0).  The solve options are solve_opts's; shift is
+    the stepper's own and is refused here.  Everything is allocated at creation; step() allocates nothing on the device."""
+
+    def __init__(self, N, L=1.0, nu=1.0, dt=1.0, theta=1.0, max_batch=1, **opts):
+        self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
+        self.opts = heat_opts(nu, dt, theta, **opts)
+        _need_heat("mg_heat_stepper_create")
+        self._s = lib().mg_heat_stepper_create(self.N, self.L, self.max_batch, C.byref(self.opts))
+        if not self._s:
+            _check()
+            raise MGError("mg_heat_stepper_create returned NULL")
+        self.sigma = _lib.mg_heat_stepper_sigma(self._s)
+
+    def step_ptrs(self, U_ptrs, Q_ptrs=None, steps=1):
+        """U_ptrs: device addresses of N x N fp64 arrays (16-byte aligned, stepped in place); Q_ptrs: None, or as many
+        addresses (None entries: no source for that instance; addresses may repeat); on the engine stream.  Returns one
+        info dict per instance: status (0 converged, -1 not), converged, steps (done), cycles (summed), cycles_per_step,
+        coarse_capped, res and ref_norm of the last solve, device_ms of the call."""
+        n = len(U_ptrs)
+        if Q_ptrs is not None and len(Q_ptrs) != n:
+            raise MGError(f"{len(Q_ptrs)} Q pointers for {n} U pointers")
+        Ua = (C.c_void_p * max(n, 1))(*U_ptrs)
+        Qa = (C.c_void_p * max(n, 1))(*Q_ptrs) if Q_ptrs is not None else None
+        res = (HeatResult * max(n, 1))()
+        status = _lib.mg_heat_stepper_step(self._s, n, Ua, Qa, int(steps), res)
+        if status > 0:
+            _check()
+            raise MGError(f"mg_heat_stepper_step failed with status {status}")
+        return [dict(status=r.status, converged=r.status == MG_SOLVE_CONVERGED, steps=r.steps, cycles=r.cycles,
+                     cycles_per_step=[r.cycles_per_step[i] for i in range(r.n_steps)], coarse_capped=bool(r.coarse_capped),
+                     res=r.res, ref_norm=r.ref_norm, device_ms=r.device_ms) for r in res[:n]]
+
+    def step(self, U, Q=None, steps=1):
+        """Advance U by `steps` time steps.  U: what Solver.solve / BatchSolver.solve accept -- a numpy array, a DeviceGrid
+        or a float64 torch CUDA tensor (worked on in place, on torch.cuda.current_stream()), (N, N) or [B, N, N], or a list of
+        B (N, N) ones.  Q (the source q, constant over the call; None: none): the same, or one (N, N) array shared by every
+        instance (no copy).  Returns (U, infos) with one info dict per instance (step_ptrs); numpy input comes back as a new
+        numpy array of U's shape.  Torch instances that are not 16-byte aligned -- every odd instance of a contiguous
+        [B, N, N] tensor with N odd -- go through a staging buffer whose instance pitch is N*N + 1 doubles (copied in and
+        back on the same stream)."""
+        first = lambda X: X[0] if isinstance(X, (list, tuple)) else X
+        if _is_torch(first(U)) or (Q is not None and _is_torch(first(Q))):
+            return self._step_torch(U, Q, steps)
+        return self._step_host(U, Q, steps)
+
+    def _step_torch(self, U, Q, steps):
+        import torch
+        N = self.N
+        Us, _ = _instances(U, "U")
+        Qs, shared = _instances(Q, "Q") if Q is not None else (None, False)
+        if Qs is not None:
+            if shared:
+                Qs = Qs * len(Us)
+            if len(Qs) != len(Us):
+                raise MGError(f"{len(Qs)} Q instances for {len(Us)} U instances")
+        for name, ts in (("U", Us), ("Q", Qs or [])):
+            for t in ts:
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                        and t.is_contiguous()):
+                    raise MGError(f"{name}: expected contiguous float64 CUDA tensors of shape ({N}, {N})")
+        dev = Us[0].device
+        stream = torch.cuda.current_stream(dev)
+        nn = N * N
+        Q_ptrs, Qbuf = _staged(Qs, shared, nn, dev) if Qs is not None else (None, None)
+        U_ptrs, Ubuf = _staged(Us, False, nn, dev)
+        prev = _lib.mg_get_stream()
+        _lib.mg_set_stream(stream.cuda_stream)
+        try:
+            infos = self.step_ptrs(U_ptrs, Q_ptrs, steps)
+        finally:
+            _lib.mg_set_stream(prev)
+        if Ubuf is not None:
+            for i, u in enumerate(Us):
+                u.copy_(Ubuf[i, :nn].view(N, N))
+        del Qbuf
+        return U, infos
+
+    def _step_host(self, U, Q, steps):
+        N = self.N
+        keep = []
+
+        def dev(a, what):
+            if isinstance(a, DeviceGrid):
+                if a.shape != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        def split(X, what):
+            if isinstance(X, DeviceGrid):
+                return [X], True
+            return _instances(X if isinstance(X, (list, tuple)) else np.asarray(X), what)
+
+        Us, single = split(U, "U")
+        host_U = not all(isinstance(u, DeviceGrid) for u in Us)
+        Ud = [dev(u, "U") for u in Us]
+        Q_ptrs = None
+        if Q is not None:
+            Qs, shared = split(Q, "Q")
+            Qd = [dev(q, "Q") for q in Qs]
+            if shared:
+                Qd = Qd * len(Ud)
+            if len(Qd) != len(Ud):
+                raise MGError(f"{len(Qd)} Q instances for {len(Ud)} U instances")
+            Q_ptrs = [q.ptr for q in Qd]
+        infos = self.step_ptrs([u.ptr for u in Ud], Q_ptrs, steps)
+        if host_U:
+            out = [u.to_host() for u in Ud]
+            return (out[0] if single else np.stack(out)), infos
+        return U, infos
+
+    def close(self):
+        if getattr(self, "_s", None) and _initialised:
+            _lib.mg_heat_stepper_destroy(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -439,6 +439,16 @@ void rim_sample(hipStream_t s, const CubicTable &t, const double *g_f, double *g
 void rim_fill(hipStream_t s, int N, const double *g, double *U, bool zero_interior);
 // *acc = 1 when gs_state[2] (the coarse solve ended at its cap) is set
 void flag_or(hipStream_t s, const int *gs_state, int *acc);
+// right-hand side of a theta-scheme time step of the heat equation (mg_heat_kernels.hip, driven by mg_heat.cpp; the
+// expression and its order: include/mg_heat.h).  lap = false (theta == 1): the Laplacian term is left out, no neighbour is read
+struct HeatConsts {
+    double sigma = 0.0, beta = 0.0, gamma = 0.0, inv = 0.0;
+    bool lap = false;
+};
+// F = rhs(U, Q) (Q == nullptr: no source); the rim of F is +0, nothing else is written
+void heat_rhs(hipStream_t s, int N, const HeatConsts &c, const double *U, const double *Q, double *F);
+// the same on n instances in one launch: in = U, coarse = Q (may be null per instance), out = F
+void heat_rhs_batch(hipStream_t s, int n, int N, const HeatConsts &c, const NodeBatchItem *items);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
