@@ -470,5 +470,7 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 #include "mg_fmg.h"
 /* time stepping of the heat equation over the solvers (theta-scheme): mg_heat_rhs, mg_heat_stepper_* */
 #include "mg_heat.h"
+/* the solver with a variable coefficient, div(a grad U) - sigma*U = F: mg_solver_set_coefficient, mg_applyOperator, ... */
+#include "mg_varcoef.h"
 
 #endif /* MG_HIP_H */

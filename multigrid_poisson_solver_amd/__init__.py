@@ -147,6 +147,17 @@ ABI_HEAT = {
     "mg_heat_stepper_destroy": (None, [_vp]),
 }
 
+# the symbols include/mg_varcoef.h declares (the solver with a variable coefficient, div(a grad U) - sigma*U = F); bound like
+# ABI_FMG: a library without them still loads, Solver.set_coefficient() / applyOperator() / ... then raise
+ABI_VC = {
+    "mg_solver_set_coefficient": (_i, [_vp, _vp]),
+    "mg_solver_has_coefficient": (_i, [_vp]),
+    "mg_applyOperator": (None, [_i, _d, _d, _vp, _vp, _vp]),
+    "mg_coarsenCoefficient": (None, [_i, _vp, _i, _vp]),
+    "mg_sweepCoefficient": (None, [_i, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "mg_residualCoefficient": (None, [_i, _d, _d, _vp, _vp, _vp, _vp, _i]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -204,7 +215,7 @@ def load_library(path=None):
         fn.restype, fn.argtypes = res, args
     if missing:
         raise MGError(f"{path} does not export: {missing}")
-    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()):
+    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -542,6 +553,37 @@ def prolongCubic(N_src, U_c, N_dst, U_f):
     _check()
 
 
+def _need_vc(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the variable-coefficient solver)")
+    return getattr(_lib, name)
+
+
+def applyOperator(N, L, shift, a, U, out):
+    """mg_applyOperator on DeviceGrids: out = inv*b(U) of div(a grad U) - shift*U inside, +0 on the rim (include/mg_varcoef.h);
+    a = None is a = 1, the constant operator."""
+    _need_vc("mg_applyOperator")(N, L, shift, a.ptr if a is not None else None, U.ptr, out.ptr)
+    _check()
+
+
+def coarsenCoefficient(N, a_f, M, a_c):
+    """mg_coarsenCoefficient on DeviceGrids: the nodal coefficient a_f (N x N) sampled at the M x M coarse points, rim included."""
+    _need_vc("mg_coarsenCoefficient")(N, a_f.ptr, M, a_c.ptr)
+    _check()
+
+
+def sweepCoefficient(N, L, shift, omega, a, U_in, F, U_out):
+    """Test hook (include/mg_varcoef.h).  mg_sweepCoefficient on DeviceGrids: one weighted Jacobi sweep of the variable-coefficient operator (U_in = None: from zero)."""
+    _need_vc("mg_sweepCoefficient")(N, L, shift, omega, a.ptr, U_in.ptr if U_in is not None else None, F.ptr, U_out.ptr)
+    _check()
+
+
+def residualCoefficient(N, L, shift, a, U, F, D, sign=1):
+    """Test hook (include/mg_varcoef.h).  mg_residualCoefficient on DeviceGrids: D = sign*(inv*b(U) - F) inside, sign*0 on the rim."""
+    _need_vc("mg_residualCoefficient")(N, L, shift, a.ptr, U.ptr, F.ptr, D.ptr, sign)
+    _check()
+
+
 def profile_begin(min_N=0, every=1):
     lib().mg_profile_sample(int(every))
     lib().mg_profile_begin(int(min_N))
@@ -851,15 +893,66 @@ class Solver:
     relative coarse target, on a caller's F and Dirichlet rim, until ||F - AU||_2 <= max(rtol*||F||_2, atol).  Every
     level array is allocated here; solve() allocates nothing on the device.  With shift=sigma > 0 the operator is
     A U = Laplace(U) - sigma*U (solve_opts); an implicit time step has sigma = 1/(nu*dt), F = -u_old/(nu*dt).
-    fmg=n (1..8) starts every solve from a full-multigrid guess instead of U's interior (solve_opts)."""
+    fmg=n (1..8) starts every solve from a full-multigrid guess instead of U's interior (solve_opts).
+    coef=a (or set_coefficient(a)) solves div(a grad U) - sigma*U = F, a > 0 given at the grid points:
+        s = Solver(N, L, shift=sigma); s.set_coefficient(a); U, info = s.solve(F, U0); s.set_coefficient(None)"""
 
-    def __init__(self, N, L=1.0, **opts):
+    def __init__(self, N, L=1.0, coef=None, **opts):
         self.N, self.L = int(N), float(L)
         self.opts = solve_opts(**opts)
         self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
         if not self._s:
             _check()
             raise MGError("mg_solver_create returned NULL")
+        if coef is not None:
+            try:
+                self.set_coefficient(coef)
+            except Exception:
+                self.close()
+                raise
+
+    def set_coefficient(self, a):
+        """a: N x N values of the coefficient at the grid points, rim included, finite and > 0 (numpy array, DeviceGrid or
+        float64 torch CUDA tensor, which is read on torch.cuda.current_stream()); None: back to the constant solver.
+        Faces average their two nodes (aE = 0.5*(a[p] + a[p+1]), ...), coarse levels are rediscretised from the sampled a
+        (include/mg_varcoef.h); a == 1 everywhere is the solver without a coefficient, bit for bit.  a is copied: it may be
+        freed after the call.  A refused coefficient (MGError) leaves the solver as it was."""
+        fn = _need_vc("mg_solver_set_coefficient")
+        N = self.N
+        if a is None:
+            fn(self._s, None)
+            _check()
+            return
+        if _is_torch(a):
+            import torch
+            if not (a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (N, N) and a.is_contiguous()):
+                raise MGError(f"coef: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(a.device).cuda_stream)
+            try:
+                status = fn(self._s, a.data_ptr())
+            finally:
+                _lib.mg_set_stream(prev)
+        elif hasattr(a, "ptr") and hasattr(a, "shape"):
+            if tuple(a.shape) != (N, N):
+                raise MGError(f"coef: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+            status = fn(self._s, a.ptr)
+        else:
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"coef: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            try:
+                status = fn(self._s, g.ptr)
+            finally:
+                g.free()
+        if status:
+            _check()
+            raise MGError(f"mg_solver_set_coefficient failed with status {status}")
+
+    @property
+    def has_coefficient(self):
+        return bool(_need_vc("mg_solver_has_coefficient")(self._s))
 
     def solve_ptr(self, F_ptr, U_ptr):
         """F_ptr, U_ptr: device addresses of N x N fp64 arrays (U in/out), on the engine stream."""
@@ -934,7 +1027,8 @@ def solve(F, U=None, L=1.0, **opts):
     tolerance; returns (U, info).  See Solver, and solve_opts for the defaults (the default rtol of 1e-10 is below the
     rounding floor of large grids: about 8e-10 at N = 8192).  shift=sigma > 0 solves Laplace(U) - sigma*U = F, the
     equation of an implicit time step: sigma = 1/(nu*dt), F = -u_old/(nu*dt).  fmg=1 starts from a full-multigrid guess
-    (U then only supplies the rim)."""
+    (U then only supplies the rim).  coef=a (N x N, > 0, at the grid points) solves div(a grad U) - sigma*U = F with faces
+    averaging their two nodes (Solver.set_coefficient); a == 1 everywhere is the solve without coef, bit for bit."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:

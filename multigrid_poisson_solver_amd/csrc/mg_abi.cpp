@@ -615,7 +615,7 @@ int mg_source_is_bit_identical(void)
     if (!require_ready("mg_source_is_bit_identical")) return 0;
     return source_selfcheck() ? 1 : 0;
 }
-const char *mg_version(void) { return "mgpoisson-hip 0.2.1 (gfx950)"; }
+const char *mg_version(void) { return "mgpoisson-hip 0.2.2 (gfx950)"; }
 
 // ------------------------------------------------------------------ memory
 double *mg_alloc(size_t n)

@@ -449,6 +449,25 @@ struct HeatConsts {
 void heat_rhs(hipStream_t s, int N, const HeatConsts &c, const double *U, const double *Q, double *F);
 // the same on n instances in one launch: in = U, coarse = Q (may be null per instance), out = F
 void heat_rhs_batch(hipStream_t s, int n, int N, const HeatConsts &c, const NodeBatchItem *items);
+// the residual-tolerance solver with a variable coefficient (mg_varcoef_kernels.hip, driven by mg_solve.cpp; the expressions
+// and their order: include/mg_varcoef.h).  A: the level's nodal coefficient, sd = shift*dx2 of the level.
+// one sweep U = U_old + omega*q*(b(U_old) - dx2*F), q = 1/d formed per point (in == nullptr: from the zero field)
+void wjacobi_vc(hipStream_t s, int N, double dx2, double sd, double omega, const double *A, const double *in, const double *F,
+                double *out);
+// D = sign * (inv*b(U) - F), rim sign*0
+void residual_vc(hipStream_t s, int N, double inv, double sd, const double *A, const double *U, const double *F, double *D, int sign);
+// out = inv*b(U), rim +0 (A == nullptr: a = 1)
+void apply_vc(hipStream_t s, int N, double inv, double sd, const double *A, const double *U, double *out);
+// *out = sqrt(sum over interior points of (inv*b(U) - F)^2) in the partition and order of resnorm (part: resnorm_partials(N))
+void resnorm_vc(hipStream_t s, int N, double inv, double sd, const double *A, const double *U, const double *F, double *part,
+                double *out);
+// gauss_seidel_relative with the variable operator (N < GS_RELATIVE_MAX_N; the same LDS request)
+void gauss_seidel_relative_vc(hipStream_t s, int N, double h2, double inv, double sd, const double *A, double *U, const double *F,
+                              double atol, double rtol, int max_iters, int *state, double *err_out);
+// Ac (M x M) = the nodal coefficient Af (N x N) sampled with t = restrict_table(N, M), rim included, clamped to its samples
+void coef_coarsen(hipStream_t s, int N, const double *Af, int M, double *Ac, const RestrictTable &t);
+// *flag = 1 when a value of A[0..n) is not finite or not > 0 (the caller zeroes the flag)
+void coef_check(hipStream_t s, const double *A, size_t n, int *flag);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
@@ -473,6 +492,9 @@ struct SolveLevels {
 // one V(pre, post) cycle operator by operator (MG_SMOOTHER=simple); returns the kernel launches it enqueued
 // top: the level the cycle starts at, from the non-zero field U0 on the source F0 (both of size sizes[top]; 0: a solve's cycle)
 int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0, int top = 0);
+// the same cycle -- node order, field ping-pong, launch count -- with the variable-coefficient kernels (include/mg_varcoef.h);
+// coef[l]: the nodal coefficient of level l
+int solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<double *> &coef, const double *F0, double *U0, int top = 0);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

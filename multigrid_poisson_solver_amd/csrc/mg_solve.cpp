@@ -5,6 +5,7 @@
 // of the cycle-file interpreter (mg_cycle.cpp): every level array is allocated at creation, a solve allocates nothing.
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "mg_internal.h"
@@ -31,6 +32,11 @@ struct mg_solver {
     std::vector<k::CubicTable> up, down;     // per level l < last: N_{l+1} -> N_l (prolongation), N_l -> N_{l+1} (rim sampling)
     int *fmg_capped = nullptr;               // device: some coarse solve of the pass ended at its cap
     int *host_fmg_capped = nullptr;          // pinned
+    // variable coefficient (include/mg_varcoef.h; nothing of it is allocated before the first mg_solver_set_coefficient)
+    std::vector<double *> coef;              // per level: the nodal coefficient a_l
+    int *coef_flag = nullptr;                // device: the check found a value that is not finite or not > 0
+    int *host_coef_flag = nullptr;           // pinned
+    bool coef_set = false;
 };
 
 namespace {
@@ -86,6 +92,9 @@ void release(mg_solver *s)
             if (t.base) (void)hipFree(t.base);
             if (t.w) (void)hipFree(t.w);
         }
+    for (double *p : s->coef) if (p) (void)hipFree(p);
+    if (s->coef_flag) (void)hipFree(s->coef_flag);
+    if (s->host_coef_flag) (void)hipHostFree(s->host_coef_flag);
     if (s->fmg_capped) (void)hipFree(s->fmg_capped);
     if (s->host_fmg_capped) (void)hipHostFree(s->host_fmg_capped);
     if (s->part) (void)hipFree(s->part);
@@ -185,6 +194,62 @@ int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double 
     return launches;
 }
 
+// the cycle above with the variable-coefficient kernels (include/mg_varcoef.h): the same node order, the same field
+// ping-pong and the same launches, each constant kernel replaced by its `_vc` form on the level's coefficient coef[l]
+int mg::solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<double *> &coef, const double *F0, double *U0, int top)
+{
+    const mg_solve_opts &o = *lv.o;
+    const std::vector<int> &sizes = *lv.sizes;
+    const int nl = (int)sizes.size();
+    int launches = 0;
+    const std::vector<LevelConsts> &lc = *lv.lc;
+    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
+    auto sd = [&](int l) { return o.shift * lc[l].dx2; };   // (the product solve_level_consts forms)
+    for (int l = top; l + 1 < nl; ++l) {
+        const int N = sizes[l], M = sizes[l + 1];
+        const double dx2 = lc[l].dx2;
+        const double *F = l == top ? F0 : lv.F[l];
+        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
+        int sweeps = o.pre;
+        if (l > top) {
+            k::wjacobi_vc(st, N, dx2, sd(l), o.omega, coef[l], nullptr, F, cur);
+            ++launches;
+            --sweeps;
+        }
+        for (int i = 0; i < sweeps; ++i) {
+            k::wjacobi_vc(st, N, dx2, sd(l), o.omega, coef[l], cur, F, other);
+            ++launches;
+            std::swap(cur, other);
+        }
+        k::residual_vc(st, N, lc[l].inv, sd(l), coef[l], cur, F, other, -1);
+        k::restrict_gather(st, N, other, M, lv.F[l + 1], restrict_table(N, M), +1);
+        launches += 2;
+        x[l] = cur;
+        y[l] = other;
+    }
+    const int last = nl - 1, Nc = sizes[last];
+    k::gauss_seidel_relative_vc(st, Nc, lc[last].dx2, lc[last].inv, sd(last), coef[last], lv.A[last], lv.F[last], o.coarse_atol,
+                                o.coarse_rtol, o.coarse_max_iters, lv.gs_state, lv.gs_err);
+    ++launches;
+    x[last] = lv.A[last];
+    for (int l = nl - 2; l >= top; --l) {
+        const int N = sizes[l], Nc_l = sizes[l + 1];
+        const double *F = l == top ? F0 : lv.F[l];
+        double *cur = x[l], *other = y[l];
+        k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
+        ++launches;
+        std::swap(cur, other);
+        for (int i = 0; i < o.post; ++i) {
+            k::wjacobi_vc(st, N, lc[l].dx2, sd(l), o.omega, coef[l], cur, F, other);
+            ++launches;
+            std::swap(cur, other);
+        }
+        x[l] = cur;
+    }
+    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return launches;
+}
+
 namespace {
 
 // the same cycle through the fused nodes of the streaming smoother (its weighted instantiations): per level one `-1`
@@ -245,7 +310,10 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0, in
 
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
-    if (ctx().smoother == SMOOTHER_SIMPLE)
+    if (s->coef_set)   // (whatever mg_set_smoother says)
+        (void)solve_vcycle_vc(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, s->coef,
+                              F0, U0, top);
+    else if (ctx().smoother == SMOOTHER_SIMPLE)
         (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0,
                                   top);
     else vcycle_fused(s, st, F0, U0, top);
@@ -290,7 +358,9 @@ void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 // enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
-    k::resnorm(st, s->N, s->lc[0].inv, U0, F0, s->part, s->dev_scal + slot, s->lc[0].sh);
+    // (the reference norm ||F|| has no operator in it)
+    if (s->coef_set && U0) k::resnorm_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->part, s->dev_scal + slot);
+    else k::resnorm(st, s->N, s->lc[0].inv, U0, F0, s->part, s->dev_scal + slot, s->lc[0].sh);
 }
 
 bool read_back(mg_solver *s, hipStream_t st)
@@ -487,6 +557,127 @@ void mg_prolongCubic(int N_src, const double *U_c, int N_dst, double *U_f)
     }
     if (t.base) (void)hipFree(t.base);
     if (t.w) (void)hipFree(t.w);
+}
+
+// ------------------------------------------------------------------ variable coefficient (include/mg_varcoef.h)
+int mg_solver_set_coefficient(mg_solver *s, const double *a_dev)
+{
+    if (!require_ready("mg_solver_set_coefficient")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_solver_set_coefficient: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (!a_dev) {   // back to the constant-coefficient solver (the level storage stays for the next coefficient)
+        s->coef_set = false;
+        return MG_OK;
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_coefficient: the solver was created with fmg = %d; the full-multigrid start is not "
+                                 "built for a variable coefficient", s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if ((uintptr_t)a_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_solver_set_coefficient: a must be 16-byte aligned");
+        return MG_ERR_ARG;
+    }
+    const hipStream_t st = ctx().stream;
+    const int nl = (int)s->sizes.size();
+    if (s->coef.empty()) {   // the first coefficient: level storage, about 4/3 N^2 doubles
+        s->coef.assign(nl, nullptr);
+        bool ok = dev_alloc(&s->coef_flag, 1) && MG_HIP(hipHostMalloc((void **)&s->host_coef_flag, sizeof(int), hipHostMallocDefault));
+        for (int l = 0; l < nl && ok; ++l) ok = dev_alloc(&s->coef[l], (size_t)s->sizes[l] * s->sizes[l]);
+        if (!ok) {   // (release() frees what was allocated; the next call starts over)
+            for (double *&p : s->coef) if (p) { (void)hipFree(p); p = nullptr; }
+            s->coef.clear();
+            if (s->coef_flag) { (void)hipFree(s->coef_flag); s->coef_flag = nullptr; }
+            if (s->host_coef_flag) { (void)hipHostFree(s->host_coef_flag); s->host_coef_flag = nullptr; }
+            return MG_ERR_HIP;
+        }
+    }
+    // the check comes first and reads the CALLER's array: a refused coefficient leaves the solver's own untouched
+    const size_t n0 = (size_t)s->N * s->N;
+    if (!MG_HIP(hipMemsetAsync(s->coef_flag, 0, sizeof(int), st))) return MG_ERR_HIP;
+    k::coef_check(st, a_dev, n0, s->coef_flag);
+    if (!MG_HIP(hipMemcpyAsync(s->host_coef_flag, s->coef_flag, sizeof(int), hipMemcpyDeviceToHost, st)) ||
+        !MG_HIP(hipStreamSynchronize(st)))
+        return MG_ERR_HIP;
+    if (*s->host_coef_flag) {
+        fail(MG_ERR_ARG, "mg_solver_set_coefficient: every value of a must be finite and > 0");
+        return MG_ERR_ARG;
+    }
+    // from here on the level storage is overwritten: until it is whole again the solver has NO coefficient, so a HIP error
+    // below leaves the constant-coefficient solver, never one on a half-replaced coefficient
+    s->coef_set = false;
+    if (!MG_HIP(hipMemcpyAsync(s->coef[0], a_dev, n0 * sizeof(double), hipMemcpyDeviceToDevice, st))) return MG_ERR_HIP;
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen(st, s->sizes[l], s->coef[l], s->sizes[l + 1], s->coef[l + 1], restrict_table(s->sizes[l], s->sizes[l + 1]));
+    if (!MG_HIP(hipStreamSynchronize(st))) return MG_ERR_HIP;   // (the caller may free a, or solve on another stream)
+    s->coef_set = true;
+    return MG_OK;
+}
+
+int mg_solver_has_coefficient(const mg_solver *s) { return s && s->coef_set ? 1 : 0; }
+
+namespace {
+bool vc_args_ok(const char *who, int N, double L, double shift, std::initializer_list<const void *> arrays)
+{
+    if (N < 3 || !(L > 0.0) || !finite(L) || !(shift >= 0.0) || !finite(shift)) {
+        fail(MG_ERR_ARG, "%s: N = %d (at least 3), L = %g (positive, finite), shift = %g (finite, >= 0)", who, N, L, shift);
+        return false;
+    }
+    for (const void *p : arrays)
+        if (!p || (uintptr_t)p % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: a NULL or not 16-byte aligned array", who);
+            return false;
+        }
+    return true;
+}
+}  // namespace
+
+void mg_applyOperator(int N, double L, double shift, const double *a_dev, const double *U, double *out)
+{
+    if (!require_ready("mg_applyOperator") || !vc_args_ok("mg_applyOperator", N, L, shift, {U, out})) return;
+    if ((uintptr_t)a_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_applyOperator: a must be 16-byte aligned");
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    k::apply_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_coarsenCoefficient(int N, const double *a_f, int M, double *a_c)
+{
+    if (!require_ready("mg_coarsenCoefficient")) return;
+    if (N < 3 || M < 2 || !a_f || !a_c) {
+        fail(MG_ERR_ARG, "mg_coarsenCoefficient: N = %d (at least 3), M = %d (at least 2) or a NULL array", N, M);
+        return;
+    }
+    const RestrictTable &t = restrict_table(N, M);   // (refuses a table that leaves the fine grid)
+    if (!t.lo) return;
+    k::coef_coarsen(ctx().stream, N, a_f, M, a_c, t);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_sweepCoefficient(int N, double L, double shift, double omega, const double *a_dev, const double *U_in, const double *F,
+                         double *U_out)
+{
+    if (!require_ready("mg_sweepCoefficient") || !vc_args_ok("mg_sweepCoefficient", N, L, shift, {a_dev, F, U_out})) return;
+    if ((uintptr_t)U_in % 16 != 0 || !(omega > 0.0 && omega <= 1.0)) {
+        fail(MG_ERR_ARG, "mg_sweepCoefficient: U_in must be 16-byte aligned, omega = %g inside (0, 1]", omega);
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    k::wjacobi_vc(ctx().stream, N, dx2, shift * dx2, omega, a_dev, U_in, F, U_out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, const double *U, const double *F, double *D, int sign)
+{
+    if (!require_ready("mg_residualCoefficient") || !vc_args_ok("mg_residualCoefficient", N, L, shift, {a_dev, U, F, D})) return;
+    const double dx2 = spacing_sq(N, L);
+    k::residual_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, F, D, sign < 0 ? -1 : +1);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
 }
 
 void mg_solver_destroy(mg_solver *s)
