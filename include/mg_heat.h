@@ -66,8 +66,12 @@ mg_heat_stepper *mg_heat_stepper_create(int N, double L, int max_batch, const mg
  * is the solver's documented behaviour.  k steps give, bit for bit, k times {mg_heat_rhs, mg_solver_solve with shift =
  * mg_heat_stepper_sigma} on each instance, whatever the others are.  Q_dev: NULL (no source), or n device pointers of which
  * any may be NULL and any may repeat.  If an instance ends a step not converged, that step still finishes for every instance
- * and the call stops there with MG_SOLVE_NOT_CONVERGED; out[i].steps tells the steps done.  Time-dependent rims or sources
- * are the caller's loop of steps = 1 calls.  Allocates nothing on the device.  Refused with MG_ERR_ARG before anything is
+ * and the call stops there with MG_SOLVE_NOT_CONVERGED; out[i].steps tells the steps done.  A time-dependent source is
+ * the caller's loop of steps = 1 calls.  A time-dependent rim written into U before each such call is exact only for
+ * theta = 1, whose right-hand side reads no neighbour: for theta < 1 the right-hand side takes Lap_h of u_old next to the rim,
+ * and a rim already at the new time puts two time levels into it (an error of first order in the rim's change, not the
+ * theta-scheme).  There the caller runs mg_heat_rhs on the old field with its old rim, then sets the new rim, then solves
+ * with mg_solver_solve at shift = mg_heat_stepper_sigma (tests/test_exact_gpu.py, test_heat_moving_rim).  Allocates nothing on the device.  Refused with MG_ERR_ARG before anything is
  * enqueued: steps < 1, n outside [1, max_batch], a NULL or not 16-byte aligned U (or non-NULL Q), a U that overlaps another
  * U or a Q.  out: n results.  Returns MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED or an error code (> 0). */
 int  mg_heat_stepper_step(mg_heat_stepper *s, int n, double *const *U_dev, const double *const *Q_dev, int steps,

@@ -1291,7 +1291,10 @@ class HeatStepper:
         instance (no copy).  Returns (U, infos) with one info dict per instance (step_ptrs); numpy input comes back as a new
         numpy array of U's shape.  Torch instances that are not 16-byte aligned -- every odd instance of a contiguous
         [B, N, N] tensor with N odd -- go through a staging buffer whose instance pitch is N*N + 1 doubles (copied in and
-        back on the same stream)."""
+        back on the same stream).
+        A time-dependent rim: writing the new rim into U before each steps=1 call is exact only for theta = 1, whose
+        right-hand side reads no neighbour.  For theta < 1 run heat_rhs on the old field with its old rim, then set the new
+        rim, then solve with Solver(shift=self.sigma) (include/mg_heat.h, mg_heat_stepper_step)."""
         first = lambda X: X[0] if isinstance(X, (list, tuple)) else X
         if _is_torch(first(U)) or (Q is not None and _is_torch(first(Q))):
             return self._step_torch(U, Q, steps)
