@@ -472,5 +472,7 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 #include "mg_heat.h"
 /* the solver with a variable coefficient, div(a grad U) - sigma*U = F: mg_solver_set_coefficient, mg_applyOperator, ... */
 #include "mg_varcoef.h"
+/* the heat stepper with a variable coefficient, u_t = nu*div(a grad u) + q: mg_heat_rhs_coef, mg_heat_stepper_set_coefficient */
+#include "mg_heat_vc.h"
 
 #endif /* MG_HIP_H */

@@ -158,6 +158,14 @@ ABI_VC = {
     "mg_residualCoefficient": (None, [_i, _d, _d, _vp, _vp, _vp, _vp, _i]),
 }
 
+# the symbols include/mg_heat_vc.h declares (the heat stepper with a variable coefficient, u_t = nu*div(a grad u) + q); bound
+# like ABI_FMG: a library without them still loads, heat_rhs_coef() / HeatStepper.set_coefficient() then raise
+ABI_HEAT_VC = {
+    "mg_heat_rhs_coef": (None, [_i, _d, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "mg_heat_stepper_set_coefficient": (_i, [_vp, _vp]),
+    "mg_heat_stepper_has_coefficient": (_i, [_vp]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -215,7 +223,7 @@ def load_library(path=None):
         fn.restype, fn.argtypes = res, args
     if missing:
         raise MGError(f"{path} does not export: {missing}")
-    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()):
+    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -888,6 +896,42 @@ def solve_opts(**opts):
     return o
 
 
+def _set_coefficient(fn, handle, N, a):
+    """The argument handling of Solver.set_coefficient and HeatStepper.set_coefficient: fn(handle, device address of a) with a
+    an N x N numpy array (uploaded for the call), a DeviceGrid, or a float64 torch CUDA tensor (read on
+    torch.cuda.current_stream()); None takes the coefficient away.  A refusal raises MGError."""
+    if a is None:
+        fn(handle, None)
+        _check()
+        return
+    if _is_torch(a):
+        import torch
+        if not (a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (N, N) and a.is_contiguous()):
+            raise MGError(f"coef: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+        prev = _lib.mg_get_stream()
+        _lib.mg_set_stream(torch.cuda.current_stream(a.device).cuda_stream)
+        try:
+            status = fn(handle, a.data_ptr())
+        finally:
+            _lib.mg_set_stream(prev)
+    elif hasattr(a, "ptr") and hasattr(a, "shape"):
+        if tuple(a.shape) != (N, N):
+            raise MGError(f"coef: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+        status = fn(handle, a.ptr)
+    else:
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (N, N):
+            raise MGError(f"coef: array of shape {a.shape}, expected ({N}, {N})")
+        g = DeviceGrid.from_host(a)
+        try:
+            status = fn(handle, g.ptr)
+        finally:
+            g.free()
+    if status:
+        _check()
+        raise MGError(f"{fn.__name__} failed with status {status}")
+
+
 class Solver:
     """Residual-tolerance solver of include/mg_hip.h: V(pre, post) cycles with a weighted Jacobi smoother and a
     relative coarse target, on a caller's F and Dirichlet rim, until ||F - AU||_2 <= max(rtol*||F||_2, atol).  Every
@@ -917,38 +961,7 @@ class Solver:
         Faces average their two nodes (aE = 0.5*(a[p] + a[p+1]), ...), coarse levels are rediscretised from the sampled a
         (include/mg_varcoef.h); a == 1 everywhere is the solver without a coefficient, bit for bit.  a is copied: it may be
         freed after the call.  A refused coefficient (MGError) leaves the solver as it was."""
-        fn = _need_vc("mg_solver_set_coefficient")
-        N = self.N
-        if a is None:
-            fn(self._s, None)
-            _check()
-            return
-        if _is_torch(a):
-            import torch
-            if not (a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (N, N) and a.is_contiguous()):
-                raise MGError(f"coef: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
-            prev = _lib.mg_get_stream()
-            _lib.mg_set_stream(torch.cuda.current_stream(a.device).cuda_stream)
-            try:
-                status = fn(self._s, a.data_ptr())
-            finally:
-                _lib.mg_set_stream(prev)
-        elif hasattr(a, "ptr") and hasattr(a, "shape"):
-            if tuple(a.shape) != (N, N):
-                raise MGError(f"coef: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
-            status = fn(self._s, a.ptr)
-        else:
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape != (N, N):
-                raise MGError(f"coef: array of shape {a.shape}, expected ({N}, {N})")
-            g = DeviceGrid.from_host(a)
-            try:
-                status = fn(self._s, g.ptr)
-            finally:
-                g.free()
-        if status:
-            _check()
-            raise MGError(f"mg_solver_set_coefficient failed with status {status}")
+        _set_coefficient(_need_vc("mg_solver_set_coefficient"), self._s, self.N, a)
 
     @property
     def has_coefficient(self):
@@ -1222,6 +1235,12 @@ def _need_heat(name):
         raise MGError(f"{LIB_PATH} does not export {name} (a build without the heat stepper)")
 
 
+def _need_heat_vc(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the heat stepper's variable coefficient)")
+    return getattr(_lib, name)
+
+
 def heat_opts(nu=1.0, dt=1.0, theta=1.0, **opts):
     """mg_heat_opts: the scheme's nu, dt, theta and the solve options of every step (solve_opts; shift must stay 0, the
     stepper sets it to sigma = 1/(theta*nu*dt))."""
@@ -1246,6 +1265,22 @@ def heat_rhs(N, L, nu, dt, theta, U, Q=None, F=None):
     return F
 
 
+def heat_rhs_coef(N, L, nu, dt, theta, a, U, Q=None, F=None):
+    """mg_heat_rhs_coef on DeviceGrids: the right-hand side of one theta-scheme step of u_t = nu*div(a grad u) + q as the
+    equation div(a grad u+) - sigma*u+ = F of Solver(shift=sigma, coef=a): F = -(sigma*U) - ((1 - theta)/theta)*A_h(U)
+    - Q/(theta*nu) on the interior, A_h the operator of applyOperator at shift 0, +0 on the rim (include/mg_heat_vc.h fixes the
+    evaluation order).  a = None is a = 1, exactly heat_rhs; a == 1 everywhere gives heat_rhs's bits; theta = 1 reads neither a
+    neighbour nor a.  a is not checked for sign or finiteness.  Q = None: no source.  F = None: a new DeviceGrid.  a, U and Q
+    are read only; returns F."""
+    fn = _need_heat_vc("mg_heat_rhs_coef")
+    if F is None:
+        F = DeviceGrid((N, N))
+    fn(int(N), float(L), float(nu), float(dt), float(theta), a.ptr if a is not None else None, U.ptr,
+       Q.ptr if Q is not None else None, F.ptr)
+    _check()
+    return F
+
+
 class HeatStepper:
     """Time stepper of include/mg_heat.h: the theta-scheme (theta = 1 backward Euler, 0.5 Crank-Nicolson) for
     u_t = nu*Laplace(u) + q on the N x N grid of the solvers, Dirichlet values on the rim of U.  One step is one launch of
@@ -1253,7 +1288,12 @@ class HeatStepper:
     sigma = 1/(theta*nu*dt) (the attribute .sigma), started from U itself -- u_old is the warm start.  k steps equal, bit for
     bit, k times {heat_rhs, Solver(shift=sigma).solve} on each instance.  max_batch = 1 steps through a Solver (fmg=n works
     as there), max_batch > 1 through a BatchSolver (which refuses fmg != 0).  The solve options are solve_opts's; shift is
-    the stepper's own and is refused here.  Everything is allocated at creation; step() allocates nothing on the device."""
+    the stepper's own and is refused here.  Everything is allocated at creation; step() allocates nothing on the device.
+    set_coefficient(a) (include/mg_heat_vc.h) steps u_t = nu*div(a grad u) + q instead, a > 0 given at the grid points: the
+    solve of every step is Solver(shift=sigma, coef=a)'s and, for theta < 1, the right-hand side is heat_rhs_coef's; k steps
+    equal, bit for bit, k times {heat_rhs_coef, Solver(shift=sigma, coef=a).solve}.  a == 1 everywhere is the stepper without
+    a coefficient bit for bit, and with theta = 1 the right-hand side reads no coefficient at all (it stays heat_rhs).  Refused
+    with [3]: a stepper with max_batch > 1 (the batched solver has no coefficient) and one created with fmg != 0."""
 
     def __init__(self, N, L=1.0, nu=1.0, dt=1.0, theta=1.0, max_batch=1, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -1264,6 +1304,21 @@ class HeatStepper:
             _check()
             raise MGError("mg_heat_stepper_create returned NULL")
         self.sigma = _lib.mg_heat_stepper_sigma(self._s)
+
+    def set_coefficient(self, a):
+        """The equation becomes u_t = nu*div(a grad u) + q.  a: what Solver.set_coefficient accepts -- N x N values at the
+        grid points, rim included, finite and > 0, as a numpy array, a DeviceGrid or a float64 torch CUDA tensor (read on
+        torch.cuda.current_stream()); None: back to the constant stepper, which enqueues what it always did.  The inner Solver
+        checks, copies and coarsens a (the stepper keeps no second copy; a may be freed after the call).  a == 1 everywhere
+        is the stepper without a coefficient, bit for bit; with theta = 1 only the solve sees a, the right-hand side stays
+        heat_rhs.  Refused (MGError, the stepper stays as it was and usable): [2] a value that is not finite or not > 0, a
+        wrong shape or alignment; [3] a stepper with max_batch > 1 (batch), or created with fmg != 0 (fmg)."""
+        _set_coefficient(_need_heat_vc("mg_heat_stepper_set_coefficient"), self._s, self.N, a)
+
+    @property
+    def has_coefficient(self):
+        """True while a coefficient is set (set_coefficient)."""
+        return bool(_need_heat_vc("mg_heat_stepper_has_coefficient")(self._s))
 
     def step_ptrs(self, U_ptrs, Q_ptrs=None, steps=1):
         """U_ptrs: device addresses of N x N fp64 arrays (16-byte aligned, stepped in place); Q_ptrs: None, or as many

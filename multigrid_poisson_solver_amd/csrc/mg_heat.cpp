@@ -3,6 +3,8 @@
 // shift = sigma started from U itself.  A thin driver over mg_solver_solve / mg_batch_solver_solve: it owns the right-hand-side
 // arrays and the table of the batched launch, a step allocates nothing and the host does not synchronise between the
 // right-hand side and the solve.
+// With a coefficient (include/mg_heat_vc.h, max_batch == 1 only) the inner mg_solver holds it; for theta != 1 the step's
+// right-hand-side launch is k::heat_rhs_vc (mg_heat_vc_kernels.hip) on the solver's own level-0 array.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -63,6 +65,8 @@ k::HeatConsts heat_consts(int N, double L, double nu, double dt, double theta)
 }
 
 double rhs_bytes(int N, bool has_q) { return (double)N * N * (has_q ? 24.0 : 16.0); }
+// with a coefficient (theta != 1): a is one more array read
+double rhs_vc_bytes(int N, bool has_q) { return (double)N * N * (has_q ? 32.0 : 24.0); }
 
 bool overlap(const void *a, const void *b, size_t bytes)
 {
@@ -114,6 +118,35 @@ void mg_heat_rhs(int N, double L, double nu, double dt, double theta, const doub
     }
     const k::HeatConsts c = heat_consts(N, L, nu, dt, theta);
     {
+        ProfScope ps(c.lap ? "heat_rhs<lap>" : "heat_rhs", N, rhs_bytes(N, Q != nullptr));
+        k::heat_rhs(ctx().stream, N, c, U, Q, F);
+    }
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_heat_rhs_coef(int N, double L, double nu, double dt, double theta, const double *a_dev, const double *U, const double *Q,
+                      double *F)
+{
+    if (!require_ready("mg_heat_rhs_coef")) return;
+    if (N < 3 || !finite_positive(L) || !U || !F) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_coef: N = %d (at least 3), L = %g (positive, finite) or a NULL array", N, L);
+        return;
+    }
+    if (!scheme_ok("mg_heat_rhs_coef", nu, dt, theta)) return;
+    if (((uintptr_t)a_dev | (uintptr_t)U | (uintptr_t)Q | (uintptr_t)F) % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_coef: a, U, Q and F must be 16-byte aligned");
+        return;
+    }
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (overlap(F, U, bytes) || (Q && overlap(F, Q, bytes)) || (a_dev && overlap(F, a_dev, bytes))) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_coef: F overlaps a, U or Q");
+        return;
+    }
+    const k::HeatConsts c = heat_consts(N, L, nu, dt, theta);
+    if (a_dev && c.lap) {
+        ProfScope ps("heat_rhs_vc", N, rhs_vc_bytes(N, Q != nullptr));
+        k::heat_rhs_vc(ctx().stream, N, c, a_dev, U, Q, F);
+    } else {   // a == 1, or theta == 1 (a is not read): mg_heat_rhs's launch
         ProfScope ps(c.lap ? "heat_rhs<lap>" : "heat_rhs", N, rhs_bytes(N, Q != nullptr));
         k::heat_rhs(ctx().stream, N, c, U, Q, F);
     }
@@ -240,8 +273,13 @@ int mg_heat_stepper_step(mg_heat_stepper *s, int n, double *const *U_dev, const 
     if (!MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)n * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)))
         return finish(MG_ERR_HIP);
     int status = MG_SOLVE_CONVERGED;
+    // (max_batch == 1 with a coefficient and theta != 1: the variable right-hand side on the solver's level-0 coefficient)
+    const double *coef = s->single && s->hc.lap ? solver_coefficient(s->single) : nullptr;
     for (int step = 0; step < steps && status == MG_SOLVE_CONVERGED; ++step) {
-        {
+        if (coef) {
+            ProfScope ps("heat_rhs_vc", s->N, rhs_vc_bytes(s->N, any_q));
+            k::heat_rhs_vc(st, s->N, s->hc, coef, U_dev[0], Q_dev ? Q_dev[0] : nullptr, s->F);
+        } else {
             ProfScope ps(s->hc.lap ? "heat_rhs<lap>" : "heat_rhs", s->N, rhs_bytes(s->N, any_q) * n);
             k::heat_rhs_batch(st, n, s->N, s->hc, s->dev_tab);
         }
@@ -266,6 +304,26 @@ int mg_heat_stepper_step(mg_heat_stepper *s, int n, double *const *U_dev, const 
 }
 
 double mg_heat_stepper_sigma(const mg_heat_stepper *s) { return s ? s->sigma : 0.0; }
+
+// ------------------------------------------------------------------ variable coefficient (include/mg_heat_vc.h)
+int mg_heat_stepper_set_coefficient(mg_heat_stepper *s, const double *a_dev)
+{
+    if (!require_ready("mg_heat_stepper_set_coefficient")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_heat_stepper_set_coefficient: NULL stepper");
+        return MG_ERR_ARG;
+    }
+    if (!s->single) {
+        if (!a_dev) return MG_OK;   // (a batched stepper never has one)
+        fail(MG_ERR_UNSUPPORTED, "mg_heat_stepper_set_coefficient: the stepper was created with max_batch = %d; the batched "
+                                 "solver has no variable coefficient", s->max_batch);
+        return MG_ERR_UNSUPPORTED;
+    }
+    // the solver checks, copies and coarsens; its refusal -- code and text -- is the stepper's, and leaves both as they were
+    return mg_solver_set_coefficient(s->single, a_dev);
+}
+
+int mg_heat_stepper_has_coefficient(const mg_heat_stepper *s) { return s && s->single ? mg_solver_has_coefficient(s->single) : 0; }
 
 void mg_heat_stepper_destroy(mg_heat_stepper *s)
 {

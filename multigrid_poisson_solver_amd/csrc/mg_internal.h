@@ -468,6 +468,10 @@ void gauss_seidel_relative_vc(hipStream_t s, int N, double h2, double inv, doubl
 void coef_coarsen(hipStream_t s, int N, const double *Af, int M, double *Ac, const RestrictTable &t);
 // *flag = 1 when a value of A[0..n) is not finite or not > 0 (the caller zeroes the flag)
 void coef_check(hipStream_t s, const double *A, size_t n, int *flag);
+// right-hand side of a theta-scheme time step with a variable coefficient (mg_heat_vc_kernels.hip, driven by mg_heat.cpp; the
+// expression and its order: include/mg_heat_vc.h).  c.lap must be set: theta == 1 reads no coefficient and goes to heat_rhs.
+// F = rhs(A, U, Q) (Q == nullptr: no source); the rim of F is +0, nothing else is written
+void heat_rhs_vc(hipStream_t s, int N, const HeatConsts &c, const double *A, const double *U, const double *Q, double *F);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
@@ -495,6 +499,9 @@ int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0,
 // the same cycle -- node order, field ping-pong, launch count -- with the variable-coefficient kernels (include/mg_varcoef.h);
 // coef[l]: the nodal coefficient of level l
 int solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<double *> &coef, const double *F0, double *U0, int top = 0);
+// the level-0 coefficient of a solver, mg_solver::coef[0] (mg_solve.cpp), nullptr when none is set: the heat stepper's
+// right-hand-side kernel reads the solver's own array instead of keeping a second copy (mg_heat.cpp)
+const double *solver_coefficient(const mg_solver *s);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

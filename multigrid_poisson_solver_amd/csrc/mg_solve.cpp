@@ -250,6 +250,8 @@ int mg::solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector
     return launches;
 }
 
+const double *mg::solver_coefficient(const mg_solver *s) { return s && s->coef_set ? s->coef[0] : nullptr; }
+
 namespace {
 
 // the same cycle through the fused nodes of the streaming smoother (its weighted instantiations): per level one `-1`
@@ -676,7 +678,10 @@ void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, 
 {
     if (!require_ready("mg_residualCoefficient") || !vc_args_ok("mg_residualCoefficient", N, L, shift, {a_dev, U, F, D})) return;
     const double dx2 = spacing_sq(N, L);
-    k::residual_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, F, D, sign < 0 ? -1 : +1);
+    {
+        ProfScope ps("residual_vc", N, (double)N * N * 32.0);   // (the yardstick of scripts/bench_heat_vc.py: the same 32 B per point)
+        k::residual_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, F, D, sign < 0 ? -1 : +1);
+    }
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
 }
 
