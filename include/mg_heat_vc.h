@@ -34,7 +34,8 @@
  * mg_heat_rhs_coef on the old field with its old rim, then sets the new rim, then solves with mg_solver_solve at shift =
  * mg_heat_stepper_sigma.
  * Not built, and refused where it could be asked for: a batched stepper with a coefficient (max_batch > 1 steps through
- * mg_batch_solver, which has none), fmg with a coefficient (the inner mg_solver refuses it), a heat capacity multiplying u_t.
+ * mg_batch_solver and does not hand it one: mg_varcoef_batch.h), fmg with a coefficient (the inner mg_solver refuses it), a
+ * heat capacity multiplying u_t.
  */
 #ifndef MG_HEAT_VC_H
 #define MG_HEAT_VC_H
@@ -60,7 +61,7 @@ void mg_heat_rhs_coef(int N, double L, double nu, double dt, double theta, const
  * Returns 0, or (mg_last_error; the stepper keeps the state it had, coefficient included, and stays usable):
  *   MG_ERR_ARG (2)          NULL stepper, or what mg_solver_set_coefficient refuses with it (alignment, a value of a that is
  *                           not finite or not > 0); the solver's code and text pass through
- *   MG_ERR_UNSUPPORTED (3)  a stepper created with max_batch > 1 (the batch solver has no coefficient; a_dev == NULL asks for
+ *   MG_ERR_UNSUPPORTED (3)  a stepper created with max_batch > 1 (the stepper hands its batch solver none; a_dev == NULL asks for
  *                           the state it is in and returns 0), or with solve.fmg != 0 (the solver's own refusal) */
 int  mg_heat_stepper_set_coefficient(mg_heat_stepper *s, const double *a_dev);
 /* 1 when a coefficient is set, else 0 (NULL: 0) */

@@ -474,5 +474,7 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 #include "mg_varcoef.h"
 /* the heat stepper with a variable coefficient, u_t = nu*div(a grad u) + q: mg_heat_rhs_coef, mg_heat_stepper_set_coefficient */
 #include "mg_heat_vc.h"
+/* the batched solver with a variable coefficient per instance (or one shared): mg_batch_solver_set_coefficient */
+#include "mg_varcoef_batch.h"
 
 #endif /* MG_HIP_H */

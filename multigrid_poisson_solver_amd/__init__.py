@@ -166,6 +166,13 @@ ABI_HEAT_VC = {
     "mg_heat_stepper_has_coefficient": (_i, [_vp]),
 }
 
+# the symbols include/mg_varcoef_batch.h declares (the batched solver with a coefficient per instance, or one shared); bound
+# like ABI_FMG: a library without them still loads, BatchSolver.set_coefficient() / solve_batched_coef() then raise
+ABI_VC_BATCH = {
+    "mg_batch_solver_set_coefficient": (_i, [_vp, _i, _vp]),
+    "mg_batch_solver_has_coefficient": (_i, [_vp]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -223,7 +230,8 @@ def load_library(path=None):
         fn.restype, fn.argtypes = res, args
     if missing:
         raise MGError(f"{path} does not export: {missing}")
-    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()):
+    for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
+            list(ABI_VC_BATCH.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -896,6 +904,32 @@ def solve_opts(**opts):
     return o
 
 
+def _coefficient_address(N, a, keep):
+    """Device address of one coefficient for the length of a call: a DeviceGrid (anything with .ptr and .shape), a float64
+    torch CUDA tensor, or an N x N numpy array, which is uploaded into a DeviceGrid appended to `keep` (the caller frees it)."""
+    if _is_torch(a):
+        import torch
+        if not (a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (N, N) and a.is_contiguous()):
+            raise MGError(f"coef: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+        if a.data_ptr() % 16 != 0:   # (odd instances of a contiguous [n, N, N] tensor with N odd; on the engine stream)
+            g = DeviceGrid((N, N))
+            keep.append(g)
+            _lib.mg_copy(g.ptr, a.data_ptr(), N * N)
+            _check()
+            return g.ptr
+        return a.data_ptr()
+    if hasattr(a, "ptr") and hasattr(a, "shape"):
+        if tuple(a.shape) != (N, N):
+            raise MGError(f"coef: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+        return a.ptr
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape != (N, N):
+        raise MGError(f"coef: array of shape {a.shape}, expected ({N}, {N})")
+    g = DeviceGrid.from_host(a)
+    keep.append(g)
+    return g.ptr
+
+
 def _set_coefficient(fn, handle, N, a):
     """The argument handling of Solver.set_coefficient and HeatStepper.set_coefficient: fn(handle, device address of a) with a
     an N x N numpy array (uploaded for the call), a DeviceGrid, or a float64 torch CUDA tensor (read on
@@ -1083,7 +1117,10 @@ class BatchSolver:
     An instance stops once it meets its own tolerance; one cycle is one launch per node over all active instances.
     Every level array for max_batch instances is allocated here; solve() allocates nothing on the device.  shift=sigma
     (one value for the whole batch) solves Laplace(U) - sigma*U = F: the many same-size solves of implicit time stepping,
-    sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt).  fmg != 0 (the full-multigrid start of Solver) is refused here."""
+    sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt).  fmg != 0 (the full-multigrid start of Solver) is refused here.
+    set_coefficient(a) solves div(a_i grad U_i) - sigma*U_i = F_i, one coefficient per instance or one shared by all, every
+    instance bit-identical to Solver(coef=a_i) on it alone (include/mg_varcoef_batch.h):
+        b = BatchSolver(N, L, max_batch=B); b.set_coefficient(a); U, infos = b.solve(F, U0); b.set_coefficient(None)"""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -1092,6 +1129,61 @@ class BatchSolver:
         if not self._s:
             _check()
             raise MGError("mg_batch_solver_create returned NULL")
+
+    def set_coefficient(self, a):
+        """a of shape (N, N): one coefficient shared by every instance (one copy is stored).  a of shape (n, N, N), or a
+        sequence of n (N, N) arrays, DeviceGrids or tensors, n <= max_batch: instance i of a solve uses a[i], and a solve
+        then takes at most n instances.  None: back to the constant solver.  Values at the grid points, rim included, finite
+        and > 0; numpy arrays, DeviceGrids or float64 torch CUDA tensors (read on torch.cuda.current_stream()), as
+        Solver.set_coefficient takes them.  Every instance then solves as Solver(coef=a[i]) solves it alone, bit for bit; a == 1
+        everywhere is the solver without a coefficient, bit for bit.  The arrays are copied: they may be freed after the
+        call.  A refused coefficient (MGError "[2] ...": a wrong shape, more than max_batch coefficients, a bad value, whose
+        instance the message names) leaves the solver as it was."""
+        fn = _need_vc_batch("mg_batch_solver_set_coefficient")
+        if a is None:
+            status = fn(self._s, 0, None)
+        else:
+            N = self.N
+            if isinstance(a, (list, tuple)):
+                items = list(a)
+            elif len(a.shape) == 3:
+                items = [a[i] for i in range(a.shape[0])]
+            elif len(a.shape) == 2:
+                items = [a]
+            else:
+                raise MGError(f"[2] coef: expected (N, N), (n, N, N) or a sequence of (N, N) arrays, got shape {tuple(a.shape)}")
+            if not items:
+                raise MGError("[2] coef: an empty sequence (None takes the coefficient away)")
+            keep, prev = [], None
+            torch_item = next((t for t in items if _is_torch(t)), None)
+            try:
+                if torch_item is not None:
+                    import torch
+                    prev = _lib.mg_get_stream()
+                    _lib.mg_set_stream(torch.cuda.current_stream(torch_item.device).cuda_stream)
+                try:
+                    ptrs = [_coefficient_address(N, t, keep) for t in items]
+                except MGError as e:   # (a wrong shape or type is an argument error like the library's own: code 2)
+                    raise MGError(f"[2] {e}") from None
+                status = fn(self._s, len(ptrs), (C.c_void_p * len(ptrs))(*ptrs))
+            finally:
+                if torch_item is not None:
+                    _lib.mg_set_stream(prev)
+                for g in keep:
+                    g.free()
+        if status:
+            _check()
+            raise MGError(f"mg_batch_solver_set_coefficient failed with status {status}")
+
+    @property
+    def has_coefficient(self):
+        """True when a coefficient is set (shared or per instance)."""
+        return self.n_coefficients > 0
+
+    @property
+    def n_coefficients(self):
+        """0 without a coefficient, 1 with one shared by every instance, else the number of per-instance coefficients."""
+        return int(_need_vc_batch("mg_batch_solver_has_coefficient")(self._s))
 
     def solve_ptrs(self, F_ptrs, U_ptrs):
         """F_ptrs, U_ptrs: sequences of device addresses of N x N fp64 arrays (16-byte aligned; F addresses may repeat),
@@ -1230,6 +1322,32 @@ def solve_batched(F, U=None, L=1.0, **opts):
         s.close()
 
 
+def solve_batched_coef(F, a, U=None, L=1.0, **opts):
+    """solve_batched with a variable coefficient: B problems div(a_i grad U_i) - sigma*U_i = F_i in one batched call; returns
+    (U, infos).  a: (N, N), shared by every instance, or (B, N, N) / a sequence of B (N, N) ones, one per instance
+    (BatchSolver.set_coefficient); F and U as solve_batched takes them.  Every instance is bit-identical to
+    solve(F_i, U_i, L, coef=a_i, ...); a == 1 everywhere is solve_batched, bit for bit."""
+    Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
+    if U is None:
+        B = 1 if shared else len(Fs)
+    else:
+        B = len(U) if isinstance(U, (list, tuple)) else (1 if isinstance(U, DeviceGrid) or len(U.shape) == 2 else int(U.shape[0]))
+    n_a = len(a) if isinstance(a, (list, tuple)) else (int(a.shape[0]) if len(a.shape) == 3 else 1)
+    N = int(Fs[0].shape[-1])
+    s = BatchSolver(N, L, max_batch=max(B, n_a, 1), **opts)
+    try:
+        s.set_coefficient(a)
+        return s.solve(F, U)
+    finally:
+        s.close()
+
+
+def _need_vc_batch(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched variable-coefficient solver is not in this library)")
+    return getattr(_lib, name)
+
+
 def _need_heat(name):
     if not hasattr(lib(), name):
         raise MGError(f"{LIB_PATH} does not export {name} (a build without the heat stepper)")
@@ -1293,7 +1411,7 @@ class HeatStepper:
     solve of every step is Solver(shift=sigma, coef=a)'s and, for theta < 1, the right-hand side is heat_rhs_coef's; k steps
     equal, bit for bit, k times {heat_rhs_coef, Solver(shift=sigma, coef=a).solve}.  a == 1 everywhere is the stepper without
     a coefficient bit for bit, and with theta = 1 the right-hand side reads no coefficient at all (it stays heat_rhs).  Refused
-    with [3]: a stepper with max_batch > 1 (the batched solver has no coefficient) and one created with fmg != 0."""
+    with [3]: a stepper with max_batch > 1 (the batched stepper passes none to its BatchSolver) and one created with fmg != 0."""
 
     def __init__(self, N, L=1.0, nu=1.0, dt=1.0, theta=1.0, max_batch=1, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)

@@ -468,6 +468,21 @@ void gauss_seidel_relative_vc(hipStream_t s, int N, double h2, double inv, doubl
 void coef_coarsen(hipStream_t s, int N, const double *Af, int M, double *Ac, const RestrictTable &t);
 // *flag = 1 when a value of A[0..n) is not finite or not > 0 (the caller zeroes the flag)
 void coef_check(hipStream_t s, const double *A, size_t n, int *flag);
+// batched forms of the above (mg_varcoef_batch_kernels.hip, driven by mg_solve_batch.cpp): one launch over n instances, each
+// running the code and the block partition of its single launch (the bodies are shared: mg_varcoef_impl.h).  items[i]: the
+// arrays of instance i, the level's coefficient in the slot `coarse`.
+// sweep: in = U (zero_in: not read), F, coarse = a, out
+void wjacobi_vc_batch(hipStream_t s, int n, int N, double dx2, double sd, double omega, bool zero_in, const NodeBatchItem *items);
+// residual: in = U, F, coarse = a, out = D
+void residual_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items, int sign);
+// norm: in = U, F, coarse = a; out[i] = its norm, its partials at part + i*resnorm_partials(N)
+void resnorm_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items, double *part, double *out);
+// coarse solve: out = U, F, coarse = a; instance i's state at state + 4i (no err_out)
+void gauss_seidel_relative_vc_batch(hipStream_t s, int n, int N, double h2, double inv, double sd, const NodeBatchItem *items,
+                                    double atol, double rtol, int max_iters, int *state);
+// coarsening N -> M: in = a_f, out = a_c; check of `count` values: in = a, flags[i] = 1 for a bad instance (zeroed by the caller)
+void coef_coarsen_batch(hipStream_t s, int n, int N, int M, const NodeBatchItem *items, const RestrictTable &t);
+void coef_check_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items, int *flags);
 // right-hand side of a theta-scheme time step with a variable coefficient (mg_heat_vc_kernels.hip, driven by mg_heat.cpp; the
 // expression and its order: include/mg_heat_vc.h).  c.lap must be set: theta == 1 reads no coefficient and goes to heat_rhs.
 // F = rhs(A, U, Q) (Q == nullptr: no source); the rim of F is +0, nothing else is written

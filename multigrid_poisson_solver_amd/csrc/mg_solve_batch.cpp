@@ -6,6 +6,8 @@
 // After each read-back the host drops the instances that met their tolerance from the active set and rebuilds and
 // uploads the tables when the set changed (the read-back already synchronises once per cycle, so one pinned staging
 // buffer serves every upload).
+// With a coefficient set (include/mg_varcoef_batch.h) the cycle is solve_vcycle_vc's instead (mg_solve.cpp), launch by launch
+// over the active set through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip): vcycle_vc_batch below.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -29,6 +31,13 @@ struct mg_batch_solver {
     int n_tables = 0;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_sync = nullptr;
     std::vector<std::vector<double>> history;   // per instance of the last solve
+    // variable coefficient (include/mg_varcoef_batch.h; nothing of it is allocated before the first
+    // mg_batch_solver_set_coefficient)
+    std::vector<double *> coef;              // per level: the nodal coefficients of coef_cap instances at the instance pitch
+    int coef_cap = 0;                        // instances the level storage holds
+    int n_coef = 0;                          // 0: none set; 1: one shared by every instance; n > 1: instance i uses copy i
+    int *coef_flags = nullptr;               // device [max_batch]: the check found a bad value in that instance
+    int *host_coef_flags = nullptr;          // pinned [max_batch]
 };
 
 namespace {
@@ -45,6 +54,14 @@ int t_gs(int nl) { return 1 + 3 * (nl - 1); }
 int t_up(int nl, int l) { return 2 + 3 * (nl - 1) + 2 * l; }
 int t_copy(int nl) { return 2 + 5 * (nl - 1); }
 int n_tables(int nl) { return 3 + 5 * (nl - 1); }
+// table slots of one variable-coefficient cycle: the norm, per level the two sweep directions between its fields P (the
+// caller's U at level 0, A[l] below) and Q = B[l] -- P -> Q (+0), Q -> P (+1): the sweeps ping-pong, so two tables serve all
+// of them --, the zero-start sweep into P (+2), the residual (+3), its restriction (+4) and the prolongation-add (+5), then
+// the coarse solve and the final copy
+int v_level(int l) { return 1 + 6 * l; }
+int v_gs(int nl) { return 1 + 6 * (nl - 1); }
+int v_copy(int nl) { return 2 + 6 * (nl - 1); }
+int n_tables_vc(int nl) { return 3 + 6 * (nl - 1); }
 
 bool down_fused(const mg_batch_solver *s, int l)
 {
@@ -62,6 +79,9 @@ void release(mg_batch_solver *s)
     for (double *p : s->A) if (p) (void)hipFree(p);
     for (double *p : s->B) if (p) (void)hipFree(p);
     for (double *p : s->F) if (p) (void)hipFree(p);
+    for (double *p : s->coef) if (p) (void)hipFree(p);
+    if (s->coef_flags) (void)hipFree(s->coef_flags);
+    if (s->host_coef_flags) (void)hipHostFree(s->host_coef_flags);
     if (s->part) (void)hipFree(s->part);
     if (s->dev_rb) (void)hipFree(s->dev_rb);
     if (s->host_rb) (void)hipHostFree(s->host_rb);
@@ -108,10 +128,47 @@ void fill_tables(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
     item(t_copy(nl)) = NodeBatchItem{x[0], nullptr, nullptr, U0, nullptr};
 }
 
+// where the pre-smoothed iterate of level l lies when the cycle has the options' sweep counts: every sweep swaps the fields,
+// and coarser levels spend their first sweep on the zero start into P
+bool down_ends_in_p(const mg_batch_solver *s, int l) { return (l == 0 ? s->o.pre : s->o.pre - 1) % 2 == 0; }
+
+// the same for solve_vcycle_vc's dataflow (mg_solve.cpp): cur / other of every launch of one cycle, the coefficient of
+// instance i (the one copy in shared mode) in the slot `coarse`
+void fill_tables_vc(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
+{
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    const int ci = s->n_coef == 1 ? 0 : i;
+    auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * mb + j]; };
+    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
+    item(0) = NodeBatchItem{U0, F0, level(s, s->coef, 0, ci), nullptr, nullptr};
+    for (int l = 0; l + 1 < nl; ++l) {
+        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
+        const double *a = level(s, s->coef, l, ci);
+        double *P = l == 0 ? U0 : level(s, s->A, l, i), *Q = level(s, s->B, l, i);
+        const int t = v_level(l);
+        item(t) = NodeBatchItem{P, F, a, Q, nullptr};
+        item(t + 1) = NodeBatchItem{Q, F, a, P, nullptr};
+        item(t + 2) = NodeBatchItem{nullptr, F, a, P, nullptr};
+        x[l] = down_ends_in_p(s, l) ? P : Q;
+        y[l] = down_ends_in_p(s, l) ? Q : P;
+        item(t + 3) = NodeBatchItem{x[l], F, a, y[l], nullptr};                              // residual into the free field
+        item(t + 4) = NodeBatchItem{y[l], nullptr, nullptr, level(s, s->F, l + 1, i), nullptr};   // its restriction
+    }
+    item(v_gs(nl)) = NodeBatchItem{nullptr, level(s, s->F, nl - 1, i), level(s, s->coef, nl - 1, ci), level(s, s->A, nl - 1, i), nullptr};
+    x[nl - 1] = level(s, s->A, nl - 1, i);
+    for (int l = nl - 2; l >= 0; --l) {
+        item(v_level(l) + 5) = NodeBatchItem{x[l], nullptr, x[l + 1], y[l], nullptr};   // x + P(coarse) into the free field
+        if (s->o.post % 2 == 0) x[l] = y[l];   // (the prolongation swapped the fields, every post sweep swaps them again)
+    }
+    item(v_copy(nl)) = NodeBatchItem{x[0], nullptr, nullptr, U0, nullptr};
+}
+
+// (without a coefficient: exactly the tables, and the bytes, the solver uploaded before it knew of one)
 bool upload_tables(mg_batch_solver *s, hipStream_t st)
 {
-    return MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)s->n_tables * s->max_batch * sizeof(NodeBatchItem),
-                                 hipMemcpyHostToDevice, st));
+    const int nl = (int)s->sizes.size();
+    const int used = s->n_coef > 0 ? n_tables_vc(nl) : n_tables(nl);
+    return MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)used * s->max_batch * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st));
 }
 
 // one V(pre, post) cycle of the n active instances whose tables are uploaded; returns the launches it enqueued
@@ -181,6 +238,59 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
     return launches;
 }
 
+// one V(pre, post) cycle with the coefficient: solve_vcycle_vc's node order and field ping-pong (mg_solve.cpp), each of its
+// launches ONE launch over the n active instances whose tables are uploaded; returns the launches it enqueued
+int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
+{
+    const mg_solve_opts &o = s->o;
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    const std::vector<LevelConsts> &lc = s->lc;
+    auto tab = [&](int t) { return s->dev_tab + (size_t)t * mb; };
+    auto sd = [&](int l) { return o.shift * lc[l].dx2; };   // (the product solve_level_consts forms)
+    std::vector<char> in_p(nl, 1);   // per level: the current iterate is in P (else in Q)
+    int launches = 0;
+    for (int l = 0; l + 1 < nl; ++l) {
+        const int N = s->sizes[l], M = s->sizes[l + 1], t = v_level(l);
+        bool p = true;
+        int sweeps = o.pre;
+        if (l > 0) {
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, true, tab(t + 2));
+            ++launches;
+            --sweeps;
+        }
+        for (int i = 0; i < sweeps; ++i) {
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, false, tab(p ? t : t + 1));
+            ++launches;
+            p = !p;
+        }
+        k::residual_vc_batch(st, n, N, lc[l].inv, sd(l), tab(t + 3), -1);
+        k::restrict_batch(st, n, N, M, tab(t + 4), restrict_table(N, M), +1);
+        launches += 2;
+        in_p[l] = p;
+    }
+    const int last = nl - 1;
+    k::gauss_seidel_relative_vc_batch(st, n, s->sizes[last], lc[last].dx2, lc[last].inv, sd(last), tab(v_gs(nl)), o.coarse_atol,
+                                      o.coarse_rtol, o.coarse_max_iters, rb_state(s->dev_rb, mb));
+    ++launches;
+    for (int l = nl - 2; l >= 0; --l) {
+        const int N = s->sizes[l], Nc_l = s->sizes[l + 1], t = v_level(l);
+        k::prolong_add_batch(st, n, Nc_l, N, tab(t + 5), prolong_table(Nc_l, N));
+        ++launches;
+        bool p = !in_p[l];
+        for (int i = 0; i < o.post; ++i) {
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, false, tab(p ? t : t + 1));
+            ++launches;
+            p = !p;
+        }
+        in_p[l] = p;
+    }
+    if (!in_p[0]) {   // the result is in B[0], not in the caller's U
+        k::copy_batch(st, n, (size_t)s->N * s->N, tab(v_copy(nl)));
+        ++launches;
+    }
+    return launches;
+}
+
 // the same cycle operator by operator, instance by instance (MG_SMOOTHER=simple): the yardstick of the batched launches
 int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int> &act, const double *const *F0,
                        double *const *U0)
@@ -203,6 +313,13 @@ int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int
 int norms(mg_batch_solver *s, hipStream_t st, int n, bool has_u, double *out)
 {
     k::resnorm_batch(st, n, s->N, s->lc[0].inv, has_u, s->dev_tab, s->part, out, s->lc[0].sh);
+    return 2;
+}
+
+// the residual norm with the coefficient (the reference norm ||F|| has no operator in it: norms(..., false, ...))
+int norms_vc(mg_batch_solver *s, hipStream_t st, int n, double *out)
+{
+    k::resnorm_vc_batch(st, n, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->dev_tab, s->part, out);
     return 2;
 }
 
@@ -269,7 +386,7 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
         const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
         ok = restrict_table(Nf, Nc).lo != nullptr && prolong_table(Nc, Nf).owner_row != nullptr;
     }
-    s->n_tables = n_tables(nl);
+    s->n_tables = n_tables_vc(nl);   // (the larger set: a coefficient may be set later, and a solve allocates nothing)
     const size_t tab_bytes = (size_t)s->n_tables * max_batch * sizeof(NodeBatchItem);
     ok = ok && MG_HIP(hipMalloc((void **)&s->part, k::resnorm_partials(N) * max_batch * sizeof(double))) &&
          MG_HIP(hipMalloc(&s->dev_rb, rb_bytes(max_batch))) &&
@@ -320,6 +437,10 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
         fail(MG_ERR_ARG, "mg_batch_solver_solve: n = %d outside [1, max_batch = %d]", n, s->max_batch);
         return finish(MG_ERR_ARG);
     }
+    if (s->n_coef > 1 && n > s->n_coef) {
+        fail(MG_ERR_ARG, "mg_batch_solver_solve: n = %d instances, but the solver holds %d coefficients (one per instance)", n, s->n_coef);
+        return finish(MG_ERR_ARG);
+    }
     for (int i = 0; i < n; ++i) s->history[i].clear();
     const size_t bytes = (size_t)s->N * s->N * sizeof(double);
     for (int i = 0; i < n; ++i) {
@@ -346,18 +467,20 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
     const hipStream_t st = ctx().stream;
     const mg_solve_opts &o = s->o;
     const int mb = s->max_batch;
+    const bool vc = s->n_coef > 0;   // (the variable-coefficient cycle, whatever mg_set_smoother says)
     const bool simple = ctx().smoother == SMOOTHER_SIMPLE;
     std::vector<int> act(n);
     std::vector<double> tol(n);
     for (int i = 0; i < n; ++i) act[i] = i;
     auto build = [&]() {
-        for (size_t j = 0; j < act.size(); ++j) fill_tables(s, (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
+        for (size_t j = 0; j < act.size(); ++j)
+            (vc ? fill_tables_vc : fill_tables)(s, (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
         return upload_tables(s, st);
     };
     if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
     if (!build()) return finish(MG_ERR_HIP);
     bs.launches += norms(s, st, n, false, rb_ref(s->dev_rb, mb));
-    bs.launches += norms(s, st, n, true, rb_res(s->dev_rb));
+    bs.launches += vc ? norms_vc(s, st, n, rb_res(s->dev_rb)) : norms(s, st, n, true, rb_res(s->dev_rb));
     if (!read_back(s, st)) return finish(MG_ERR_HIP);
     std::vector<int> next;
     for (int i = 0; i < n; ++i) {
@@ -373,8 +496,8 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
             if (!build()) return finish(MG_ERR_HIP);
         }
         const int na = (int)act.size();
-        bs.launches += simple ? vcycle_simple_each(s, st, act, F_dev, U_dev) : vcycle_batch(s, st, na);
-        bs.launches += norms(s, st, na, true, rb_res(s->dev_rb));
+        bs.launches += vc ? vcycle_vc_batch(s, st, na) : simple ? vcycle_simple_each(s, st, act, F_dev, U_dev) : vcycle_batch(s, st, na);
+        bs.launches += vc ? norms_vc(s, st, na, rb_res(s->dev_rb)) : norms(s, st, na, true, rb_res(s->dev_rb));
         if (!read_back(s, st)) return finish(MG_ERR_HIP);
         next.clear();
         for (int j = 0; j < na; ++j) {
@@ -405,5 +528,105 @@ void mg_batch_solver_destroy(mg_batch_solver *s)
     if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
     release(s);
 }
+
+// ------------------------------------------------------------------ variable coefficient (include/mg_varcoef_batch.h)
+int mg_batch_solver_set_coefficient(mg_batch_solver *s, int n, const double *const *a_dev)
+{
+    if (!require_ready("mg_batch_solver_set_coefficient")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (n < 0 || n > s->max_batch) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: n = %d outside [0, max_batch = %d]", n, s->max_batch);
+        return MG_ERR_ARG;
+    }
+    if (n == 0) {
+        if (a_dev) {
+            fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: n = 0 takes the coefficient away and needs a NULL array");
+            return MG_ERR_ARG;
+        }
+        s->n_coef = 0;   // back to the constant-coefficient solver (the level storage stays for the next coefficient)
+        return MG_OK;
+    }
+    if (!a_dev) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: NULL array of %d coefficients", n);
+        return MG_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!a_dev[i] || (uintptr_t)a_dev[i] % 16 != 0) {
+            fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: the coefficient of instance %d is NULL or not 16-byte aligned", i);
+            return MG_ERR_ARG;
+        }
+    const hipStream_t st = ctx().stream;
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    if (!s->coef_flags &&
+        !(MG_HIP(hipMalloc((void **)&s->coef_flags, mb * sizeof(int))) &&
+          MG_HIP(hipHostMalloc((void **)&s->host_coef_flags, mb * sizeof(int), hipHostMallocDefault)))) {
+        if (s->coef_flags) { (void)hipFree(s->coef_flags); s->coef_flags = nullptr; }
+        return MG_ERR_HIP;
+    }
+    // level storage for n instances: what is there when it is large enough, else a fresh set, which replaces the old one
+    // only once the check has passed -- a refused coefficient leaves the solver's own untouched
+    std::vector<double *> fresh;
+    auto drop_fresh = [&]() {
+        for (double *p : fresh) if (p) (void)hipFree(p);
+        fresh.clear();
+    };
+    if (s->coef_cap < n) {
+        fresh.assign(nl, nullptr);
+        for (int l = 0; l < nl; ++l)
+            if (!MG_HIP(hipMalloc((void **)&fresh[l], s->pitch[l] * n * sizeof(double)))) {
+                drop_fresh();
+                return MG_ERR_HIP;
+            }
+    }
+    const std::vector<double *> &dst = fresh.empty() ? s->coef : fresh;
+    // tables: the check and the copy into level 0 (slot 0: in = the caller's a_i, out = level 0), then per level the
+    // coarsening (slot 1 + l: in = level l, out = level l + 1).  The solver's own tables: every solve rebuilds them.
+    for (int i = 0; i < n; ++i) {
+        s->host_tab[i] = NodeBatchItem{a_dev[i], nullptr, nullptr, dst[0] + (size_t)i * s->pitch[0], nullptr};
+        for (int l = 0; l + 1 < nl; ++l)
+            s->host_tab[(size_t)(1 + l) * mb + i] =
+                NodeBatchItem{dst[l] + (size_t)i * s->pitch[l], nullptr, nullptr, dst[l + 1] + (size_t)i * s->pitch[l + 1], nullptr};
+    }
+    const size_t n0 = (size_t)s->N * s->N;
+    bool ok = MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)nl * mb * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)) &&
+              MG_HIP(hipMemsetAsync(s->coef_flags, 0, n * sizeof(int), st));
+    if (ok) {
+        // the check comes first and reads the CALLER's arrays
+        k::coef_check_batch(st, n, n0, s->dev_tab, s->coef_flags);
+        ok = MG_HIP(hipMemcpyAsync(s->host_coef_flags, s->coef_flags, n * sizeof(int), hipMemcpyDeviceToHost, st)) &&
+             MG_HIP(hipStreamSynchronize(st));
+    }
+    if (!ok) {
+        drop_fresh();
+        return MG_ERR_HIP;
+    }
+    for (int i = 0; i < n; ++i)
+        if (s->host_coef_flags[i]) {
+            drop_fresh();
+            fail(MG_ERR_ARG, "mg_batch_solver_set_coefficient: every value of a must be finite and > 0 (instance %d has one that is not)", i);
+            return MG_ERR_ARG;
+        }
+    // from here on the level storage is overwritten: until it is whole again the solver has NO coefficient, so a HIP error
+    // below leaves the constant-coefficient solver, never one on a half-replaced coefficient
+    s->n_coef = 0;
+    if (!fresh.empty()) {
+        for (double *p : s->coef) if (p) (void)hipFree(p);
+        s->coef.swap(fresh);
+        fresh.clear();
+        s->coef_cap = n;
+    }
+    k::copy_batch(st, n, n0, s->dev_tab);
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen_batch(st, n, s->sizes[l], s->sizes[l + 1], s->dev_tab + (size_t)(1 + l) * mb,
+                              restrict_table(s->sizes[l], s->sizes[l + 1]));
+    if (!MG_HIP(hipStreamSynchronize(st))) return MG_ERR_HIP;   // (the caller may free the a_i, or solve on another stream)
+    s->n_coef = n;
+    return MG_OK;
+}
+
+int mg_batch_solver_has_coefficient(const mg_batch_solver *s) { return s ? s->n_coef : 0; }
 
 }  // extern "C"
