@@ -191,6 +191,28 @@ void mg_profile_sample(int every);
 int  mg_profile_end(mg_profile_entry *out, int cap);
 
 /* ------------------------------------------------------------------------- */
+/* geometry record of the streaming smoother (host side only, off by default)  */
+/* ------------------------------------------------------------------------- */
+/* While the log is on, every launch of the streaming kernel appends one record when it is ENQUEUED (a traced, batched
+ * or graph-captured plan records while it is built, not when it replays).  A record is MG_STREAM_GEOMETRY_FIELDS ints:
+ *   N, own rows (N, or the rows of a slab window), rows_per_chunk, chunks, groups (workgroups per chunk row),
+ *   instances (of a batch, else 1), S (sweeps), COLS (columns per lane), IN (0 load, 1 zero, 2 prolong), RESTRICT,
+ *   PRE (recomputed pre-sweeps), flags (MG_GEOMETRY_NT | _WT | _SH | _F32).
+ * The chunk height is the launcher's choice (device, occupancy, batch size, slab window, env MG_RESIDENT_PCT,
+ * MG_MAX_ROWS); no result depends on it.  The log keeps at most 65536 records: later ones are dropped, and the next
+ * fetch reports that as an error (MG_ERR_ARG). */
+#define MG_STREAM_GEOMETRY_FIELDS 12
+#define MG_GEOMETRY_NT  1   /* non-temporal stores of U */
+#define MG_GEOMETRY_WT  2   /* weighted sweep */
+#define MG_GEOMETRY_SH  4   /* screened (shifted) operator */
+#define MG_GEOMETRY_F32 8   /* fp32 fields */
+/* on != 0: start recording (the log is emptied); 0: stop and empty it */
+void mg_stream_geometry_log(int on);
+/* copies the oldest records, at most cap of them, to out (MG_STREAM_GEOMETRY_FIELDS ints each) and removes them from
+ * the log; returns how many.  out == NULL: the number of records waiting, nothing removed. */
+int  mg_stream_geometry_fetch(int *out, int cap);
+
+/* ------------------------------------------------------------------------- */
 /* cycle-file driver: main() of src/MG_solver_CPU.cpp:36-462                   */
 /* ------------------------------------------------------------------------- */
 typedef struct mg_node_record {

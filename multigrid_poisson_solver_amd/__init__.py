@@ -128,7 +128,12 @@ ABI = {
     "mg_batch_solver_solve": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(BatchSolveStats)]),
     "mg_batch_solver_destroy": (None, [_vp]),
     "mg_profile_begin": (None, [_i]), "mg_profile_sample": (None, [_i]), "mg_profile_end": (_i, [C.POINTER(ProfileEntry), _i]),
+    "mg_stream_geometry_log": (None, [_i]), "mg_stream_geometry_fetch": (_i, [_vp, _i]),
 }
+
+# one record of the streaming smoother's geometry log (include/mg_hip.h: MG_STREAM_GEOMETRY_FIELDS ints, in this order)
+GEOMETRY_FIELDS = ("N", "own", "rows_per_chunk", "chunks", "groups", "instances", "S", "COLS", "IN", "RESTRICT", "PRE", "flags")
+MG_GEOMETRY_NT, MG_GEOMETRY_WT, MG_GEOMETRY_SH, MG_GEOMETRY_F32 = 1, 2, 4, 8
 
 # the symbols include/mg_fmg.h declares (the full-multigrid start's building blocks); a library without them -- an older
 # build named by MG_LIB for an A/B run -- still loads, cubic_table() / prolongCubic() then raise
@@ -612,6 +617,25 @@ def profile_end(cap=256):
     _check()
     return [dict(name=buf[i].name.decode(), N=buf[i].N, launches=buf[i].launches, total_ms=buf[i].total_ms,
                  algo_bytes=buf[i].algo_bytes) for i in range(n)]
+
+
+def stream_geometry_log(on=True):
+    """mg_stream_geometry_log: record how every launch of the streaming kernel is cut into chunks (host side, at enqueue)."""
+    lib().mg_stream_geometry_log(1 if on else 0)
+
+
+def stream_geometry_fetch():
+    """mg_stream_geometry_fetch: the records since the last fetch, one dict with the keys GEOMETRY_FIELDS per launch."""
+    out = []
+    while True:
+        n = lib().mg_stream_geometry_fetch(None, 0)
+        if n <= 0:
+            break
+        buf = np.empty((n, len(GEOMETRY_FIELDS)), dtype=np.int32)
+        got = _lib.mg_stream_geometry_fetch(buf.ctypes.data, n)
+        _check()
+        out += [dict(zip(GEOMETRY_FIELDS, (int(v) for v in row))) for row in buf[:got]]
+    return out
 
 
 class CyclePlan:

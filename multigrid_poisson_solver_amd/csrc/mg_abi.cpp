@@ -31,6 +31,18 @@ void fail(int code, const char *fmt, ...)
     if (c.abort_on_error) exit(1);  // the reference's convention: printf + exit(1)
 }
 
+constexpr int GEOMETRY_LOG_MAX = 65536;   // records the geometry log keeps between two fetches
+
+void stream_geometry_record(const int (&rec)[MG_STREAM_GEOMETRY_FIELDS])
+{
+    Context &c = ctx();
+    if (c.geometry.size() >= (size_t)GEOMETRY_LOG_MAX * MG_STREAM_GEOMETRY_FIELDS) {
+        c.geometry_dropped = true;
+        return;
+    }
+    c.geometry.insert(c.geometry.end(), rec, rec + MG_STREAM_GEOMETRY_FIELDS);
+}
+
 bool hip_ok(hipError_t e, const char *what, const char *file, int line)
 {
     if (e == hipSuccess) return true;
@@ -1263,6 +1275,30 @@ int mg_profile_end(mg_profile_entry *out, int cap)
     }
     c.prof.clear();
     return count;
+}
+
+// ------------------------------------------------------------------ geometry record of the streaming smoother
+void mg_stream_geometry_log(int on)
+{
+    Context &c = ctx();
+    c.geometry.clear();
+    c.geometry_dropped = false;
+    c.geometry_log = on != 0;
+}
+
+int mg_stream_geometry_fetch(int *out, int cap)
+{
+    Context &c = ctx();
+    const int have = (int)(c.geometry.size() / MG_STREAM_GEOMETRY_FIELDS);
+    if (!out) return have;
+    const int n = cap < 0 ? 0 : (cap < have ? cap : have);
+    memcpy(out, c.geometry.data(), (size_t)n * MG_STREAM_GEOMETRY_FIELDS * sizeof(int));
+    c.geometry.erase(c.geometry.begin(), c.geometry.begin() + (size_t)n * MG_STREAM_GEOMETRY_FIELDS);
+    if (c.geometry_dropped) {
+        c.geometry_dropped = false;
+        fail(MG_ERR_ARG, "mg_stream_geometry_fetch: the log was full (%d records), launches since then were not recorded", GEOMETRY_LOG_MAX);
+    }
+    return n;
 }
 
 int mg_recompute_pair_available(int pre, int post) { return k::stream_recompute_supported(pre, post) ? 1 : 0; }

@@ -153,6 +153,10 @@ struct Context {
     struct ProfRec { std::string name; int N; double bytes; hipEvent_t e0, e1; };
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> event_pool;
+    // geometry record of the streaming smoother (mg_stream_geometry_log/fetch): MG_STREAM_GEOMETRY_FIELDS ints per launch
+    bool geometry_log = false;
+    bool geometry_dropped = false;         // the log was full: a record was lost since the last fetch
+    std::vector<int> geometry;
 };
 
 // live kernel timing: RAII event pair around a launch (no-op unless profiling is on)
@@ -164,6 +168,8 @@ struct ProfScope {
 };
 
 Context &ctx();
+// one record of the geometry log (the streaming kernel's launcher calls it while ctx().geometry_log is set)
+void stream_geometry_record(const int (&rec)[MG_STREAM_GEOMETRY_FIELDS]);
 bool require_ready(const char *who);
 double *partials(size_t n);   // device scratch for at least n doubles
 Pool &scratch_pool();         // where operator-internal scratch comes from

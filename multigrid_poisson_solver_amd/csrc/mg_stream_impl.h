@@ -1149,6 +1149,10 @@ void launch_k(hipStream_t s, StreamParams p, double *err_out)
     p.rows_per_chunk = rows;
     p.groups = groups;
     p.n_blocks = chunks * groups;
+    if (ctx().geometry_log)   // (mg_stream_geometry_log: what this launch was cut into, for the tests that force a geometry)
+        stream_geometry_record({N, own, rows, chunks, groups, nb, S, COLS, IN, (int)RESTRICT, PRE,
+                                (NT ? MG_GEOMETRY_NT : 0) | (WT ? MG_GEOMETRY_WT : 0) | (SH ? MG_GEOMETRY_SH : 0) |
+                                    (sizeof(real_t) == 4 ? MG_GEOMETRY_F32 : 0)});
     p.part = nullptr;
 #ifdef MG_STREAM_TRACE
     static long long *trace_dev = nullptr;
