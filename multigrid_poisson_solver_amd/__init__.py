@@ -178,6 +178,19 @@ ABI_VC_BATCH = {
     "mg_batch_solver_has_coefficient": (_i, [_vp]),
 }
 
+# the symbols include/mg_krylov.h declares (restarted GCR(m) around the cycle of Solver); bound like ABI_FMG: a library
+# without them still loads, Solver(krylov=...) / Solver.set_krylov() / krylovDots() / ... then raise
+ABI_KRYLOV = {
+    "mg_solver_set_krylov": (_i, [_vp, _i]),
+    "mg_solver_krylov": (_i, [_vp]),
+    "mg_solver_krylov_breakdown": (_i, [_vp]),
+    "mg_solver_krylov_log": (_i, [_vp, _vp, _i]),
+    "mg_krylovDots": (None, [_i, _i, _vp, _vp, _vp]),
+    "mg_krylovOrth": (None, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mg_krylovUpdate": (None, [_i, _d, _vp, _vp, _vp, _vp, _vp]),
+}
+MG_KRYLOV_MAX_M = 16
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -236,7 +249,7 @@ def load_library(path=None):
     if missing:
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
-            list(ABI_VC_BATCH.items()):
+            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -603,6 +616,45 @@ def residualCoefficient(N, L, shift, a, U, F, D, sign=1):
     """Test hook (include/mg_varcoef.h).  mg_residualCoefficient on DeviceGrids: D = sign*(inv*b(U) - F) inside, sign*0 on the rim."""
     _need_vc("mg_residualCoefficient")(N, L, shift, a.ptr, U.ptr, F.ptr, D.ptr, sign)
     _check()
+
+
+def _need_krylov(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the Krylov acceleration)")
+    return getattr(_lib, name)
+
+
+def _pointer_array(views):
+    return (C.c_void_p * max(len(views), 1))(*[v.ptr for v in views])
+
+
+def krylovDots(N, q, Q):
+    """Test hook (include/mg_krylov.h).  mg_krylovDots on DeviceGrids: [<q, Q[j]>] over the interior, one pass."""
+    out = np.zeros(max(len(Q), 1))
+    _need_krylov("mg_krylovDots")(N, len(Q), q.ptr, _pointer_array(Q), out.ctypes.data)
+    _check()
+    return out[:len(Q)]
+
+
+def krylovOrth(N, b, q, z, r, Q, Z):
+    """Test hook (include/mg_krylov.h).  mg_krylovOrth on DeviceGrids: q -= b[j]*Q[j], z -= b[j]*Z[j] in order on the interior,
+    returns (<q, q>, <r, q>) of the updated q."""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    assert len(b) == len(Q) == len(Z)
+    gh = np.zeros(2)
+    _need_krylov("mg_krylovOrth")(N, len(Q), b.ctypes.data if len(b) else None, q.ptr, z.ptr, r.ptr, _pointer_array(Q),
+                                  _pointer_array(Z), gh.ctypes.data)
+    _check()
+    return float(gh[0]), float(gh[1])
+
+
+def krylovUpdate(N, alpha, U, z, r, q):
+    """Test hook (include/mg_krylov.h).  mg_krylovUpdate on DeviceGrids: U += alpha*z, r -= alpha*q on the interior, returns
+    <r, r> of the updated r."""
+    rr = np.zeros(1)
+    _need_krylov("mg_krylovUpdate")(N, float(alpha), U.ptr, z.ptr, r.ptr, q.ptr, rr.ctypes.data)
+    _check()
+    return float(rr[0])
 
 
 def profile_begin(min_N=0, every=1):
@@ -997,21 +1049,58 @@ class Solver:
     A U = Laplace(U) - sigma*U (solve_opts); an implicit time step has sigma = 1/(nu*dt), F = -u_old/(nu*dt).
     fmg=n (1..8) starts every solve from a full-multigrid guess instead of U's interior (solve_opts).
     coef=a (or set_coefficient(a)) solves div(a grad U) - sigma*U = F, a > 0 given at the grid points:
-        s = Solver(N, L, shift=sigma); s.set_coefficient(a); U, info = s.solve(F, U0); s.set_coefficient(None)"""
+        s = Solver(N, L, shift=sigma); s.set_coefficient(a); U, info = s.solve(F, U0); s.set_coefficient(None)
+    krylov=m (or set_krylov(m), 1 <= m <= 16) wraps the cycle in restarted GCR(m) with the V-cycle from a zero start as the
+    preconditioner (include/mg_krylov.h): the residual norm then cannot grow, and coefficients on which the plain cycle
+    is slow or diverges (jumps, strong contrast) converge.  It costs memory, (2m + 1)*N^2 doubles allocated when it is
+    switched on (8.7 GB at N = 8192 for m = 8), and 120 + 24k bytes per point and iteration.  Convergence is only stated on a
+    recomputed residual, never on the recurred norm; info gains `breakdown`.  krylov=0 (the default) is the plain solver, bit for bit."""
 
-    def __init__(self, N, L=1.0, coef=None, **opts):
+    def __init__(self, N, L=1.0, coef=None, krylov=0, **opts):
         self.N, self.L = int(N), float(L)
         self.opts = solve_opts(**opts)
         self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
         if not self._s:
             _check()
             raise MGError("mg_solver_create returned NULL")
-        if coef is not None:
-            try:
+        try:
+            if coef is not None:
                 self.set_coefficient(coef)
-            except Exception:
-                self.close()
-                raise
+            if krylov:
+                self.set_krylov(krylov)
+        except Exception:
+            self.close()
+            raise
+
+    def set_krylov(self, m):
+        """m = 1 .. 16: restarted GCR(m) around the cycle (include/mg_krylov.h), m directions kept between restarts; m = 0:
+        the plain cycle iteration again, bit for bit.  Switching it on allocates the memory it needs, (2m + 1)*N^2 doubles
+        (a later, larger m the additional slots); a solve allocates nothing.  Convergence is stated on a recomputed residual
+        only.  Works with and without a coefficient and with any shift.  A refusal (MGError: m outside [0, 16], "[3]" for a
+        solver created with fmg != 0, a failed allocation) leaves the solver as it was."""
+        status = _need_krylov("mg_solver_set_krylov")(self._s, int(m))
+        if status:
+            _check()
+            raise MGError(f"mg_solver_set_krylov failed with status {status}")
+
+    @property
+    def krylov(self):
+        """the m of set_krylov (0: off)"""
+        return int(_need_krylov("mg_solver_krylov")(self._s))
+
+    def krylov_log(self):
+        """Diagnostic and test hook (include/mg_krylov.h): one dict per iteration of the last accelerated solve with the keys
+        k, d (the k dot products <q_k, q_j>), g, h, alpha, rho_rec, restarted, rho."""
+        fn = _need_krylov("mg_solver_krylov_log")
+        n = fn(self._s, None, 0)
+        if n <= 0:
+            return []
+        m = self._krylov_log_m   # (the m of that solve, noted by solve_ptr: a record is m + 7 doubles)
+        buf = np.zeros((n, m + 7))
+        got = fn(self._s, buf.ctypes.data, n)
+        return [dict(k=int(rec[0]), d=[float(v) for v in rec[1:1 + int(rec[0])]], g=float(rec[m + 1]), h=float(rec[m + 2]),
+                     alpha=float(rec[m + 3]), rho_rec=float(rec[m + 4]), restarted=bool(rec[m + 5]), rho=float(rec[m + 6]))
+                for rec in buf[:got]]
 
     def set_coefficient(self, a):
         """a: N x N values of the coefficient at the grid points, rim included, finite and > 0 (numpy array, DeviceGrid or
@@ -1033,9 +1122,13 @@ class Solver:
             _check()
             raise MGError(f"mg_solver_solve failed with status {status}")
         history = [res.history[i] for i in range(res.n_history)]
-        return dict(status=res.status, cycles=res.cycles, converged=bool(res.converged),
+        info = dict(status=res.status, cycles=res.cycles, converged=bool(res.converged),
                     coarse_capped=bool(res.coarse_capped), res0=res.res0, res=res.res, ref_norm=res.ref_norm,
                     device_ms=res.device_ms, history=history)
+        if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))
+            info["breakdown"] = bool(_lib.mg_solver_krylov_breakdown(self._s))
+        return info
 
     def solve(self, F, U=None):
         """F, U: numpy arrays, DeviceGrid, or float64 torch CUDA tensors (worked on in place, on
@@ -1099,7 +1192,9 @@ def solve(F, U=None, L=1.0, **opts):
     rounding floor of large grids: about 8e-10 at N = 8192).  shift=sigma > 0 solves Laplace(U) - sigma*U = F, the
     equation of an implicit time step: sigma = 1/(nu*dt), F = -u_old/(nu*dt).  fmg=1 starts from a full-multigrid guess
     (U then only supplies the rim).  coef=a (N x N, > 0, at the grid points) solves div(a grad U) - sigma*U = F with faces
-    averaging their two nodes (Solver.set_coefficient); a == 1 everywhere is the solve without coef, bit for bit."""
+    averaging their two nodes (Solver.set_coefficient); a == 1 everywhere is the solve without coef, bit for bit.
+    krylov=m (1..16) wraps the cycle in restarted GCR(m) (Solver.set_krylov, include/mg_krylov.h): (2m + 1)*N^2 doubles of
+    memory more, a residual norm that cannot grow, and convergence stated on a recomputed residual only."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:

@@ -493,6 +493,32 @@ void coef_check_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *i
 // expression and its order: include/mg_heat_vc.h).  c.lap must be set: theta == 1 reads no coefficient and goes to heat_rhs.
 // F = rhs(A, U, Q) (Q == nullptr: no source); the rim of F is +0, nothing else is written
 void heat_rhs_vc(hipStream_t s, int N, const HeatConsts &c, const double *A, const double *U, const double *Q, double *F);
+// Krylov acceleration of the residual-tolerance solver (mg_krylov_kernels.hip, driven by mg_solve.cpp; the method and the
+// order of every operation: include/mg_krylov.h).  All sums run over the interior; no rim is read into a result or written.
+constexpr int KRYLOV_MAX_K = MG_KRYLOV_MAX_M - 1;   // stored directions an iteration orthogonalises against
+struct KrylovVecs {
+    const double *q[KRYLOV_MAX_K];
+    const double *z[KRYLOV_MAX_K];
+};
+// blocks of one launch over an N x N grid: every sum needs this many partials
+size_t krylov_blocks(int N);
+// d_out[j] = <q, v.q[j]> and, where w is given, b[j] = d_out[j]*w[j], j < k (1 <= k <= KRYLOV_MAX_K; part: k*krylov_blocks(N))
+void krylov_dots(hipStream_t s, int N, int k, const double *q, const KrylovVecs &v, double *part, const double *w, double *b,
+                 double *d_out);
+// q -= b[j]*v.q[j], z -= b[j]*v.z[j] for j = 0 .. k-1 in order (b: device, k doubles); the partials of <q, q> and <r, q> into
+// part (2*krylov_blocks(N))
+void krylov_orth(hipStream_t s, int N, int k, double *q, double *z, const double *r, const KrylovVecs &v, const double *b,
+                 double *part);
+// gh[0..1] = g, h.  alpha != nullptr (a solve): *w_k = 1/g, *alpha = h/g or 0 with *brk = 1.0 on a breakdown (else 0.0), and
+// where rec is given the head of the log record of m + 7 doubles
+void krylov_orth_finish(hipStream_t s, int N, const double *part, int k, int m, double *gh, double *w_k, double *alpha, double *brk,
+                        double *rec);
+// U += alpha*z, r -= alpha*q (*alpha == 0: neither is written); the partials of <r, r> into part (krylov_blocks(N))
+void krylov_update(hipStream_t s, int N, const double *alpha, double *U, const double *z, double *r, const double *q, double *part);
+// rr != nullptr: *rr = <r, r>.  rho_out != nullptr (a solve): *rho_out = sqrt of it, rec_tail[0..2] = rho_rec, 0, rho_rec
+void krylov_update_finish(hipStream_t s, int N, const double *part, double *rr, double *rho_out, double *rec_tail);
+// a restart's mark in the log record: rec_tail[1] = 1, rec_tail[2] = *rho
+void krylov_log_restart(hipStream_t s, double *rec_tail, const double *rho);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp

@@ -37,6 +37,17 @@ struct mg_solver {
     int *coef_flag = nullptr;                // device: the check found a value that is not finite or not > 0
     int *host_coef_flag = nullptr;           // pinned
     bool coef_set = false;
+    // Krylov acceleration (include/mg_krylov.h; nothing of it is allocated before the first enabling mg_solver_set_krylov)
+    int kr_m = 0;                            // 0: off
+    double *kr_r = nullptr;                  // the residual r
+    std::vector<double *> kr_Z, kr_Q;        // the slots z_j, q_j allocated so far (>= kr_m of each once enabled)
+    double *kr_part = nullptr;               // partials: KRYLOV_MAX_K stripes of krylov_blocks(N)
+    double *kr_scal = nullptr;               // device [KR_SCALARS]: b_j, w_j, alpha, rho_rec, breakdown
+    double *kr_log = nullptr;                // device: max(max_cycles, 1) records of KR_REC_MAX doubles
+    double *kr_host = nullptr;               // pinned [2]: rho_rec, breakdown
+    std::vector<double> kr_log_host;         // the last solve's records, kr_log_m + 7 doubles each
+    int kr_log_m = 0, kr_records = 0;
+    bool kr_breakdown = false;
 };
 
 namespace {
@@ -95,6 +106,10 @@ void release(mg_solver *s)
     for (double *p : s->coef) if (p) (void)hipFree(p);
     if (s->coef_flag) (void)hipFree(s->coef_flag);
     if (s->host_coef_flag) (void)hipHostFree(s->host_coef_flag);
+    for (auto *v : {&s->kr_Z, &s->kr_Q})
+        for (double *p : *v) if (p) (void)hipFree(p);
+    for (double *p : {s->kr_r, s->kr_part, s->kr_scal, s->kr_log}) if (p) (void)hipFree(p);
+    if (s->kr_host) (void)hipHostFree(s->kr_host);
     if (s->fmg_capped) (void)hipFree(s->fmg_capped);
     if (s->host_fmg_capped) (void)hipHostFree(s->host_fmg_capped);
     if (s->part) (void)hipFree(s->part);
@@ -373,6 +388,96 @@ bool read_back(mg_solver *s, hipStream_t st)
     return MG_HIP(hipEventSynchronize(s->ev_norm));
 }
 
+// ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov.h)
+constexpr int KR_B = 0, KR_W = MG_KRYLOV_MAX_M, KR_ALPHA = 2 * MG_KRYLOV_MAX_M, KR_RHO = KR_ALPHA + 1, KR_BRK = KR_ALPHA + 2,
+              KR_SCALARS = KR_ALPHA + 3;
+constexpr int KR_REC_MAX = MG_KRYLOV_MAX_M + 7;
+
+// r = -(inv*b(U) - F): the launch of the cycle's signed residual at level 0
+void krylov_residual(mg_solver *s, hipStream_t st, const double *F0, const double *U0)
+{
+    if (s->coef_set) k::residual_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->kr_r, -1);
+    else k::residual(st, s->N, s->lc[0].inv, U0, F0, s->kr_r, -1, s->lc[0].sh);
+}
+
+// the read-back of an iteration: rho_rec and the breakdown flag, the coarse solve's state and (with_norm: a restart) dev_scal
+bool krylov_read_back(mg_solver *s, hipStream_t st, bool with_norm)
+{
+    if (!MG_HIP(hipMemcpyAsync(s->kr_host, s->kr_scal + KR_RHO, 2 * sizeof(double), hipMemcpyDeviceToHost, st))) return false;
+    if (with_norm) return read_back(s, st);
+    if (!MG_HIP(hipMemcpyAsync(s->host_state, s->gs_state, 4 * sizeof(int), hipMemcpyDeviceToHost, st))) return false;
+    if (!MG_HIP(hipEventRecord(s->ev_norm, st))) return false;
+    return MG_HIP(hipEventSynchronize(s->ev_norm));
+}
+
+// the loop of include/mg_krylov.h from history[0] = *res on; false on a HIP error
+bool krylov_iterate(mg_solver *s, hipStream_t st, const double *F0, double *U0, double tol, mg_solve_result *r, double *res)
+{
+    const mg_solve_opts &o = s->o;
+    const int N = s->N, m = s->kr_m, rec_len = m + 7;
+    const size_t n = (size_t)N * N;
+    const double pts = (double)N * N;
+    s->kr_log_m = m;
+    s->kr_records = 0;
+    s->kr_breakdown = false;
+    int kk = 0;
+    if (!(*res <= tol) && r->cycles < o.max_cycles) krylov_residual(s, st, F0, U0);
+    while (!(*res <= tol) && r->cycles < o.max_cycles) {
+        double *z = s->kr_Z[kk], *q = s->kr_Q[kk];
+        double *rec = s->kr_log + (size_t)r->cycles * rec_len;
+        k::KrylovVecs v{};
+        for (int j = 0; j < kk; ++j) {
+            v.q[j] = s->kr_Q[j];
+            v.z[j] = s->kr_Z[j];
+        }
+        if (!MG_HIP(hipMemsetAsync(z, 0, n * sizeof(double), st))) return false;
+        vcycle(s, st, s->kr_r, z);
+        k::apply_vc(st, N, s->lc[0].inv, o.shift * s->lc[0].dx2, s->coef_set ? s->coef[0] : nullptr, z, q);
+        if (kk > 0) {
+            ProfScope ps("krylov_dots", N, pts * (8.0 + 8.0 * kk));
+            k::krylov_dots(st, N, kk, q, v, s->kr_part, s->kr_scal + KR_W, s->kr_scal + KR_B, rec + 1);
+        }
+        {
+            ProfScope ps("krylov_orth", N, pts * (kk > 0 ? 40.0 + 16.0 * kk : 16.0));
+            k::krylov_orth(st, N, kk, q, z, s->kr_r, v, s->kr_scal + KR_B, s->kr_part);
+        }
+        k::krylov_orth_finish(st, N, s->kr_part, kk, m, rec + 1 + m, s->kr_scal + KR_W + kk, s->kr_scal + KR_ALPHA, s->kr_scal + KR_BRK,
+                              rec);
+        {
+            ProfScope ps("krylov_update", N, pts * 48.0);
+            k::krylov_update(st, N, s->kr_scal + KR_ALPHA, U0, z, s->kr_r, q, s->kr_part);
+        }
+        k::krylov_update_finish(st, N, s->kr_part, nullptr, s->kr_scal + KR_RHO, rec + m + 4);
+        r->cycles += 1;
+        kk += 1;
+        bool restart = kk == m;   // (known here: the recomputation is enqueued behind the update and read with it)
+        if (!restart) {
+            if (!krylov_read_back(s, st, false)) return false;
+            *res = s->kr_host[0];
+            restart = *res <= tol;
+        }
+        if (restart) {
+            krylov_residual(s, st, F0, U0);
+            norm(s, st, F0, U0, 0);
+            k::krylov_log_restart(st, rec + m + 4, s->dev_scal);
+            if (!krylov_read_back(s, st, true)) return false;
+            *res = s->host_scal[0];
+            kk = 0;
+        }
+        s->history.push_back(*res);
+        s->kr_records = r->cycles;
+        if (s->host_state[2]) r->coarse_capped = 1;
+        if (s->kr_host[1] != 0.0) {
+            s->kr_breakdown = true;
+            break;
+        }
+    }
+    if (s->kr_records > 0 &&
+        !MG_HIP(hipMemcpyAsync(s->kr_log_host.data(), s->kr_log, (size_t)s->kr_records * rec_len * sizeof(double), hipMemcpyDeviceToHost, st)))
+        return false;
+    return true;
+}
+
 }  // namespace
 
 bool mg::solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o) { return opts_ok(who, N, L, o); }
@@ -518,11 +623,13 @@ int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_r
     s->history.push_back(res);
     const double tol = std::fmax(o.rtol * r.ref_norm, o.atol);
     const bool fmg = o.fmg >= 1 && !(res <= tol);
+    const bool krylov = s->kr_m > 0;   // (fmg == 0 with it: mg_solver_set_krylov refuses the combination)
+    if (krylov && !krylov_iterate(s, st, F_dev, U_dev, tol, &r, &res)) return finish(MG_ERR_HIP);
     if (fmg) {
         fmg_start(s, st, F_dev, U_dev);
         if (o.max_cycles == 0 && !read_back(s, st)) return finish(MG_ERR_HIP);   // (the loop's read-back otherwise)
     }
-    while (!(res <= tol) && r.cycles < o.max_cycles) {
+    while (!krylov && !(res <= tol) && r.cycles < o.max_cycles) {
         vcycle(s, st, F_dev, U_dev);
         norm(s, st, F_dev, U_dev, 0);
         if (!read_back(s, st)) return finish(MG_ERR_HIP);
@@ -683,6 +790,182 @@ void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, 
         k::residual_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, F, D, sign < 0 ? -1 : +1);
     }
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+// ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov.h)
+int mg_solver_set_krylov(mg_solver *s, int m)
+{
+    if (!require_ready("mg_solver_set_krylov")) return MG_ERR_NOT_INIT;
+    if (!s || m < 0 || m > MG_KRYLOV_MAX_M) {
+        fail(MG_ERR_ARG, "mg_solver_set_krylov: NULL solver, or m = %d outside [0, %d]", m, MG_KRYLOV_MAX_M);
+        return MG_ERR_ARG;
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_krylov: the solver was created with fmg = %d; the full-multigrid start is not "
+                                 "combined with the Krylov acceleration", s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    const int have = (int)s->kr_Z.size();
+    if (m > have) {   // the additional slots, and with the first of them r, the partials, the scalars and the log
+        const size_t n = (size_t)s->N * s->N;
+        const size_t n_part = (size_t)k::KRYLOV_MAX_K * k::krylov_blocks(s->N);
+        const size_t n_log = (size_t)(s->o.max_cycles > 0 ? s->o.max_cycles : 1) * KR_REC_MAX;
+        const bool first = s->kr_r == nullptr;
+        std::vector<double *> Z, Q;
+        double *r = nullptr, *part = nullptr, *scal = nullptr, *log = nullptr, *host = nullptr;
+        bool ok = true;
+        if (first)
+            ok = dev_alloc(&r, n) && dev_alloc(&part, n_part) && dev_alloc(&scal, (size_t)KR_SCALARS) && dev_alloc(&log, n_log) &&
+                 MG_HIP(hipHostMalloc((void **)&host, 2 * sizeof(double), hipHostMallocDefault)) &&
+                 MG_HIP(hipMemset(scal, 0, KR_SCALARS * sizeof(double)));
+        for (int j = have; j < m && ok; ++j) {
+            double *z = nullptr, *q = nullptr;
+            ok = dev_alloc(&z, n);
+            if (ok) Z.push_back(z);
+            ok = ok && dev_alloc(&q, n);
+            if (ok) Q.push_back(q);
+        }
+        if (!ok) {   // the solver keeps what it had
+            for (double *p : Z) (void)hipFree(p);
+            for (double *p : Q) (void)hipFree(p);
+            for (double *p : {r, part, scal, log}) if (p) (void)hipFree(p);
+            if (host) (void)hipHostFree(host);
+            return MG_ERR_HIP;
+        }
+        if (pool_poison_wanted()) {   // MG_POOL_POISON: no array starts from what hipMalloc happened to return
+            for (double *p : Z) poison_block(p, n * sizeof(double));
+            for (double *p : Q) poison_block(p, n * sizeof(double));
+            if (first) {
+                poison_block(r, n * sizeof(double));
+                poison_block(part, n_part * sizeof(double));
+                poison_block(log, n_log * sizeof(double));
+            }
+            (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+        }
+        if (first) {
+            s->kr_r = r;
+            s->kr_part = part;
+            s->kr_scal = scal;
+            s->kr_log = log;
+            s->kr_host = host;
+            s->kr_host[0] = s->kr_host[1] = 0.0;
+            s->kr_log_host.assign(n_log, 0.0);
+        }
+        s->kr_Z.insert(s->kr_Z.end(), Z.begin(), Z.end());
+        s->kr_Q.insert(s->kr_Q.end(), Q.begin(), Q.end());
+    }
+    s->kr_m = m;
+    return MG_OK;
+}
+
+int mg_solver_krylov(const mg_solver *s) { return s ? s->kr_m : 0; }
+
+int mg_solver_krylov_breakdown(const mg_solver *s) { return s && s->kr_m > 0 && s->kr_breakdown ? 1 : 0; }
+
+int mg_solver_krylov_log(const mg_solver *s, double *out, int cap)
+{
+    if (!s) return 0;
+    if (!out) return s->kr_records;
+    const int n = cap < s->kr_records ? (cap > 0 ? cap : 0) : s->kr_records;
+    if (n > 0) std::memcpy(out, s->kr_log_host.data(), (size_t)n * (s->kr_log_m + 7) * sizeof(double));
+    return n;
+}
+
+namespace {
+bool krylov_hook_ok(const char *who, int N, int k, std::initializer_list<const void *> arrays)
+{
+    if (N < 3 || k < 0 || k > k::KRYLOV_MAX_K) {
+        fail(MG_ERR_ARG, "%s: N = %d (at least 3), k = %d (0 .. %d)", who, N, k, k::KRYLOV_MAX_K);
+        return false;
+    }
+    for (const void *p : arrays)
+        if (!p || (uintptr_t)p % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: a NULL or not 16-byte aligned array", who);
+            return false;
+        }
+    return true;
+}
+}  // namespace
+
+void mg_krylovDots(int N, int k, const double *q, const double *const *Q, double *out)
+{
+    if (!require_ready("mg_krylovDots") || !krylov_hook_ok("mg_krylovDots", N, k, {q})) return;
+    if (k == 0) return;
+    if (!Q || !out) {
+        fail(MG_ERR_ARG, "mg_krylovDots: NULL Q or out");
+        return;
+    }
+    k::KrylovVecs v{};
+    for (int j = 0; j < k; ++j) {
+        if (!krylov_hook_ok("mg_krylovDots", N, k, {Q[j]})) return;
+        v.q[j] = Q[j];
+    }
+    Context &c = ctx();
+    double *part = partials((size_t)k * k::krylov_blocks(N));
+    if (!part) return;
+    {
+        ProfScope ps("krylov_dots", N, (double)N * N * (8.0 + 8.0 * k));
+        k::krylov_dots(c.stream, N, k, q, v, part, nullptr, nullptr, c.scalars);
+    }
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars, c.scalars, k * sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)))
+        std::memcpy(out, c.host_scalars, k * sizeof(double));
+}
+
+void mg_krylovOrth(int N, int k, const double *b, double *q, double *z, const double *r, const double *const *Q,
+                   const double *const *Z, double *gh)
+{
+    if (!require_ready("mg_krylovOrth") || !krylov_hook_ok("mg_krylovOrth", N, k, {q, z, r})) return;
+    if (!gh || (k > 0 && (!b || !Q || !Z))) {
+        fail(MG_ERR_ARG, "mg_krylovOrth: NULL b, Q, Z or gh");
+        return;
+    }
+    k::KrylovVecs v{};
+    for (int j = 0; j < k; ++j) {
+        if (!krylov_hook_ok("mg_krylovOrth", N, k, {Q[j], Z[j]})) return;
+        v.q[j] = Q[j];
+        v.z[j] = Z[j];
+    }
+    Context &c = ctx();
+    double *part = partials(2 * k::krylov_blocks(N));
+    if (!part) return;
+    // b at scalars[0 .. k), g and h at scalars[16 .. 18)
+    if (k > 0) {
+        std::memcpy(c.host_scalars, b, k * sizeof(double));
+        if (!MG_HIP(hipMemcpyAsync(c.scalars, c.host_scalars, k * sizeof(double), hipMemcpyHostToDevice, c.stream))) return;
+    }
+    {
+        ProfScope ps("krylov_orth", N, (double)N * N * (k > 0 ? 40.0 + 16.0 * k : 16.0));
+        k::krylov_orth(c.stream, N, k, q, z, r, v, c.scalars, part);
+    }
+    k::krylov_orth_finish(c.stream, N, part, k, 0, c.scalars + 16, nullptr, nullptr, nullptr, nullptr);
+    if (!MG_HIP(hipStreamSynchronize(c.stream))) return;   // (host_scalars is free again)
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars, c.scalars + 16, 2 * sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)))
+        std::memcpy(gh, c.host_scalars, 2 * sizeof(double));
+}
+
+void mg_krylovUpdate(int N, double alpha, double *U, const double *z, double *r, const double *q, double *rr)
+{
+    if (!require_ready("mg_krylovUpdate") || !krylov_hook_ok("mg_krylovUpdate", N, 0, {U, z, r, q})) return;
+    if (!rr) {
+        fail(MG_ERR_ARG, "mg_krylovUpdate: NULL rr");
+        return;
+    }
+    Context &c = ctx();
+    double *part = partials(k::krylov_blocks(N));
+    if (!part) return;
+    c.host_scalars[0] = alpha;
+    if (!MG_HIP(hipMemcpyAsync(c.scalars, c.host_scalars, sizeof(double), hipMemcpyHostToDevice, c.stream))) return;
+    {
+        ProfScope ps("krylov_update", N, (double)N * N * 48.0);
+        k::krylov_update(c.stream, N, c.scalars, U, z, r, q, part);
+    }
+    k::krylov_update_finish(c.stream, N, part, c.scalars + 16, nullptr, nullptr);
+    if (!MG_HIP(hipStreamSynchronize(c.stream))) return;
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars, c.scalars + 16, sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)))
+        *rr = c.host_scalars[0];
 }
 
 void mg_solver_destroy(mg_solver *s)
