@@ -191,6 +191,15 @@ ABI_KRYLOV = {
 }
 MG_KRYLOV_MAX_M = 16
 
+# the symbols include/mg_krylov_batch.h declares (GCR(m) per instance in the batched solver); bound like ABI_FMG: a library
+# without them still loads, BatchSolver.set_krylov() / solve_batched_krylov() then raise
+ABI_KRYLOV_BATCH = {
+    "mg_batch_solver_set_krylov": (_i, [_vp, _i]),
+    "mg_batch_solver_krylov": (_i, [_vp]),
+    "mg_batch_solver_krylov_breakdown": (_i, [_vp, _i]),
+    "mg_batch_solver_krylov_log": (_i, [_vp, _i, _vp, _i]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -249,7 +258,7 @@ def load_library(path=None):
     if missing:
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
-            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()):
+            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -1239,7 +1248,9 @@ class BatchSolver:
     sigma = 1/(nu*dt), F_i = -u_old_i/(nu*dt).  fmg != 0 (the full-multigrid start of Solver) is refused here.
     set_coefficient(a) solves div(a_i grad U_i) - sigma*U_i = F_i, one coefficient per instance or one shared by all, every
     instance bit-identical to Solver(coef=a_i) on it alone (include/mg_varcoef_batch.h):
-        b = BatchSolver(N, L, max_batch=B); b.set_coefficient(a); U, infos = b.solve(F, U0); b.set_coefficient(None)"""
+        b = BatchSolver(N, L, max_batch=B); b.set_coefficient(a); U, infos = b.solve(F, U0); b.set_coefficient(None)
+    set_krylov(m) wraps the cycle of every instance in restarted GCR(m) (include/mg_krylov_batch.h), every instance
+    bit-identical to Solver(krylov=m) on it alone: for coefficients on which the plain cycle crawls or diverges."""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -1304,10 +1315,45 @@ class BatchSolver:
         """0 without a coefficient, 1 with one shared by every instance, else the number of per-instance coefficients."""
         return int(_need_vc_batch("mg_batch_solver_has_coefficient")(self._s))
 
+    def set_krylov(self, m):
+        """m = 1 .. 16: restarted GCR(m) around the cycle, per instance (include/mg_krylov_batch.h; the method is
+        include/mg_krylov.h's), every launch over all active instances; m = 0: the plain batch solver again, bit for bit and
+        launch for launch.  Contract: instance i of a solve is bit-identical to Solver(krylov=m, coef=a_i) solving F_i, U_i
+        alone -- U, cycles, status, history, the breakdown flag and krylov_log(i) -- whatever the other instances are and
+        wherever it sits in the batch, with per-instance coefficients, a shared one or none, any shift, any V(pre, post).
+        Each instance runs with its own k, tolerance and restarts, and is stated converged on a recomputed residual only,
+        never on the recurred norm.  Memory: switching it on allocates (2m + 1)*N^2*max_batch doubles (N^2 rounded up to
+        32) plus small change; a later, larger m the additional slots; a solve allocates nothing.  Works before or after
+        set_coefficient.  A refusal (MGError: "[2]" for m outside [0, 16], a failed allocation) leaves the solver as it was."""
+        status = _need_krylov_batch("mg_batch_solver_set_krylov")(self._s, int(m))
+        if status:
+            _check()
+            raise MGError(f"mg_batch_solver_set_krylov failed with status {status}")
+
+    @property
+    def krylov(self):
+        """the m of set_krylov (0: off)"""
+        return int(_need_krylov_batch("mg_batch_solver_krylov")(self._s))
+
+    def krylov_log(self, i):
+        """Diagnostic and test hook (include/mg_krylov_batch.h): the records of instance i of the last accelerated solve, one
+        dict per iteration of that instance with the keys of Solver.krylov_log (k, d, g, h, alpha, rho_rec, restarted, rho);
+        [] for an instance that never iterated or an i outside that solve."""
+        fn = _need_krylov_batch("mg_batch_solver_krylov_log")
+        n = fn(self._s, int(i), None, 0)
+        if n <= 0:
+            return []
+        m = self._krylov_log_m   # (the m of that solve, noted by solve_ptrs: a record is m + 7 doubles)
+        buf = np.zeros((n, m + 7))
+        got = fn(self._s, int(i), buf.ctypes.data, n)
+        return [dict(k=int(rec[0]), d=[float(v) for v in rec[1:1 + int(rec[0])]], g=float(rec[m + 1]), h=float(rec[m + 2]),
+                     alpha=float(rec[m + 3]), rho_rec=float(rec[m + 4]), restarted=bool(rec[m + 5]), rho=float(rec[m + 6]))
+                for rec in buf[:got]]
+
     def solve_ptrs(self, F_ptrs, U_ptrs):
         """F_ptrs, U_ptrs: sequences of device addresses of N x N fp64 arrays (16-byte aligned; F addresses may repeat),
         on the engine stream.  Returns one info dict per instance (the keys of Solver.solve_ptr, plus `stats` of the
-        call: cycles = the most any instance ran, launches, device_ms)."""
+        call: cycles = the most any instance ran, launches, device_ms; with set_krylov on, `breakdown` too)."""
         n = len(U_ptrs)
         if len(F_ptrs) != n:
             raise MGError(f"{len(F_ptrs)} F pointers for {n} U pointers")
@@ -1325,6 +1371,10 @@ class BatchSolver:
             out.append(dict(status=r.status, cycles=r.cycles, converged=bool(r.converged), coarse_capped=bool(r.coarse_capped),
                             res0=r.res0, res=r.res, ref_norm=r.ref_norm, device_ms=r.device_ms,
                             history=[r.history[i] for i in range(r.n_history)], stats=stats))
+        if hasattr(_lib, "mg_batch_solver_krylov") and _lib.mg_batch_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_batch_solver_krylov(self._s))
+            for i, info in enumerate(out):
+                info["breakdown"] = bool(_lib.mg_batch_solver_krylov_breakdown(self._s, i))
         return out
 
     def solve(self, F, U=None):
@@ -1459,6 +1509,35 @@ def solve_batched_coef(F, a, U=None, L=1.0, **opts):
         return s.solve(F, U)
     finally:
         s.close()
+
+
+def solve_batched_krylov(F, m, U=None, L=1.0, coef=None, **opts):
+    """solve_batched with restarted GCR(m) around the cycle of every instance (BatchSolver.set_krylov, include/mg_krylov_batch.h);
+    returns (U, infos), infos[i] with `breakdown`.  coef: None, or what solve_batched_coef takes as a -- (N, N) shared by every
+    instance, or (B, N, N) / a sequence of B (N, N) ones; F and U as solve_batched takes them.  Every instance is
+    bit-identical to solve(F_i, U_i, L, coef=a_i, krylov=m, ...) alone, and is stated converged on a recomputed residual
+    only.  Allocates (2m + 1)*N^2*B doubles beside the batch solver's own arrays for the call."""
+    Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
+    if U is None:
+        B = 1 if shared else len(Fs)
+    else:
+        B = len(U) if isinstance(U, (list, tuple)) else (1 if isinstance(U, DeviceGrid) or len(U.shape) == 2 else int(U.shape[0]))
+    n_a = 0 if coef is None else len(coef) if isinstance(coef, (list, tuple)) else (int(coef.shape[0]) if len(coef.shape) == 3 else 1)
+    N = int(Fs[0].shape[-1])
+    s = BatchSolver(N, L, max_batch=max(B, n_a, 1), **opts)
+    try:
+        if coef is not None:
+            s.set_coefficient(coef)
+        s.set_krylov(m)
+        return s.solve(F, U)
+    finally:
+        s.close()
+
+
+def _need_krylov_batch(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched Krylov acceleration is not in this library)")
+    return getattr(_lib, name)
 
 
 def _need_vc_batch(name):

@@ -519,6 +519,36 @@ void krylov_update(hipStream_t s, int N, const double *alpha, double *U, const d
 void krylov_update_finish(hipStream_t s, int N, const double *part, double *rr, double *rho_out, double *rec_tail);
 // a restart's mark in the log record: rec_tail[1] = 1, rec_tail[2] = *rho
 void krylov_log_restart(hipStream_t s, double *rec_tail, const double *rho);
+// batched forms of the above (mg_krylov_batch_kernels.hip, driven by mg_solve_batch.cpp; include/mg_krylov_batch.h): one
+// launch over n instances, each running the code, the block partition and the summation order of its single launch (the
+// bodies are shared: mg_krylov_impl.h).  items[slot]: the arrays of the instance in that active slot; v: the slots of the
+// stored directions, each holding every instance at the instance pitch.
+struct KrylovBatchItem {
+    double *U, *r;       // the caller's U, the instance's residual
+    double *zk, *qk;     // this iteration's z_k, q_k
+    double *scal;        // its scalars, KRYLOV_SCAL_COUNT doubles
+    double *part;        // its partials, KRYLOV_MAX_K*krylov_blocks(N)
+    double *rec;         // its log record of this iteration, m + 7 doubles
+    size_t off;          // its offset (doubles) in every slot of the stored directions: z_j = v.z[j] + off
+    int k, pad;          // its stored directions so far
+};
+constexpr int KRYLOV_SCAL_B = 0, KRYLOV_SCAL_W = MG_KRYLOV_MAX_M, KRYLOV_SCAL_ALPHA = 2 * MG_KRYLOV_MAX_M,
+              KRYLOV_SCAL_BRK = KRYLOV_SCAL_ALPHA + 1, KRYLOV_SCAL_COUNT = KRYLOV_SCAL_ALPHA + 2;
+// z_k = +0, all N*N doubles
+void krylov_zero_batch(hipStream_t s, int n, int N, const KrylovBatchItem *items);
+// d_j = <q_k, q_j> into the record and b_j = d_j*w_j, j < the instance's k; kmax: the largest k of the n instances
+// (1 .. KRYLOV_MAX_K; instances at k = 0 are left alone).  Two launches.
+void krylov_dots_batch(hipStream_t s, int n, int N, int kmax, const KrylovBatchItem *items, const KrylovVecs &v);
+// the orthogonalisation against the instance's k directions, g, h, w_k, alpha, the breakdown flag and the head of the
+// record (kmax: 0 .. KRYLOV_MAX_K).  Two launches.
+void krylov_orth_batch(hipStream_t s, int n, int N, int kmax, int m, const KrylovBatchItem *items, const KrylovVecs &v);
+// U += alpha*z_k, r -= alpha*q_k, rho_rec and the tail of the record; rb[slot] = rho_rec, rb[stride + slot] = the breakdown
+// flag.  Two launches.
+void krylov_update_batch(hipStream_t s, int n, int N, int m, const KrylovBatchItem *items, double *rb, int stride);
+// a restart's mark in the records of n restarting instances: restarted = 1, rho = norms[slot]
+void krylov_log_restart_batch(hipStream_t s, int n, int m, const KrylovBatchItem *items, const double *norms);
+// A*z for n instances: in = z, coarse = a (nullptr for that instance: a = 1), out (mg_varcoef_batch_kernels.hip: apply_vc's body)
+void apply_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp

@@ -8,6 +8,8 @@
 // buffer serves every upload).
 // With a coefficient set (include/mg_varcoef_batch.h) the cycle is solve_vcycle_vc's instead (mg_solve.cpp), launch by launch
 // over the active set through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip): vcycle_vc_batch below.
+// With mg_batch_solver_set_krylov(m > 0) (include/mg_krylov_batch.h) the loop is restarted GCR(m) per instance around either
+// cycle: krylov_iterate_batch below, launch by launch over the active set (mg_krylov_batch_kernels.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -38,6 +40,22 @@ struct mg_batch_solver {
     int n_coef = 0;                          // 0: none set; 1: one shared by every instance; n > 1: instance i uses copy i
     int *coef_flags = nullptr;               // device [max_batch]: the check found a bad value in that instance
     int *host_coef_flags = nullptr;          // pinned [max_batch]
+    // Krylov acceleration (include/mg_krylov_batch.h; nothing of it is allocated before the first enabling
+    // mg_batch_solver_set_krylov).  Everything is indexed by the instance's position in the call, not by its active slot.
+    int kr_m = 0;                            // 0: off
+    double *kr_r = nullptr;                  // the residuals r_i, at the level-0 instance pitch
+    std::vector<double *> kr_Z, kr_Q;        // the slots allocated so far: slot j holds z_j (q_j) of max_batch instances at that pitch
+    double *kr_part = nullptr;               // partials: KRYLOV_MAX_K stripes of krylov_blocks(N) per instance
+    double *kr_scal = nullptr;               // device [max_batch][KRYLOV_SCAL_COUNT]: b_j, w_j, alpha, breakdown
+    double *kr_log = nullptr;                // device [max_batch][max(max_cycles, 1)] records of KR_REC_MAX doubles
+    double *kr_rb = nullptr, *kr_host_rb = nullptr;   // read-back by active slot: rho_rec[max_batch], breakdown[max_batch] (pinned twin)
+    void *kr_dev_tab = nullptr, *kr_host_tab = nullptr;   // one block, one upload: KrylovTables (below)
+    std::vector<double> kr_log_host;         // the last solve's records, per instance max(max_cycles, 1) of kr_log_m + 7 doubles
+    std::vector<int> kr_k, kr_records;       // per instance: its k, its records of the last solve
+    std::vector<char> kr_brk;                // per instance: the last solve ended on a breakdown
+    std::vector<const double *> kr_F;        // per instance: the cycle's F0 = r_i (MG_SMOOTHER=simple takes pointers by instance)
+    std::vector<double *> kr_U;              // per instance: the cycle's U0 = z_k of this iteration
+    int kr_log_m = 0, kr_n = 0;              // the m and the instances of the last accelerated solve
 };
 
 namespace {
@@ -82,6 +100,12 @@ void release(mg_batch_solver *s)
     for (double *p : s->coef) if (p) (void)hipFree(p);
     if (s->coef_flags) (void)hipFree(s->coef_flags);
     if (s->host_coef_flags) (void)hipHostFree(s->host_coef_flags);
+    for (double *p : s->kr_Z) if (p) (void)hipFree(p);
+    for (double *p : s->kr_Q) if (p) (void)hipFree(p);
+    for (double *p : {s->kr_r, s->kr_part, s->kr_scal, s->kr_log, s->kr_rb}) if (p) (void)hipFree(p);
+    if (s->kr_dev_tab) (void)hipFree(s->kr_dev_tab);
+    if (s->kr_host_rb) (void)hipHostFree(s->kr_host_rb);
+    if (s->kr_host_tab) (void)hipHostFree(s->kr_host_tab);
     if (s->part) (void)hipFree(s->part);
     if (s->dev_rb) (void)hipFree(s->dev_rb);
     if (s->host_rb) (void)hipHostFree(s->host_rb);
@@ -336,6 +360,188 @@ bool overlap(const void *a, const void *b, size_t bytes)
     return x < y + bytes && y < x + bytes;
 }
 
+
+// ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov_batch.h)
+constexpr int KR_REC_MAX = MG_KRYLOV_MAX_M + 7;
+
+// the tables of one iteration, one block in pinned and one in device memory, uploaded together: by active slot the Krylov
+// kernels' entries and A*z (in = z_k, coarse = a_i or NULL, out = q_k); by slot of the restarting subset the record to mark
+// and the residual and norm (in = U_i, F = F_i, coarse = a_i or NULL, out = r_i); `first` is the latter for the residual
+// that starts the loop, a table of its own because it is uploaded while the first iteration's tables are written
+struct KrylovTables {
+    k::KrylovBatchItem *act, *mark;
+    NodeBatchItem *apply, *recompute, *first;
+};
+size_t krylov_tables_bytes(int mb) { return (size_t)mb * (2 * sizeof(k::KrylovBatchItem) + 3 * sizeof(NodeBatchItem)); }
+KrylovTables krylov_tables(void *base, int mb)
+{
+    KrylovTables t;
+    t.act = static_cast<k::KrylovBatchItem *>(base);
+    t.mark = t.act + mb;
+    t.apply = reinterpret_cast<NodeBatchItem *>(t.mark + mb);
+    t.recompute = t.apply + mb;
+    t.first = t.recompute + mb;
+    return t;
+}
+size_t krylov_log_stride(const mg_batch_solver *s) { return (size_t)(s->o.max_cycles > 0 ? s->o.max_cycles : 1) * KR_REC_MAX; }
+
+// every table but `first` (which the call that starts the loop uploads alone)
+bool krylov_upload(mg_batch_solver *s, hipStream_t st)
+{
+    const size_t bytes = krylov_tables_bytes(s->max_batch) - (size_t)s->max_batch * sizeof(NodeBatchItem);
+    return MG_HIP(hipMemcpyAsync(s->kr_dev_tab, s->kr_host_tab, bytes, hipMemcpyHostToDevice, st));
+}
+
+// the read-back of an iteration: rho_rec and the breakdown flag of every active slot, and the block of read_back
+bool krylov_read_back(mg_batch_solver *s, hipStream_t st)
+{
+    if (!MG_HIP(hipMemcpyAsync(s->kr_host_rb, s->kr_rb, 2 * (size_t)s->max_batch * sizeof(double), hipMemcpyDeviceToHost, st))) return false;
+    return read_back(s, st);
+}
+
+// The loop of include/mg_krylov.h for every instance of `act` (those above their tolerance after history[0]), each with its
+// own k, tolerance and restart decisions; one launch per kernel of the single solver's iteration over the active set
+// (include/mg_krylov_batch.h).  false on a HIP error.
+bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const double *const *F_dev, double *const *U_dev,
+                          const std::vector<double> &tol, std::vector<mg_solve_result> &r, mg_batch_solve_stats &bs,
+                          std::vector<int> act)
+{
+    const mg_solve_opts &o = s->o;
+    const int N = s->N, m = s->kr_m, rec_len = m + 7, mb = s->max_batch;
+    const size_t p0 = s->pitch[0], n_part = (size_t)k::KRYLOV_MAX_K * k::krylov_blocks(N), log_stride = krylov_log_stride(s);
+    const double pts = (double)N * N, sd = o.shift * s->lc[0].dx2;
+    const bool vc = s->n_coef > 0, simple = ctx().smoother == SMOOTHER_SIMPLE;
+    const KrylovTables host = krylov_tables(s->kr_host_tab, mb), dev = krylov_tables(s->kr_dev_tab, mb);
+    s->kr_log_m = m;
+    s->kr_n = n;
+    for (int i = 0; i < n; ++i) {
+        s->kr_k[i] = s->kr_records[i] = 0;
+        s->kr_brk[i] = 0;
+    }
+    k::KrylovVecs v{};
+    for (int j = 0; j < m && j < k::KRYLOV_MAX_K; ++j) {
+        v.q[j] = s->kr_Q[j];
+        v.z[j] = s->kr_Z[j];
+    }
+    auto coef_of = [&](int i) -> const double * { return vc ? level(s, s->coef, 0, s->n_coef == 1 ? 0 : i) : nullptr; };
+    auto rec_of = [&](int i) { return s->kr_log + (size_t)i * log_stride + (size_t)r[i].cycles * rec_len; };
+    // r = -(inv*b(U) - F) and ||F - AU|| of the instances `sub`, whose table entries are uploaded: the launches of the
+    // batched cycle's signed residual at level 0 and of the stopping norm, into rb_res by slot of `sub`
+    auto fill_recompute = [&](const std::vector<int> &sub) {
+        for (size_t js = 0; js < sub.size(); ++js) {
+            const int i = sub[js];
+            host.recompute[js] = NodeBatchItem{U_dev[i], F_dev[i], coef_of(i), s->kr_r + (size_t)i * p0, nullptr};
+            host.mark[js] = k::KrylovBatchItem{};
+            host.mark[js].rec = rec_of(i);
+        }
+    };
+    auto residual = [&](int ns, const NodeBatchItem *items) {
+        ProfScope ps("krylov_residual_batch", N, pts * ns * (vc ? 32.0 : 24.0));
+        if (vc) k::residual_vc_batch(st, ns, N, s->lc[0].inv, sd, items, -1);
+        else k::residual_batch(st, ns, N, s->lc[0].inv, items, -1, s->lc[0].sh);
+        return 1;
+    };
+    auto recompute = [&](int ns) {
+        int launches = residual(ns, dev.recompute);
+        if (vc) k::resnorm_vc_batch(st, ns, N, s->lc[0].inv, sd, dev.recompute, s->part, rb_res(s->dev_rb));
+        else k::resnorm_batch(st, ns, N, s->lc[0].inv, true, dev.recompute, s->part, rb_res(s->dev_rb), s->lc[0].sh);
+        k::krylov_log_restart_batch(st, ns, m, dev.mark, rb_res(s->dev_rb));
+        return launches + 3;
+    };
+    if (act.empty()) return true;
+    for (size_t j = 0; j < act.size(); ++j)
+        host.first[j] = NodeBatchItem{U_dev[act[j]], F_dev[act[j]], coef_of(act[j]), s->kr_r + (size_t)act[j] * p0, nullptr};
+    if (!MG_HIP(hipMemcpyAsync(dev.first, host.first, act.size() * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st))) return false;
+    bs.launches += residual((int)act.size(), dev.first);
+    std::vector<int> known, late, next;   // restarts known before the read-back (k + 1 == m), and found by it
+    std::vector<double> res(n, 0.0);
+    while (!act.empty()) {
+        const int na = (int)act.size();
+        int kmax = 0;
+        double dots_bytes = 0.0, orth_bytes = 0.0;
+        known.clear();
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j], kk = s->kr_k[i];
+            double *ri = s->kr_r + (size_t)i * p0, *z = s->kr_Z[kk] + (size_t)i * p0, *q = s->kr_Q[kk] + (size_t)i * p0;
+            s->kr_F[i] = ri;
+            s->kr_U[i] = z;
+            (vc ? fill_tables_vc : fill_tables)(s, j, ri, z, i);
+            host.act[j] = k::KrylovBatchItem{U_dev[i], ri, z, q, s->kr_scal + (size_t)i * k::KRYLOV_SCAL_COUNT,
+                                             s->kr_part + (size_t)i * n_part, rec_of(i), (size_t)i * p0, kk, 0};
+            host.apply[j] = NodeBatchItem{z, nullptr, coef_of(i), q, nullptr};
+            if (kk > kmax) kmax = kk;
+            dots_bytes += kk > 0 ? 8.0 + 8.0 * kk : 0.0;
+            orth_bytes += kk > 0 ? 40.0 + 16.0 * kk : 16.0;
+            if (kk + 1 == m) known.push_back(i);
+        }
+        fill_recompute(known);
+        if (!upload_tables(s, st) || !krylov_upload(s, st)) return false;
+        {
+            ProfScope ps("krylov_zero_batch", N, pts * na * 8.0);
+            k::krylov_zero_batch(st, na, N, dev.act);
+        }
+        bs.launches += 1;
+        bs.launches += vc ? vcycle_vc_batch(s, st, na)
+                          : simple ? vcycle_simple_each(s, st, act, s->kr_F.data(), s->kr_U.data()) : vcycle_batch(s, st, na);
+        {
+            ProfScope ps("krylov_apply_batch", N, pts * na * (vc ? 24.0 : 16.0));
+            k::apply_vc_batch(st, na, N, s->lc[0].inv, sd, dev.apply);
+        }
+        bs.launches += 1;
+        if (kmax > 0) {
+            ProfScope ps("krylov_dots_batch", N, pts * dots_bytes);
+            k::krylov_dots_batch(st, na, N, kmax, dev.act, v);
+            bs.launches += 2;
+        }
+        {
+            ProfScope ps("krylov_orth_batch", N, pts * orth_bytes);
+            k::krylov_orth_batch(st, na, N, kmax, m, dev.act, v);
+        }
+        {
+            ProfScope ps("krylov_update_batch", N, pts * na * 48.0);
+            k::krylov_update_batch(st, na, N, m, dev.act, s->kr_rb, mb);
+        }
+        bs.launches += 4;
+        if (!known.empty()) bs.launches += recompute((int)known.size());
+        if (!krylov_read_back(s, st)) return false;
+        late.clear();
+        size_t at_known = 0;
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j];
+            if (at_known < known.size() && known[at_known] == i) {
+                res[i] = rb_res(s->host_rb)[at_known++];
+            } else {
+                res[i] = s->kr_host_rb[j];
+                if (res[i] <= tol[i]) late.push_back(i);
+            }
+            if (rb_state(s->host_rb, mb)[4 * j + 2]) r[i].coarse_capped = 1;
+            if (s->kr_host_rb[mb + j] != 0.0) s->kr_brk[i] = 1;
+        }
+        if (!late.empty()) {   // the recurred norm met the tolerance: the recomputed one decides
+            fill_recompute(late);
+            if (!krylov_upload(s, st)) return false;
+            bs.launches += recompute((int)late.size());
+            if (!read_back(s, st)) return false;
+            for (size_t js = 0; js < late.size(); ++js) res[late[js]] = rb_res(s->host_rb)[js];
+        }
+        for (int i : known) s->kr_k[i] = -1;
+        for (int i : late) s->kr_k[i] = -1;
+        next.clear();
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j];
+            r[i].cycles += 1;
+            s->kr_k[i] += 1;   // (0 after a restart)
+            s->kr_records[i] = r[i].cycles;
+            r[i].res = res[i];
+            s->history[i].push_back(res[i]);
+            if (r[i].cycles > bs.cycles) bs.cycles = r[i].cycles;
+            if (!s->kr_brk[i] && !(res[i] <= tol[i]) && r[i].cycles < o.max_cycles) next.push_back(i);
+        }
+        act.swap(next);
+    }
+    return MG_HIP(hipMemcpyAsync(s->kr_log_host.data(), s->kr_log, (size_t)n * log_stride * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
 }  // namespace
 
 extern "C" {
@@ -490,6 +696,10 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
         tol[i] = std::fmax(o.rtol * r[i].ref_norm, o.atol);
         if (!(r[i].res <= tol[i]) && o.max_cycles > 0) next.push_back(i);
     }
+    if (s->kr_m > 0) {   // (the plain loop below then has nothing to do)
+        if (!krylov_iterate_batch(s, st, n, F_dev, U_dev, tol, r, bs, next)) return finish(MG_ERR_HIP);
+        next.clear();
+    }
     while (!next.empty()) {
         if (next != act) {   // the active set changed: compact it, rebuild and upload the tables
             act.swap(next);
@@ -628,5 +838,99 @@ int mg_batch_solver_set_coefficient(mg_batch_solver *s, int n, const double *con
 }
 
 int mg_batch_solver_has_coefficient(const mg_batch_solver *s) { return s ? s->n_coef : 0; }
+
+// ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov_batch.h)
+int mg_batch_solver_set_krylov(mg_batch_solver *s, int m)
+{
+    if (!require_ready("mg_batch_solver_set_krylov")) return MG_ERR_NOT_INIT;
+    if (!s || m < 0 || m > MG_KRYLOV_MAX_M) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_krylov: NULL solver, or m = %d outside [0, %d]", m, MG_KRYLOV_MAX_M);
+        return MG_ERR_ARG;
+    }
+    const int have = (int)s->kr_Z.size(), mb = s->max_batch;
+    if (m > have) {   // the additional slots, and with the first of them r, the partials, the scalars, the log and the tables
+        const size_t n_field = s->pitch[0] * mb;
+        const size_t n_part = (size_t)k::KRYLOV_MAX_K * k::krylov_blocks(s->N) * mb;
+        const size_t n_scal = (size_t)k::KRYLOV_SCAL_COUNT * mb, n_log = krylov_log_stride(s) * mb;
+        const bool first = s->kr_r == nullptr;
+        auto dev_alloc = [](double **p, size_t count) { return MG_HIP(hipMalloc((void **)p, count * sizeof(double))); };
+        std::vector<double *> Z, Q;
+        double *r = nullptr, *part = nullptr, *scal = nullptr, *log = nullptr, *rb = nullptr, *host_rb = nullptr;
+        void *dev_tab = nullptr, *host_tab = nullptr;
+        bool ok = true;
+        if (first)
+            ok = dev_alloc(&r, n_field) && dev_alloc(&part, n_part) && dev_alloc(&scal, n_scal) && dev_alloc(&log, n_log) &&
+                 dev_alloc(&rb, 2 * (size_t)mb) && MG_HIP(hipMalloc(&dev_tab, krylov_tables_bytes(mb))) &&
+                 MG_HIP(hipHostMalloc((void **)&host_rb, 2 * (size_t)mb * sizeof(double), hipHostMallocDefault)) &&
+                 MG_HIP(hipHostMalloc(&host_tab, krylov_tables_bytes(mb), hipHostMallocDefault)) &&
+                 MG_HIP(hipMemset(scal, 0, n_scal * sizeof(double))) && MG_HIP(hipMemset(rb, 0, 2 * (size_t)mb * sizeof(double)));
+        for (int j = have; j < m && ok; ++j) {
+            double *z = nullptr, *q = nullptr;
+            ok = dev_alloc(&z, n_field);
+            if (ok) Z.push_back(z);
+            ok = ok && dev_alloc(&q, n_field);
+            if (ok) Q.push_back(q);
+        }
+        if (!ok) {   // the solver keeps what it had
+            for (double *p : Z) (void)hipFree(p);
+            for (double *p : Q) (void)hipFree(p);
+            for (double *p : {r, part, scal, log, rb}) if (p) (void)hipFree(p);
+            if (dev_tab) (void)hipFree(dev_tab);
+            if (host_rb) (void)hipHostFree(host_rb);
+            if (host_tab) (void)hipHostFree(host_tab);
+            return MG_ERR_HIP;
+        }
+        if (pool_poison_wanted()) {   // MG_POOL_POISON: no array starts from what hipMalloc happened to return
+            for (double *p : Z) poison_block(p, n_field * sizeof(double));
+            for (double *p : Q) poison_block(p, n_field * sizeof(double));
+            if (first) {
+                poison_block(r, n_field * sizeof(double));
+                poison_block(part, n_part * sizeof(double));
+                poison_block(log, n_log * sizeof(double));
+            }
+            (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+        }
+        if (first) {
+            s->kr_r = r;
+            s->kr_part = part;
+            s->kr_scal = scal;
+            s->kr_log = log;
+            s->kr_rb = rb;
+            s->kr_host_rb = host_rb;
+            s->kr_dev_tab = dev_tab;
+            s->kr_host_tab = host_tab;
+            std::memset(host_tab, 0, krylov_tables_bytes(mb));
+            std::memset(host_rb, 0, 2 * (size_t)mb * sizeof(double));
+            s->kr_log_host.assign(n_log, 0.0);
+            s->kr_k.assign(mb, 0);
+            s->kr_records.assign(mb, 0);
+            s->kr_brk.assign(mb, 0);
+            s->kr_F.assign(mb, nullptr);
+            s->kr_U.assign(mb, nullptr);
+        }
+        s->kr_Z.insert(s->kr_Z.end(), Z.begin(), Z.end());
+        s->kr_Q.insert(s->kr_Q.end(), Q.begin(), Q.end());
+    }
+    s->kr_m = m;
+    return MG_OK;
+}
+
+int mg_batch_solver_krylov(const mg_batch_solver *s) { return s ? s->kr_m : 0; }
+
+int mg_batch_solver_krylov_breakdown(const mg_batch_solver *s, int i)
+{
+    return s && s->kr_m > 0 && i >= 0 && i < s->kr_n && s->kr_brk[i] ? 1 : 0;
+}
+
+int mg_batch_solver_krylov_log(const mg_batch_solver *s, int i, double *out, int cap)
+{
+    if (!s || i < 0 || i >= s->kr_n) return 0;
+    const int have = s->kr_records[i];
+    if (!out) return have;
+    const int n = cap < have ? (cap > 0 ? cap : 0) : have;
+    if (n > 0)
+        std::memcpy(out, s->kr_log_host.data() + (size_t)i * krylov_log_stride(s), (size_t)n * (s->kr_log_m + 7) * sizeof(double));
+    return n;
+}
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 //   residual, norm   in = U, F, coarse = a, out = D (the norm: none; partials at part + z*resnorm_partials(N))
 //   coarse solve     F, coarse = a, out = U; state at state + 4*instance
 //   coarsening       in = a_f, out = a_c          check   in = a; flag at flags + instance
+//   operator alone   in = U, coarse = a (may be null for an instance: a = 1), out
 // N, dx2, inv, sd and omega are the same for every instance of a launch and stay kernel arguments.
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,15 @@ __global__ __launch_bounds__(TB) void k_residual_vc_b(int N, double inv, double 
     const VcArgs k = item_args(items[blockIdx.z], N, 0.0, inv, sd, 0.0, sign);
     if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true>(k);
     else vc_cols<OP_RESIDUAL>(k);
+}
+
+// the operator alone (apply_vc): the coefficient may be absent PER INSTANCE (a = 1 through the same expressions, as the
+// single kernel without one); the choice is the same for every lane of a block
+__global__ __launch_bounds__(TB) void k_apply_vc_b(int N, double inv, double sd, const NodeBatchItem *__restrict__ items)
+{
+    const VcArgs k = item_args(items[blockIdx.z], N, 0.0, inv, sd, 0.0, +1);
+    if (k.A) vc_cols<OP_APPLY, true>(k);
+    else vc_cols<OP_APPLY, false>(k);
 }
 
 // instance z's np partials at part + z*np
@@ -115,6 +125,11 @@ void residual_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const
 {
     if (use_pairs(N)) hipLaunchKernelGGL(k_residual_vc_b<true>, with_instances(grid_pairs(N), n), dim3(TB), 0, s, N, inv, sd, items, sign);
     else hipLaunchKernelGGL(k_residual_vc_b<false>, with_instances(grid_rows(N), n), dim3(TB), 0, s, N, inv, sd, items, sign);
+}
+
+void apply_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items)
+{
+    hipLaunchKernelGGL(k_apply_vc_b, with_instances(grid_rows(N), n), dim3(TB), 0, s, N, inv, sd, items);
 }
 
 void resnorm_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items, double *part, double *out)
