@@ -200,6 +200,17 @@ ABI_KRYLOV_BATCH = {
     "mg_batch_solver_krylov_log": (_i, [_vp, _i, _vp, _i]),
 }
 
+# the symbols include/mg_adjoint.h declares (adjoint sensitivities: gradients of a solve in F, the rim data and a(x, y));
+# bound like ABI_FMG: a library without them still loads, coefficientGradient() / Solver.adjoint() / ... then raise
+ABI_ADJOINT = {
+    "mg_coefficientGradient": (None, [_i, _d, _vp, _vp, _vp]),
+    "mg_boundaryGradient": (None, [_i, _d, _vp, _vp, _vp, _vp]),
+    "mg_coefficientGradient_batch": (None, [_i, _i, _d, _vp, _vp, _vp]),
+    "mg_boundaryGradient_batch": (None, [_i, _i, _d, _vp, _vp, _vp, _vp]),
+    "mg_solver_adjoint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SolveResult)]),
+    "mg_batch_solver_adjoint": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BatchSolveStats)]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -258,7 +269,7 @@ def load_library(path=None):
     if missing:
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
-            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()):
+            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -1179,6 +1190,79 @@ class Solver:
         info = self.solve_ptr(Fd.ptr, Ud.ptr)
         return (Ud.to_host() if host_U else Ud), info
 
+    def adjoint_ptr(self, Ubar_ptr, U_ptr, lam_ptr, gA_ptr=None, gU_ptr=None):
+        """mg_solver_adjoint on device addresses of N x N fp64 arrays, on the engine stream: lam (out) = the adjoint field of
+        the right-hand side Ubar, gA (out, or None) = the gradient in the coefficient from lam and the forward solution U,
+        gU (out, or None) = the gradient in the rim data.  Returns the info dict of solve_ptr for the adjoint solve."""
+        res = SolveResult()
+        status = _need_adjoint("mg_solver_adjoint")(self._s, Ubar_ptr, U_ptr, lam_ptr, gA_ptr, gU_ptr, C.byref(res))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_solver_adjoint failed with status {status}")
+        info = _solve_info(res)
+        if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))
+            info["breakdown"] = bool(_lib.mg_solver_krylov_breakdown(self._s))
+        return info
+
+    def adjoint(self, Ubar, U, want_coef=True, want_rim=True):
+        """The adjoint of a solve of this solver (include/mg_adjoint.h): for a functional J(U) of the solution U of
+        div(a grad U) - sigma*U = F with Ubar = dJ/dU (N x N; its rim entries are the direct dependence of J on the rim
+        values), returns (lam, gA, gU, info):
+          lam   the adjoint field, the solve of the same equation -- coefficient, shift, krylov, fmg as set -- with
+                right-hand side Ubar from the zero field; dJ/dF is lam on the interior and 0 on the rim
+          gA    dJ/da at every grid point, rim included (want_coef; None otherwise).  Without a coefficient set it is
+                the sensitivity at a == 1
+          gU    dJ/d(rim data) as an N x N array: 0 inside, Ubar at the corners (want_rim; None otherwise)
+          info  the dict of solve() for the adjoint solve; a solve that did not converge still gives the gradients
+        Ubar, U: numpy arrays (results are new numpy arrays), DeviceGrids (results are DeviceGrids) or float64 torch CUDA
+        tensors (results are tensors; on torch.cuda.current_stream()), handled as solve() handles them.  Bit for bit the
+        sequence {zero fill, solve, coefficientGradient, boundaryGradient} made by the caller."""
+        N = self.N
+        if _is_torch(Ubar) or _is_torch(U):
+            import torch
+            for name, t in (("Ubar", Ubar), ("U", U)):
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N) and t.is_contiguous()):
+                    raise MGError(f"{name}: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            dev = Ubar.device
+            (ub_ptr,), ub_buf = _staged([Ubar], False, N * N, dev)
+            (u_ptr,), u_buf = _staged([U], False, N * N, dev)
+            lam = torch.empty((N, N), dtype=torch.float64, device=dev)
+            gA = torch.empty((N, N), dtype=torch.float64, device=dev) if want_coef else None
+            gU = torch.empty((N, N), dtype=torch.float64, device=dev) if want_rim else None
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            try:
+                info = self.adjoint_ptr(ub_ptr, u_ptr, lam.data_ptr(), gA.data_ptr() if want_coef else None,
+                                        gU.data_ptr() if want_rim else None)
+            finally:
+                _lib.mg_set_stream(prev)
+            del ub_buf, u_buf
+            return lam, gA, gU, info
+        keep = []
+
+        def dev(a, what):
+            if hasattr(a, "ptr") and hasattr(a, "shape"):
+                if tuple(a.shape) != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        host = not (hasattr(Ubar, "ptr") and hasattr(U, "ptr"))
+        Ud, Ub = dev(U, "U"), dev(Ubar, "Ubar")
+        lam = DeviceGrid((N, N))
+        gA = DeviceGrid((N, N)) if want_coef else None
+        gU = DeviceGrid((N, N)) if want_rim else None
+        info = self.adjoint_ptr(Ub.ptr, Ud.ptr, lam.ptr, gA.ptr if want_coef else None, gU.ptr if want_rim else None)
+        if host:
+            return lam.to_host(), gA.to_host() if want_coef else None, gU.to_host() if want_rim else None, info
+        return lam, gA, gU, info
+
     def close(self):
         if getattr(self, "_s", None) and _initialised:
             _lib.mg_solver_destroy(self._s)
@@ -1461,6 +1545,108 @@ class BatchSolver:
             return np.stack([u.to_host() for u in Ud]), infos
         return Ud, infos
 
+    def adjoint_ptrs(self, Ubar_ptrs, U_ptrs, lam_ptrs, gA_ptrs=None, gU_ptrs=None):
+        """mg_batch_solver_adjoint on sequences of device addresses (one N x N fp64 array per instance, 16-byte aligned), on the
+        engine stream; gA_ptrs / gU_ptrs = None: that gradient is not wanted.  Returns one info dict per instance, as
+        solve_ptrs does (stats.launches counts the two gradient launches too)."""
+        n = len(lam_ptrs)
+        arr = lambda ps: None if ps is None else (C.c_void_p * max(n, 1))(*ps)
+        for ps in (Ubar_ptrs, U_ptrs, gA_ptrs, gU_ptrs):
+            if ps is not None and len(ps) != n:
+                raise MGError(f"{len(ps)} pointers for {n} instances")
+        res = (SolveResult * max(n, 1))()
+        st = BatchSolveStats()
+        status = _need_adjoint("mg_batch_solver_adjoint")(self._s, n, arr(Ubar_ptrs), arr(U_ptrs), arr(lam_ptrs), arr(gA_ptrs),
+                                                          arr(gU_ptrs), res, C.byref(st))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_batch_solver_adjoint failed with status {status}")
+        stats = dict(status=status, cycles=st.cycles, launches=st.launches, device_ms=st.device_ms)
+        out = [dict(_solve_info(r), stats=stats) for r in res[:n]]
+        if hasattr(_lib, "mg_batch_solver_krylov") and _lib.mg_batch_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_batch_solver_krylov(self._s))
+            for i, info in enumerate(out):
+                info["breakdown"] = bool(_lib.mg_batch_solver_krylov_breakdown(self._s, i))
+        return out
+
+    def adjoint(self, Ubar, U, want_coef=True, want_rim=True):
+        """Solver.adjoint for B instances in one call (include/mg_adjoint.h): returns (lam, gA, gU, infos), every instance
+        bit-identical to Solver(coef=a_i).adjoint(Ubar_i, U_i) alone.  The adjoint solves run as one batched solve and each
+        gradient is ONE launch over all instances, those that left the batch early included.  Ubar, U: numpy arrays
+        [B, N, N] (results are numpy arrays [B, N, N]), float64 torch CUDA tensors [B, N, N] (results are tensors; on
+        torch.cuda.current_stream()) or lists of B (N, N) arrays / tensors / DeviceGrids (DeviceGrids give lists of
+        DeviceGrids).  With a coefficient shared by the instances gA[i] is instance i's own sensitivity; the gradient in the
+        shared a is the caller's sum over i."""
+        N, nn = self.N, self.N * self.N
+        first = Ubar[0] if isinstance(Ubar, (list, tuple)) else Ubar
+        if _is_torch(first):
+            import torch
+            Ubs, _ = _instances(Ubar, "Ubar")
+            Us, _ = _instances(U, "U")
+            if len(Ubs) != len(Us):
+                raise MGError(f"{len(Ubs)} Ubar instances for {len(Us)} U instances")
+            for name, ts in (("Ubar", Ubs), ("U", Us)):
+                for t in ts:
+                    if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N) and t.is_contiguous()):
+                        raise MGError(f"{name}: expected contiguous float64 CUDA tensors of shape ({N}, {N})")
+            dev, B = Ubs[0].device, len(Ubs)
+            ub_ptrs, ub_buf = _staged(Ubs, False, nn, dev)
+            u_ptrs, u_buf = _staged(Us, False, nn, dev)
+            pitch = nn + nn % 2   # (every instance of an output 16-byte aligned)
+
+            def out():
+                return torch.empty((B, pitch), dtype=torch.float64, device=dev)
+
+            def ptrs(buf):
+                return None if buf is None else [buf[i].data_ptr() for i in range(B)]
+
+            def done(buf):
+                return None if buf is None else buf[:, :nn].reshape(B, N, N)
+
+            lam, gA, gU = out(), out() if want_coef else None, out() if want_rim else None
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            try:
+                infos = self.adjoint_ptrs(ub_ptrs, u_ptrs, ptrs(lam), ptrs(gA), ptrs(gU))
+            finally:
+                _lib.mg_set_stream(prev)
+            del ub_buf, u_buf
+            return done(lam), done(gA), done(gU), infos
+        keep = []
+
+        def dev(a, what):
+            if hasattr(a, "ptr") and hasattr(a, "shape"):
+                if tuple(a.shape) != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        def many(X, what):
+            if hasattr(X, "ptr"):
+                return [X]
+            return _instances(X if isinstance(X, (list, tuple)) else np.asarray(X), what)[0]
+
+        Ubs, Us = many(Ubar, "Ubar"), many(U, "U")
+        if len(Ubs) != len(Us):
+            raise MGError(f"{len(Ubs)} Ubar instances for {len(Us)} U instances")
+        host = not all(hasattr(x, "ptr") for x in list(Ubs) + list(Us))
+        Ub, Ud = [dev(x, "Ubar") for x in Ubs], [dev(x, "U") for x in Us]
+        B = len(Ub)
+        lam = [DeviceGrid((N, N)) for _ in range(B)]
+        gA = [DeviceGrid((N, N)) for _ in range(B)] if want_coef else None
+        gU = [DeviceGrid((N, N)) for _ in range(B)] if want_rim else None
+        ptrs = lambda gs: None if gs is None else [g.ptr for g in gs]
+        infos = self.adjoint_ptrs(ptrs(Ub), ptrs(Ud), ptrs(lam), ptrs(gA), ptrs(gU))
+        if host:
+            back = lambda gs: None if gs is None else np.stack([g.to_host() for g in gs])
+            return back(lam), back(gA), back(gU), infos
+        return lam, gA, gU, infos
+
     def close(self):
         if getattr(self, "_s", None) and _initialised:
             _lib.mg_batch_solver_destroy(self._s)
@@ -1532,6 +1718,71 @@ def solve_batched_krylov(F, m, U=None, L=1.0, coef=None, **opts):
         return s.solve(F, U)
     finally:
         s.close()
+
+
+def _need_adjoint(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the adjoint sensitivities are not in this library)")
+    return getattr(_lib, name)
+
+
+def _solve_info(res):
+    """a SolveResult as the info dict of Solver.solve_ptr"""
+    return dict(status=res.status, cycles=res.cycles, converged=bool(res.converged), coarse_capped=bool(res.coarse_capped),
+                res0=res.res0, res=res.res, ref_norm=res.ref_norm, device_ms=res.device_ms,
+                history=[res.history[i] for i in range(res.n_history)])
+
+
+def coefficientGradient(N, L, lam, U, gA=None):
+    """mg_coefficientGradient on DeviceGrids (include/mg_adjoint.h): gA = dJ/da at every grid point, rim included, from the
+    adjoint field lam and the forward solution U,  gA_k = 0.5*inv*((((0 + tN) + tS) + tE) + tW),
+    tX = (lam'_k - lam'_q)*(U_k - U_q) over the neighbours q inside the grid, lam' = lam with its rim taken as +0 (the rim
+    of lam is never used).  gA = None: a new DeviceGrid.  lam and U are read only; returns gA."""
+    fn = _need_adjoint("mg_coefficientGradient")
+    if gA is None:
+        gA = DeviceGrid((N, N))
+    fn(int(N), float(L), lam.ptr, U.ptr, gA.ptr)
+    _check()
+    return gA
+
+
+def boundaryGradient(N, L, a, lam, Ubar=None, gU=None):
+    """mg_boundaryGradient on DeviceGrids (include/mg_adjoint.h): gU = dJ/d(rim data) as an N x N array -- 0 inside, Ubar at
+    the corners, Ubar[b] - inv*(0.5*(a[b] + a[p])*lam[p]) at a rim point b with interior neighbour p.  a = None: a = 1;
+    Ubar = None: 0.  gU = None: a new DeviceGrid.  a, lam and Ubar are read only; returns gU."""
+    fn = _need_adjoint("mg_boundaryGradient")
+    if gU is None:
+        gU = DeviceGrid((N, N))
+    fn(int(N), float(L), a.ptr if a is not None else None, lam.ptr, Ubar.ptr if Ubar is not None else None, gU.ptr)
+    _check()
+    return gU
+
+
+def _optional_pointer_array(views, n):
+    if views is None:
+        return None
+    return (C.c_void_p * max(n, 1))(*[v.ptr if v is not None else None for v in views])
+
+
+def coefficientGradient_batch(N, L, lam, U, gA):
+    """mg_coefficientGradient_batch on sequences of DeviceGrids: coefficientGradient for every instance in ONE launch, each
+    bit-identical to the single call.  Returns gA."""
+    n = len(gA)
+    _need_adjoint("mg_coefficientGradient_batch")(n, int(N), float(L), _optional_pointer_array(lam, n), _optional_pointer_array(U, n),
+                                                  _optional_pointer_array(gA, n))
+    _check()
+    return gA
+
+
+def boundaryGradient_batch(N, L, a, lam, Ubar, gU):
+    """mg_boundaryGradient_batch on sequences of DeviceGrids: boundaryGradient for every instance in ONE launch, each
+    bit-identical to the single call.  a and Ubar may be None, and so may entries of them (a = 1, Ubar = 0 for that
+    instance).  Returns gU."""
+    n = len(gU)
+    _need_adjoint("mg_boundaryGradient_batch")(n, int(N), float(L), _optional_pointer_array(a, n), _optional_pointer_array(lam, n),
+                                               _optional_pointer_array(Ubar, n), _optional_pointer_array(gU, n))
+    _check()
+    return gU
 
 
 def _need_krylov_batch(name):

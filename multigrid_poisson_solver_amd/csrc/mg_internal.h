@@ -549,6 +549,17 @@ void krylov_update_batch(hipStream_t s, int n, int N, int m, const KrylovBatchIt
 void krylov_log_restart_batch(hipStream_t s, int n, int m, const KrylovBatchItem *items, const double *norms);
 // A*z for n instances: in = z, coarse = a (nullptr for that instance: a = 1), out (mg_varcoef_batch_kernels.hip: apply_vc's body)
 void apply_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items);
+// adjoint sensitivities (mg_adjoint_kernels.hip, driven by mg_adjoint.cpp; the expressions and their order:
+// include/mg_adjoint.h).  gA = the gradient in the nodal coefficient at every grid point, h = 0.5*inv; the rim of lam is
+// substituted by +0.0, never used from memory
+void coef_grad(hipStream_t s, int N, double h, const double *lam, const double *U, double *gA);
+// gU = the gradient in the rim data: +0 on the interior, Ubar at the corners, Ubar - inv*(f*lam[p]) on the rest of the rim
+// (A == nullptr: a = 1; Ubar == nullptr: 0.0)
+void rim_grad(hipStream_t s, int N, double inv, const double *A, const double *lam, const double *Ubar, double *gU);
+// the same on n instances in one launch each: in = lam, F = U, out = gA / in = lam, F = Ubar, coarse = a (both may be null
+// per instance), out = gU
+void coef_grad_batch(hipStream_t s, int n, int N, double h, const NodeBatchItem *items);
+void rim_grad_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
@@ -579,6 +590,12 @@ int solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<dou
 // the level-0 coefficient of a solver, mg_solver::coef[0] (mg_solve.cpp), nullptr when none is set: the heat stepper's
 // right-hand-side kernel reads the solver's own array instead of keeping a second copy (mg_heat.cpp)
 const double *solver_coefficient(const mg_solver *s);
+// what a driver over the solvers needs of their shape (mg_adjoint.cpp): N, and L / max_batch where asked for
+int solver_size(const mg_solver *s, double *L);
+int batch_solver_size(const mg_batch_solver *s, double *L, int *max_batch);
+// the level-0 coefficient instance i of a batched solve uses (mg_solve_batch.cpp): its own copy, the shared one, or nullptr
+// when none is set
+const double *batch_solver_coefficient(const mg_batch_solver *s, int i);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

@@ -266,6 +266,11 @@ int mg::solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector
 }
 
 const double *mg::solver_coefficient(const mg_solver *s) { return s && s->coef_set ? s->coef[0] : nullptr; }
+int mg::solver_size(const mg_solver *s, double *L)
+{
+    if (L) *L = s->L;
+    return s->N;
+}
 
 namespace {
 

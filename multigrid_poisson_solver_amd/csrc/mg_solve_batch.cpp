@@ -544,6 +544,20 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
 
 }  // namespace
 
+int mg::batch_solver_size(const mg_batch_solver *s, double *L, int *max_batch)
+{
+    if (L) *L = s->L;
+    if (max_batch) *max_batch = s->max_batch;
+    return s->N;
+}
+
+const double *mg::batch_solver_coefficient(const mg_batch_solver *s, int i)
+{
+    if (!s || s->n_coef == 0 || i < 0) return nullptr;
+    if (s->n_coef == 1) return s->coef[0];
+    return i < s->n_coef ? s->coef[0] + (size_t)i * s->pitch[0] : nullptr;
+}
+
 extern "C" {
 
 mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg_solve_opts *opts)
