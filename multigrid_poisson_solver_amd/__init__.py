@@ -61,6 +61,16 @@ class BatchSolveStats(C.Structure):
     _fields_ = [("cycles", C.c_int), ("launches", C.c_int), ("device_ms", C.c_double)]
 
 
+class EigsOpts(C.Structure):
+    _fields_ = [("cycle", SolveOpts), ("k", C.c_int), ("guard", C.c_int), ("max_iters", C.c_int), ("rtol", C.c_double),
+                ("atol", C.c_double)]
+
+
+class EigsResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("iters", C.c_int), ("converged", C.c_int), ("breakdown", C.c_int), ("restarts", C.c_int),
+                ("cycles", C.c_int), ("coarse_capped", C.c_int)]
+
+
 class HeatOpts(C.Structure):
     _fields_ = [("nu", C.c_double), ("dt", C.c_double), ("theta", C.c_double), ("solve", SolveOpts)]
 
@@ -211,6 +221,21 @@ ABI_ADJOINT = {
     "mg_batch_solver_adjoint": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BatchSolveStats)]),
 }
 
+# the symbols include/mg_eigs.h declares (the lowest eigenmodes of -div(a grad u): multigrid-preconditioned LOBPCG); bound
+# like ABI_FMG: a library without them still loads, EigenSolver / eigs() / eigsGram() / ... then raise
+ABI_EIGS = {
+    "mg_eigs_opts_default": (None, [C.POINTER(EigsOpts)]),
+    "mg_eigs_create": (_vp, [_i, _d, C.POINTER(EigsOpts)]),
+    "mg_eigs_set_coefficient": (_i, [_vp, _vp]),
+    "mg_eigs_solve": (_i, [_vp, _vp, _i, _u64, _vp, _vp, C.POINTER(EigsResult)]),
+    "mg_eigs_history": (_i, [_vp, _vp, _i]),
+    "mg_eigs_destroy": (None, [_vp]),
+    "mg_eigsGram": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "mg_eigsRotate": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mg_eigsRayleighRitz": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+MG_EIGS_MAX_BLOCK, MG_EIGS_DROP = 12, 1e-12
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -269,7 +294,8 @@ def load_library(path=None):
     if missing:
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
-            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()):
+            list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
+            list(ABI_EIGS.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -1795,6 +1821,206 @@ def _need_vc_batch(name):
     if not hasattr(lib(), name):
         raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched variable-coefficient solver is not in this library)")
     return getattr(_lib, name)
+
+
+def _need_eigs(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the eigen-solver is not in this library)")
+    return getattr(_lib, name)
+
+
+def eigs_default_guard(k):
+    """the guard columns EigenSolver(guard=None) takes: min(max(2, k // 2), MG_EIGS_MAX_BLOCK - k)"""
+    return min(max(2, int(k) // 2), MG_EIGS_MAX_BLOCK - int(k))
+
+
+def eigsGram(N, S, AS):
+    """Test hook (include/mg_eigs.h).  mg_eigsGram on lists of m DeviceGrids: (G, H), G[j, l] = <S[j], S[l]>,
+    H[j, l] = <S[j], AS[l]> for j <= l over the interior, both mirrored; one pass, nothing on the device is written."""
+    m = len(S)
+    assert len(AS) == m
+    G, H = np.zeros((m, m)), np.zeros((m, m))
+    status = _need_eigs("mg_eigsGram")(int(N), m, _pointer_array(S), _pointer_array(AS), G.ctypes.data, H.ctypes.data)
+    if status:
+        _check()
+        raise MGError(f"mg_eigsGram failed with status {status}")
+    return G, H
+
+
+def eigsRotate(N, C_, Cp, theta, S, AS, R):
+    """Test hook (include/mg_eigs.h).  mg_eigsRotate on DeviceGrids, in place: C_, Cp of shape (m, p), theta of p values; S, AS:
+    lists of 3p DeviceGrids of which the first m are read; written on the interior: S[i] = X'_i, AS[i] = AX'_i,
+    S[2p + i] = P'_i, AS[2p + i] = AP'_i, R[i] = AX'_i - theta_i*X'_i.  Returns [<R_i, R_i>]."""
+    C_ = np.ascontiguousarray(C_, dtype=np.float64)
+    Cp = np.ascontiguousarray(Cp, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    m, p = C_.shape
+    assert Cp.shape == (m, p) and theta.shape == (p,) and len(S) == len(AS) == 3 * p and len(R) == p
+    res2 = np.zeros(p)
+    status = _need_eigs("mg_eigsRotate")(int(N), m, p, C_.ctypes.data, Cp.ctypes.data, theta.ctypes.data, _pointer_array(S),
+                                         _pointer_array(AS), _pointer_array(R), res2.ctypes.data)
+    if status:
+        _check()
+        raise MGError(f"mg_eigsRotate failed with status {status}")
+    return res2
+
+
+def eigsRayleighRitz(G, H, p):
+    """Test hook (include/mg_eigs.h).  The host Rayleigh-Ritz step on G, H (m x m): (kept, C, Cp, theta); kept < p is the
+    breakdown, C, Cp, theta are then None.  Needs no device."""
+    load_library()
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    m = G.shape[0]
+    C_, Cp, theta = np.zeros((m, p)), np.zeros((m, p)), np.zeros(p)
+    if not hasattr(_lib, "mg_eigsRayleighRitz"):
+        raise MGError(f"{LIB_PATH} does not export mg_eigsRayleighRitz: rebuild it (the eigen-solver is not in this library)")
+    kept = _lib.mg_eigsRayleighRitz(m, int(p), G.ctypes.data, H.ctypes.data, C_.ctypes.data, Cp.ctypes.data, theta.ctypes.data)
+    if kept < p:
+        return kept, None, None, None
+    return kept, C_, Cp, theta
+
+
+class EigenSolver:
+    """The k lowest eigenmodes of -div(a grad u) on the N x N vertex grid with a zero rim (include/mg_eigs.h): LOBPCG on the
+    basis [X, W, P] with one V(pre, post) cycle as the preconditioner, k + guard columns in every launch.
+        e = EigenSolver(N, L, k=4, coef=a); lam, X, info = e.solve(); e.close()
+    lam ascending, X of shape (k, N, N) with orthonormal interiors and a zero rim.  guard=None takes
+    min(max(2, k // 2), 12 - k) guard columns: a block that cuts a cluster of eigenvalues without them may not converge.
+    cycle_opts are solve_opts' pre, post, omega, N_min and coarse targets; shift and fmg are refused (the eigenvalues of the
+    shifted operator are lam + shift with the same vectors).  Everything is allocated here -- about 8(k + guard) fields; a
+    solve allocates nothing on the device beyond the result it returns."""
+
+    def __init__(self, N, L=1.0, k=1, guard=None, coef=None, rtol=1e-8, atol=0.0, max_iters=60, **cycle_opts):
+        self.N, self.L, self.k = int(N), float(L), int(k)
+        self.guard = eigs_default_guard(k) if guard is None else int(guard)
+        o = EigsOpts()
+        _need_eigs("mg_eigs_opts_default")(C.byref(o))
+        o.cycle = solve_opts(**cycle_opts)
+        o.k, o.guard, o.max_iters, o.rtol, o.atol = self.k, self.guard, int(max_iters), float(rtol), float(atol)
+        self.opts = o
+        self._e = _need_eigs("mg_eigs_create")(self.N, self.L, C.byref(o))
+        if not self._e:
+            _check()
+            raise MGError("mg_eigs_create returned NULL")
+        if coef is not None:
+            try:
+                self.set_coefficient(coef)
+            except Exception:
+                self.close()
+                raise
+
+    def set_coefficient(self, a):
+        """a: (N, N) nodal coefficient shared by all columns (numpy array, DeviceGrid or float64 torch CUDA tensor, finite and
+        > 0, copied); None: back to a = 1.  A refusal (MGError "[2] ...") leaves the earlier coefficient."""
+        _set_coefficient(_need_eigs("mg_eigs_set_coefficient"), self._e, self.N, a)
+
+    def solve_ptrs(self, X_ptrs, use_start=False, seed=0):
+        """X_ptrs: k device addresses of N x N fp64 arrays (16-byte aligned), on the engine stream.  Returns (lam, info)."""
+        if len(X_ptrs) != self.k:
+            raise MGError(f"{len(X_ptrs)} vectors for k = {self.k}")
+        lam, res = np.zeros(self.k), np.zeros(self.k)
+        r = EigsResult()
+        status = _lib.mg_eigs_solve(self._e, (C.c_void_p * self.k)(*X_ptrs), int(bool(use_start)), int(seed), lam.ctypes.data,
+                                    res.ctypes.data, C.byref(r))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_eigs_solve failed with status {status}")
+        return lam, dict(status=r.status, iters=r.iters, converged=bool(r.converged), breakdown=bool(r.breakdown),
+                         restarts=r.restarts, cycles=r.cycles, coarse_capped=bool(r.coarse_capped), res=res)
+
+    def solve(self, X0=None, seed=0):
+        """X0 = None: a random start from `seed`.  X0 of shape (k, N, N) -- a numpy array, a list of k (N, N) arrays or
+        DeviceGrids, or a contiguous float64 torch CUDA tensor (worked on in place, on torch.cuda.current_stream()) --: its
+        interiors start the k columns (the guard columns are random).  Returns (lam, X, info): X a numpy array (k, N, N),
+        the list of DeviceGrids, or the tensor."""
+        N, k = self.N, self.k
+        first = X0[0] if isinstance(X0, (list, tuple)) else X0
+        if X0 is not None and _is_torch(first):
+            import torch
+            Xs, _ = _instances(X0, "X0")
+            for t in Xs:
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N) and t.is_contiguous()):
+                    raise MGError(f"X0: expected contiguous float64 CUDA tensors of shape ({N}, {N})")
+            if len(Xs) != k:
+                raise MGError(f"X0: {len(Xs)} vectors for k = {k}")
+            dev = Xs[0].device
+            ptrs, buf = _staged(Xs, False, N * N, dev)
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            try:
+                lam, info = self.solve_ptrs(ptrs, True, seed)
+            finally:
+                _lib.mg_set_stream(prev)
+            if buf is not None:
+                for i in range(k):
+                    Xs[i].copy_(buf[i, :N * N].view(N, N))
+            return lam, X0, info
+        if X0 is None:
+            Xd = [DeviceGrid.zeros((N, N)) for _ in range(k)]
+            owned, host = list(Xd), True
+        else:
+            Xs = list(X0) if isinstance(X0, (list, tuple)) else [x for x in np.asarray(X0, dtype=np.float64)]
+            if len(Xs) != k:
+                raise MGError(f"X0: {len(Xs)} vectors for k = {k}")
+            host = not all(isinstance(x, DeviceGrid) for x in Xs)
+            Xd, owned = [], []
+            for x in Xs:
+                if isinstance(x, DeviceGrid):
+                    if x.shape != (N, N):
+                        raise MGError(f"X0: DeviceGrid of shape {x.shape}, expected ({N}, {N})")
+                    Xd.append(x)
+                else:
+                    x = np.asarray(x, dtype=np.float64)
+                    if x.shape != (N, N):
+                        raise MGError(f"X0: array of shape {x.shape}, expected ({N}, {N})")
+                    Xd.append(DeviceGrid.from_host(x))
+                    owned.append(Xd[-1])
+        try:
+            lam, info = self.solve_ptrs([x.ptr for x in Xd], X0 is not None, seed)
+            X = np.stack([x.to_host() for x in Xd]) if host else Xd
+        finally:
+            for x in owned:
+                x.free()
+        return lam, X, info
+
+    def history(self):
+        """the records of the last solve, one dict per Rayleigh-Ritz step: theta (k), res (k, the rotation's), kept (basis
+        directions kept), restarted"""
+        fn = _need_eigs("mg_eigs_history")
+        n = fn(self._e, None, 0)
+        if n <= 0:
+            return []
+        k = self.k
+        buf = np.zeros((n, 2 * k + 2))
+        got = fn(self._e, buf.ctypes.data, n)
+        return [dict(theta=rec[:k].copy(), res=rec[k:2 * k].copy(), kept=int(rec[2 * k]), restarted=bool(rec[2 * k + 1]))
+                for rec in buf[:got]]
+
+    def close(self):
+        if getattr(self, "_e", None):
+            _lib.mg_eigs_destroy(self._e)
+            self._e = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def eigs(N, k, L=1.0, coef=None, **opts):
+    """The k lowest eigenmodes of -div(coef grad u) (coef = None: the Laplacian) on the N x N grid of side L with a zero rim:
+    (lam, X, info) of one EigenSolver.solve() from a random start; opts are EigenSolver's."""
+    seed = opts.pop("seed", 0)
+    with EigenSolver(N, L, k=k, coef=coef, **opts) as e:
+        return e.solve(seed=seed)
 
 
 def _need_heat(name):

@@ -560,6 +560,32 @@ void rim_grad(hipStream_t s, int N, double inv, const double *A, const double *l
 // per instance), out = gU
 void coef_grad_batch(hipStream_t s, int n, int N, double h, const NodeBatchItem *items);
 void rim_grad_batch(hipStream_t s, int n, int N, double inv, const NodeBatchItem *items);
+// lowest eigenmodes, LOBPCG (mg_eigs_kernels.hip, driven by mg_eigs.cpp; the method and the order of every operation:
+// include/mg_eigs.h).  All sums run over the interior; no rim is read into a result or written.
+constexpr int EIGS_MAX_M = 3 * MG_EIGS_MAX_BLOCK;   // the largest basis [X, W, P]
+constexpr int EIGS_TILE = 6;                        // the Gram kernel's tile of (j, l) pairs is EIGS_TILE x EIGS_TILE
+// tiles (a, b), a <= b, of an m x m matrix, and the sums one tile leaves: its block of G, then its block of H
+inline int eigs_tiles(int m) { const int nt = (m + EIGS_TILE - 1) / EIGS_TILE; return nt * (nt + 1) / 2; }
+constexpr int EIGS_TILE_SUMS = 2 * EIGS_TILE * EIGS_TILE;
+// blocks of a Gram / a rotation launch over an N x N grid: every sum needs this many partials
+size_t eigs_gram_blocks(int N);
+size_t eigs_rotate_blocks(int N);
+// out[(z*EIGS_TILE_SUMS) + e]: tile z (row-major over a <= b), e = jj*T + ll the entry <S_j, S_l> of G, T*T + jj*T + ll the
+// entry <S_j, AS_l> of H (j = a*T + jj, l = b*T + ll; entries with j or l >= m: +0).  ptrs: 2m device pointers, S then AS,
+// in device memory; part: eigs_tiles(m)*EIGS_TILE_SUMS*eigs_gram_blocks(N) doubles.  Two launches.
+void eigs_gram(hipStream_t s, int N, int m, const double *const *ptrs, double *part, double *out);
+// the rotation of include/mg_eigs.h.  ptrs (device memory): EIGS_MAX_M pointers S, EIGS_MAX_M pointers AS (the first m of each
+// are read; X' -> S[i], AX' -> AS[i], P' -> S[2p + i], AP' -> AS[2p + i]), then MG_EIGS_MAX_BLOCK pointers R.  coef (device
+// memory): C column by column (column i at i*EIGS_MAX_M), Cp likewise from MG_EIGS_MAX_BLOCK*EIGS_MAX_M on, then theta.
+// res2[i] = <R_i, R_i>; part: p*eigs_rotate_blocks(N) doubles.  Two launches.
+constexpr int EIGS_COEF_CP = MG_EIGS_MAX_BLOCK * EIGS_MAX_M, EIGS_COEF_THETA = 2 * EIGS_COEF_CP,
+              EIGS_COEF_COUNT = EIGS_COEF_THETA + MG_EIGS_MAX_BLOCK;
+constexpr int EIGS_PTR_AS = EIGS_MAX_M, EIGS_PTR_R = 2 * EIGS_MAX_M, EIGS_PTR_COUNT = 2 * EIGS_MAX_M + MG_EIGS_MAX_BLOCK;
+void eigs_rotate(hipStream_t s, int N, int m, int p, double *const *ptrs, const double *coef, double *part, double *res2);
+// R_i = AX_i - theta_i*X_i and res2[i] = <R_i, R_i>, i < p: the same tables (S[i], AS[i], R[i], theta).  Two launches.
+void eigs_resnorm(hipStream_t s, int N, int p, double *const *ptrs, const double *coef, double *part, double *res2);
+// the start of a column: dst = src on the interior (src == nullptr: dst - 0.5, dst holding mg_fill_uniform's values), +0 on the rim
+void eigs_start(hipStream_t s, int N, double *dst, const double *src);
 }  // namespace k
 
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
@@ -596,6 +622,15 @@ int batch_solver_size(const mg_batch_solver *s, double *L, int *max_batch);
 // the level-0 coefficient instance i of a batched solve uses (mg_solve_batch.cpp): its own copy, the shared one, or nullptr
 // when none is set
 const double *batch_solver_coefficient(const mg_batch_solver *s, int i);
+// one cycle of a batch solver's own, U0[i] = vcycle(F0[i], U0[i]) for i < n <= max_batch, as an iteration of
+// mg_batch_solver_solve enqueues it (the constant, the variable-coefficient or, under MG_SMOOTHER=simple, the operator-by-
+// operator cycle) -- for a driver that uses the cycle as a preconditioner (mg_eigs.cpp).  Rebuilds and uploads the solver's
+// tables; returns the launches it enqueued, or -1 on a HIP error.
+int batch_solver_cycle(mg_batch_solver *s, hipStream_t st, int n, const double *const *F0, double *const *U0);
+// the coarse solves' state of that cycle: enqueue its copy into the solver's pinned block behind the cycle (no synchronisation);
+// once the stream has been synchronised, whether a coarse solve of the instances 0 .. n-1 stopped at coarse_max_iters
+bool batch_solver_enqueue_state(mg_batch_solver *s, hipStream_t st);
+bool batch_solver_coarse_capped(const mg_batch_solver *s, int n);
 
 // The pre-smoothed U of a level is dead weight between its `-1` and its `1` node: 8 B per point written, 8 B read.  When
 // recompute_available(), the `-1` node (zero start) may run with smooth_restrict_no_out() and the `1` node with

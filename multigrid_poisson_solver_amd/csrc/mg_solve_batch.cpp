@@ -558,6 +558,31 @@ const double *mg::batch_solver_coefficient(const mg_batch_solver *s, int i)
     return i < s->n_coef ? s->coef[0] + (size_t)i * s->pitch[0] : nullptr;
 }
 
+int mg::batch_solver_cycle(mg_batch_solver *s, hipStream_t st, int n, const double *const *F0, double *const *U0)
+{
+    const bool vc = s->n_coef > 0;
+    std::vector<int> act(n);
+    for (int i = 0; i < n; ++i) {
+        act[i] = i;
+        (vc ? fill_tables_vc : fill_tables)(s, i, F0[i], U0[i], i);
+    }
+    if (!upload_tables(s, st)) return -1;
+    if (vc) return vcycle_vc_batch(s, st, n);
+    return ctx().smoother == SMOOTHER_SIMPLE ? vcycle_simple_each(s, st, act, F0, U0) : vcycle_batch(s, st, n);
+}
+
+bool mg::batch_solver_enqueue_state(mg_batch_solver *s, hipStream_t st)
+{
+    return MG_HIP(hipMemcpyAsync(s->host_rb, s->dev_rb, rb_bytes(s->max_batch), hipMemcpyDeviceToHost, st));
+}
+
+bool mg::batch_solver_coarse_capped(const mg_batch_solver *s, int n)
+{
+    for (int j = 0; j < n; ++j)
+        if (rb_state(s->host_rb, s->max_batch)[4 * j + 2]) return true;
+    return false;
+}
+
 extern "C" {
 
 mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg_solve_opts *opts)
