@@ -4,8 +4,9 @@ header's order.  The small dense eigenproblems of the Rayleigh-Ritz step go thro
 its own Jacobi routine: both are backward stable, the step is specified through its result (tests/test_eigs_cpu.py holds the
 engine's against this one), and iteration counts of the two may differ by one or two.
 The second half holds the references that share no code with the engine: the dense (N-2)^2 matrix assembled in longdouble
-from a, L and N alone (as _solve_vc_ref.direct_solution assembles it) with numpy.linalg.eigvalsh, and the closed form for
-a == 1.  TEST INFRASTRUCTURE."""
+from a, L and N alone (as _solve_vc_ref.direct_solution assembles it) with numpy.linalg.eigvalsh, the closed form for
+a == 1, and -- for the sizes no dense matrix reaches -- the exact spectrum of a coefficient that is constant along one axis,
+by separation of variables (written from include/mg_varcoef.h's face means and the mathematics alone).  TEST INFRASTRUCTURE."""
 import functools
 import math
 
@@ -242,6 +243,71 @@ def closed_form(N, L=1.0, count=None):
     s = np.array([math.sin(i * math.pi / (2.0 * (N - 1))) ** 2 for i in range(1, N - 1)])
     lam = np.sort((4.0 / (dx * dx)) * (s[:, None] + s[None, :]), axis=None)
     return lam if count is None else lam[:count]
+
+
+# ---------------------------------------------------------------- layered coefficients: an exact reference at any N
+# a[r, c] = p[c] ("cols") or p[r] ("rows"): constant along one axis.  The header's arithmetic face means across the constant
+# axis are 0.5*(p + p) = p itself, so -div_h(a grad_h .) = inv*(T_p (x) I + diag(p) (x) T) with T = tridiag(-1, 2, -1) along
+# the constant axis and T_p the three-point operator of p along the other one (diagonal aE + aW, off-diagonal -aE,
+# aE = 0.5*(p[c] + p[c+1]), aW = 0.5*(p[c] + p[c-1])).  The sine modes of T, mu_j = 4 sin^2(j*pi/(2(N-1))), block-diagonalise
+# it: the spectrum is the union over j = 1 .. N-2 of the eigenvalues of the (N-2) x (N-2) symmetric tridiagonal
+# inv*(T_p + mu_j*diag(p)).  The transpose of a has the same spectrum: one reference serves both orientations.
+PROFILES = ("one", "smooth", "jump")
+
+
+def profile(name, N):
+    """p at the N points of one axis.  smooth: 2 + sin(2*pi*t + 0.5), contrast 3, not symmetric about the middle; jump: 1
+    below the index j0, 10 from it on, j0 odd (the odd index next to 0.37*(N-1)): a column pair (j0 - 1, j0) straddles it."""
+    t = np.arange(N) / float(N - 1)
+    if name == "one":
+        return np.ones(N)
+    if name == "smooth":
+        return 2.0 + np.sin(2.0 * np.pi * t + 0.5)
+    if name == "jump":
+        j0 = 2 * (int(0.37 * (N - 1)) // 2) + 1
+        return np.where(np.arange(N) < j0, 1.0, 10.0)
+    raise ValueError(name)
+
+
+def layered(name, N, axis):
+    """the N x N coefficient of profile(name, N): axis "cols": a[r, c] = p[c]; "rows": a[r, c] = p[r]"""
+    p = profile(name, N)
+    a = np.empty((N, N))
+    a[:, :] = p[None, :] if axis == "cols" else p[:, None]
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def _separated_cached(name, N, L, count):
+    p = np.asarray(profile(name, N), dtype=LD)
+    h = LD(L) / LD(N - 1)
+    inv = LD(1) / (h * h)
+    half = LD(1) / LD(2)
+    aE, aW = half * (p[1:-1] + p[2:]), half * (p[1:-1] + p[:-2])
+    n = N - 2
+    Tp = np.zeros((n, n), dtype=LD)
+    i = np.arange(n)
+    Tp[i, i] = aE + aW
+    Tp[i[:-1], i[:-1] + 1] = Tp[i[:-1] + 1, i[:-1]] = -aE[:-1]
+    D = np.zeros((n, n), dtype=LD)
+    D[i, i] = p[1:-1]
+    pmin = float(np.min(p))
+    found = np.zeros(0)
+    for j in range(1, N - 1):
+        s = np.sin(LD(j) * LD(np.pi) / LD(2 * (N - 1)))
+        mu = LD(4) * s * s
+        # every eigenvalue of block j is at least inv*mu_j*min(p), T_p being positive semidefinite, and mu_j grows with j
+        if found.size >= count and float(inv * mu) * pmin > found[count - 1]:
+            break
+        w = np.linalg.eigvalsh((inv * (Tp + mu * D)).astype(np.float64))
+        found = np.sort(np.concatenate([found, w[:count]]))[:count]
+    return found
+
+
+def separated_eigenvalues(name, N, L=1.0, count=13):
+    """the `count` lowest eigenvalues, ascending, of -div_h(a grad_h .) for a = layered(name, N, either axis): blocks assembled
+    in longdouble, rounded to fp64, numpy.linalg.eigvalsh on each (dimension N-2: within about (N-2)*u*||block|| of exact)"""
+    return _separated_cached(name, N, float(L), int(count)).copy()
 
 
 def residuals_ld(a, N, L, lam, X):
