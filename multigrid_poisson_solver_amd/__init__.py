@@ -236,6 +236,23 @@ ABI_EIGS = {
 }
 MG_EIGS_MAX_BLOCK, MG_EIGS_DROP = 12, 1e-12
 
+# the symbols include/mg_bc.h declares (Neumann and mixed boundary kinds per side in Solver and HeatStepper); bound like
+# ABI_FMG: a library without them still loads, Solver.set_boundary() / neumann_source() / ... then raise
+ABI_BC = {
+    "mg_solver_set_boundary": (_i, [_vp, _vp]),
+    "mg_solver_boundary": (_i, [_vp, _vp]),
+    "mg_neumannSource": (None, [_i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "mg_applyOperatorBoundary": (None, [_i, _d, _d, _vp, _vp, _vp, _vp]),
+    "mg_boundary_prolongation_table": (None, [_i, _i, _vp, _vp]),
+    "mg_sweepBoundary": (None, [_i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "mg_residualBoundary": (None, [_i, _d, _d, _vp, _vp, _vp, _vp, _vp, _i]),
+    "mg_restrictBoundary": (None, [_i, _vp, _vp, _i, _vp]),
+    "mg_prolongAddBoundary": (None, [_i, _vp, _vp, _i, _vp, _vp]),
+    "mg_heat_rhs_boundary": (None, [_i, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "mg_heat_stepper_set_boundary": (_i, [_vp, _vp]),
+}
+DIRICHLET, NEUMANN = 0, 1
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -295,7 +312,7 @@ def load_library(path=None):
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
-            list(ABI_EIGS.items()):
+            list(ABI_EIGS.items()) + list(ABI_BC.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -661,6 +678,132 @@ def sweepCoefficient(N, L, shift, omega, a, U_in, F, U_out):
 def residualCoefficient(N, L, shift, a, U, F, D, sign=1):
     """Test hook (include/mg_varcoef.h).  mg_residualCoefficient on DeviceGrids: D = sign*(inv*b(U) - F) inside, sign*0 on the rim."""
     _need_vc("mg_residualCoefficient")(N, L, shift, a.ptr, U.ptr, F.ptr, D.ptr, sign)
+    _check()
+
+
+def _need_bc(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the boundary kinds)")
+    return getattr(_lib, name)
+
+
+def _kinds(bc):
+    """bc as a C int[4] in the order S, N, W, E (row 0, row N-1, column 0, column N-1): a 4-sequence of DIRICHLET (0) /
+    NEUMANN (1), or a 4-character string of 'd' / 'n'; None: four Dirichlet sides.  The values are checked by the library."""
+    if bc is None:
+        bc = (0, 0, 0, 0)
+    if isinstance(bc, str):
+        if len(bc) != 4 or any(ch not in "dnDN" for ch in bc):
+            raise MGError(f"bc = {bc!r}: expected 4 characters of 'd' / 'n' in the order S, N, W, E")
+        bc = [1 if ch in "nN" else 0 for ch in bc]
+    bc = list(bc)
+    if len(bc) != 4:
+        raise MGError(f"bc: expected 4 kinds in the order S, N, W, E, got {len(bc)}")
+    return (C.c_int * 4)(*[int(v) for v in bc])
+
+
+def _opt(a):
+    return a.ptr if a is not None else None
+
+
+def boundary_prolongation_table(M, N):
+    """mg_boundary_prolongation_table: (lo[N], w[N]) of the 1-D prolongation from M coarse to N fine points of the boundary
+    path (include/mg_bc.h); host only."""
+    lo = np.empty(N, dtype=np.int32)
+    w = np.empty(N, dtype=np.float64)
+    if not hasattr(load_library(), "mg_boundary_prolongation_table"):
+        raise MGError(f"{LIB_PATH} does not export mg_boundary_prolongation_table (a build without the boundary kinds)")
+    load_library().mg_boundary_prolongation_table(int(M), int(N), lo.ctypes.data, w.ctypes.data)
+    return lo, w
+
+
+def neumann_source(N, L, bc, F, g, coef=None, out=None):
+    """mg_neumannSource: out = F with the flux data dU/dn = g (outward normal) folded in, F - (2/h)*a*g at the rim unknowns of
+    Neumann sides (a the NODAL coefficient; both terms at a corner of two Neumann sides), a copy elsewhere.
+    bc: S, N, W, E (row 0, row N-1, column 0, column N-1).  g: shape (4, N) with the rows S, N, W, E; entries on Dirichlet
+    sides are not read.  F, g, coef: numpy arrays (the result is a new numpy array), DeviceGrids (anything with .ptr and
+    .shape; out = None: a new DeviceGrid) or float64 torch CUDA tensors (on torch.cuda.current_stream(); out = None: a new
+    tensor), with the rules of Solver.set_coefficient.  coef = None: a = 1.  Returns out; the solver takes it as F."""
+    fn = _need_bc("mg_neumannSource")
+    N, kinds, keep = int(N), _kinds(bc), []
+    if _is_torch(F) or _is_torch(g):
+        import torch
+        for name, t, shape in (("F", F, (N, N)), ("g", g, (4, N))) + ((("out", out, (N, N)),) if out is not None else ()):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous()
+                    and t.data_ptr() % 16 == 0):
+                raise MGError(f"{name}: expected a contiguous, 16-byte aligned float64 CUDA tensor of shape {shape}")
+        if out is None:
+            out = torch.empty_like(F)
+        prev = _lib.mg_get_stream()
+        _lib.mg_set_stream(torch.cuda.current_stream(F.device).cuda_stream)
+        try:
+            fn(N, float(L), kinds, _coefficient_address(N, coef, keep) if coef is not None else None, F.data_ptr(), g.data_ptr(),
+               out.data_ptr())
+        finally:
+            _lib.mg_set_stream(prev)
+            for k in keep:
+                k.free()
+        _check()
+        return out
+
+    def dev(a, shape, what):
+        if hasattr(a, "ptr") and hasattr(a, "shape"):
+            if tuple(a.shape) != shape:
+                raise MGError(f"{what}: device array of shape {a.shape}, expected {shape}")
+            return a
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise MGError(f"{what}: array of shape {a.shape}, expected {shape}")
+        keep.append(DeviceGrid.from_host(a))
+        return keep[-1]
+
+    host = not (hasattr(F, "ptr") and hasattr(F, "shape"))
+    try:
+        Fd, gd = dev(F, (N, N), "F"), dev(g, (4, N), "g")
+        a_ptr = _coefficient_address(N, coef, keep) if coef is not None else None
+        if out is None:
+            out = DeviceGrid((N, N))
+            if host:
+                keep.append(out)
+        fn(N, float(L), kinds, a_ptr, Fd.ptr, gd.ptr, out.ptr)
+        _check()
+        return out.to_host() if host and out in keep else out
+    finally:
+        for k in keep:
+            k.free()
+
+
+def applyOperatorBoundary(N, L, shift, bc, a, U, out):
+    """mg_applyOperatorBoundary on DeviceGrids: out = inv*b(U) of div(a grad U) - shift*U at the unknowns with mirrored
+    neighbours beyond Neumann sides, +0 at data points (include/mg_bc.h); bc: S, N, W, E; a = None is a = 1."""
+    _need_bc("mg_applyOperatorBoundary")(int(N), float(L), float(shift), _kinds(bc), _opt(a), U.ptr, out.ptr)
+    _check()
+
+
+def sweepBoundary(N, L, shift, omega, bc, a, U_in, F, U_out):
+    """Test hook (include/mg_bc.h).  One weighted Jacobi sweep at the unknowns (U_in = None: from zero); bc: S, N, W, E; on
+    Neumann sides the rim of U is part of the guess and is written."""
+    _need_bc("mg_sweepBoundary")(int(N), float(L), float(shift), float(omega), _kinds(bc), _opt(a), _opt(U_in), F.ptr, U_out.ptr)
+    _check()
+
+
+def residualBoundary(N, L, shift, bc, a, U, F, D, sign=1):
+    """Test hook (include/mg_bc.h).  D = sign*(inv*b(U) - F) at the unknowns, sign*0 at data points; bc: S, N, W, E."""
+    _need_bc("mg_residualBoundary")(int(N), float(L), float(shift), _kinds(bc), _opt(a), U.ptr, F.ptr, D.ptr, int(sign))
+    _check()
+
+
+def restrictBoundary(N, bc, D, M, F_c):
+    """Test hook (include/mg_bc.h).  F_c (M x M) = the restriction of D (N x N) at the coarse unknowns, +0 at coarse data
+    points; bc: S, N, W, E."""
+    _need_bc("mg_restrictBoundary")(int(N), _kinds(bc), D.ptr, int(M), F_c.ptr)
+    _check()
+
+
+def prolongAddBoundary(M, bc, U_c, N, U_in, U_out):
+    """Test hook (include/mg_bc.h).  U_out = U_in + P(U_c) at the fine unknowns -- the rim of Neumann sides is written --,
+    U_in at fine data points; bc: S, N, W, E."""
+    _need_bc("mg_prolongAddBoundary")(int(M), _kinds(bc), U_c.ptr, int(N), U_in.ptr, U_out.ptr)
     _check()
 
 
@@ -1100,9 +1243,13 @@ class Solver:
     preconditioner (include/mg_krylov.h): the residual norm then cannot grow, and coefficients on which the plain cycle
     is slow or diverges (jumps, strong contrast) converge.  It costs memory, (2m + 1)*N^2 doubles allocated when it is
     switched on (8.7 GB at N = 8192 for m = 8), and 120 + 24k bytes per point and iteration.  Convergence is only stated on a
-    recomputed residual, never on the recurred norm; info gains `breakdown`.  krylov=0 (the default) is the plain solver, bit for bit."""
+    recomputed residual, never on the recurred norm; info gains `breakdown`.  krylov=0 (the default) is the plain solver, bit for bit.
+    bc=kinds (or set_boundary(kinds)) makes sides Neumann (include/mg_bc.h): four kinds in the order S, N, W, E -- row 0, row
+    N-1, column 0, column N-1 -- as a sequence of DIRICHLET / NEUMANN or a string such as "ndnd".  On Neumann sides the rim of
+    U is part of the guess and is written; flux data goes into F with neumann_source()."""
 
     def __init__(self, N, L=1.0, coef=None, krylov=0, **opts):
+        bc = opts.pop("bc", None)   # (the boundary kinds travel beside the solve options, not in mg_solve_opts)
         self.N, self.L = int(N), float(L)
         self.opts = solve_opts(**opts)
         self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
@@ -1114,6 +1261,8 @@ class Solver:
                 self.set_coefficient(coef)
             if krylov:
                 self.set_krylov(krylov)
+            if bc is not None:
+                self.set_boundary(bc)
         except Exception:
             self.close()
             raise
@@ -1159,6 +1308,27 @@ class Solver:
     @property
     def has_coefficient(self):
         return bool(_need_vc("mg_solver_has_coefficient")(self._s))
+
+    def set_boundary(self, bc):
+        """bc: the four kinds in the order S, N, W, E (row 0, row N-1, column 0, column N-1), a sequence of DIRICHLET (0) /
+        NEUMANN (1) or a string of 'd' / 'n'; None or four Dirichlet sides take the boundary away (the plain solver again, bit
+        for bit).  A Neumann side is homogeneous, dU/dn = 0, discretised with a mirrored ghost point (include/mg_bc.h); flux
+        data dU/dn = g goes into F with neumann_source().  On Neumann sides the rim of U is part of the guess and is written by
+        the solve; points on Dirichlet sides (corners shared with a Neumann side included) stay data.  Works with and without
+        a coefficient and in either order with set_coefficient.  A refusal (MGError) leaves the solver and its earlier kinds
+        as they were: "[2]" a kind outside {0, 1}; "[3]" four Neumann sides with shift == 0 (the singular problem), a solver
+        created with fmg != 0, krylov switched on.  While a boundary is set, set_krylov(m > 0) and adjoint() are refused."""
+        status = _need_bc("mg_solver_set_boundary")(self._s, _kinds(bc))
+        if status:
+            _check()
+            raise MGError(f"mg_solver_set_boundary failed with status {status}")
+
+    @property
+    def boundary(self):
+        """the four kinds (S, N, W, E) as a tuple of DIRICHLET / NEUMANN"""
+        out = (C.c_int * 4)()
+        _need_bc("mg_solver_boundary")(self._s, out)
+        return tuple(int(v) for v in out)
 
     def solve_ptr(self, F_ptr, U_ptr):
         """F_ptr, U_ptr: device addresses of N x N fp64 arrays (U in/out), on the engine stream."""
@@ -1313,7 +1483,9 @@ def solve(F, U=None, L=1.0, **opts):
     (U then only supplies the rim).  coef=a (N x N, > 0, at the grid points) solves div(a grad U) - sigma*U = F with faces
     averaging their two nodes (Solver.set_coefficient); a == 1 everywhere is the solve without coef, bit for bit.
     krylov=m (1..16) wraps the cycle in restarted GCR(m) (Solver.set_krylov, include/mg_krylov.h): (2m + 1)*N^2 doubles of
-    memory more, a residual norm that cannot grow, and convergence stated on a recomputed residual only."""
+    memory more, a residual norm that cannot grow, and convergence stated on a recomputed residual only.
+    bc=kinds makes sides Neumann (Solver.set_boundary): four kinds in the order S, N, W, E (row 0, row N-1, column 0, column
+    N-1), e.g. "ndnd"; on Neumann sides the rim of U is part of the guess and is written."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:
@@ -2074,6 +2246,19 @@ def heat_rhs_coef(N, L, nu, dt, theta, a, U, Q=None, F=None):
     return F
 
 
+def heat_rhs_boundary(N, L, nu, dt, theta, bc, a, U, Q=None, F=None):
+    """mg_heat_rhs_boundary on DeviceGrids: heat_rhs_coef evaluated at every unknown of the boundary kinds bc (S, N, W, E: row
+    0, row N-1, column 0, column N-1) with mirrored neighbours beyond Neumann sides, +0 at data points (include/mg_bc.h);
+    theta = 1 reads no neighbour and no coefficient.  a = None is a = 1.  Q = None: no source.  F = None: a new DeviceGrid.  On
+    Neumann sides the rim of U is part of the field.  Returns F."""
+    fn = _need_bc("mg_heat_rhs_boundary")
+    if F is None:
+        F = DeviceGrid((N, N))
+    fn(int(N), float(L), float(nu), float(dt), float(theta), _kinds(bc), _opt(a), U.ptr, _opt(Q), F.ptr)
+    _check()
+    return F
+
+
 class HeatStepper:
     """Time stepper of include/mg_heat.h: the theta-scheme (theta = 1 backward Euler, 0.5 Crank-Nicolson) for
     u_t = nu*Laplace(u) + q on the N x N grid of the solvers, Dirichlet values on the rim of U.  One step is one launch of
@@ -2112,6 +2297,25 @@ class HeatStepper:
     def has_coefficient(self):
         """True while a coefficient is set (set_coefficient)."""
         return bool(_need_heat_vc("mg_heat_stepper_has_coefficient")(self._s))
+
+    def set_boundary(self, bc):
+        """bc: the four kinds of the walls in the order S, N, W, E (row 0, row N-1, column 0, column N-1), as
+        Solver.set_boundary takes them; None or four Dirichlet sides: the stepper as it was.  Neumann walls are insulated
+        (du/dn = 0); a constant wall flux enters through the source, Q_eff = Q + nu*(2/h)*a*g at the wall points
+        (include/mg_bc.h).  On Neumann sides the rim of U is part of the field and is written by every step.  k steps equal,
+        bit for bit, k times {heat_rhs_boundary, Solver(shift=sigma, bc=bc, coef=a).solve}.  Refused (MGError, the stepper
+        stays as it was): what Solver.set_boundary refuses, and "[3]" a stepper with max_batch > 1."""
+        kinds = _kinds(bc)
+        status = _need_bc("mg_heat_stepper_set_boundary")(self._s, kinds)
+        if status:
+            _check()
+            raise MGError(f"mg_heat_stepper_set_boundary failed with status {status}")
+        self._bc = tuple(int(v) for v in kinds)
+
+    @property
+    def boundary(self):
+        """the four kinds (S, N, W, E) as a tuple of DIRICHLET / NEUMANN"""
+        return getattr(self, "_bc", (0, 0, 0, 0))
 
     def step_ptrs(self, U_ptrs, Q_ptrs=None, steps=1):
         """U_ptrs: device addresses of N x N fp64 arrays (16-byte aligned, stepped in place); Q_ptrs: None, or as many

@@ -204,6 +204,10 @@ int mg_solver_adjoint(mg_solver *s, const double *Ubar, const double *U, double 
         fail(MG_ERR_ARG, "mg_solver_adjoint: every array must be 16-byte aligned");
         return refuse(MG_ERR_ARG);
     }
+    if (solver_boundary(s)) {   // (include/mg_bc.h: the gradient kernels treat the whole rim as data)
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_adjoint: a boundary with a Neumann side is set; the adjoint is not built for boundary kinds");
+        return refuse(MG_ERR_UNSUPPORTED);
+    }
     double L = 1.0;
     const int N = solver_size(s, &L);
     const double *coef = solver_coefficient(s);   // (the solver's own level-0 array: what the solve itself reads)

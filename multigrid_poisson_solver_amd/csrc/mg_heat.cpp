@@ -275,8 +275,13 @@ int mg_heat_stepper_step(mg_heat_stepper *s, int n, double *const *U_dev, const 
     int status = MG_SOLVE_CONVERGED;
     // (max_batch == 1 with a coefficient and theta != 1: the variable right-hand side on the solver's level-0 coefficient)
     const double *coef = s->single && s->hc.lap ? solver_coefficient(s->single) : nullptr;
+    // (include/mg_bc.h: with a boundary the right-hand side runs over the unknowns, whatever theta)
+    const int *kind = s->single ? solver_boundary(s->single) : nullptr;
     for (int step = 0; step < steps && status == MG_SOLVE_CONVERGED; ++step) {
-        if (coef) {
+        if (kind) {
+            ProfScope ps("heat_rhs_bc", s->N, s->hc.lap && solver_coefficient(s->single) ? rhs_vc_bytes(s->N, any_q) : rhs_bytes(s->N, any_q));
+            k::heat_rhs_bc(st, s->N, s->hc, kind, solver_coefficient(s->single), U_dev[0], Q_dev ? Q_dev[0] : nullptr, s->F);
+        } else if (coef) {
             ProfScope ps("heat_rhs_vc", s->N, rhs_vc_bytes(s->N, any_q));
             k::heat_rhs_vc(st, s->N, s->hc, coef, U_dev[0], Q_dev ? Q_dev[0] : nullptr, s->F);
         } else {
@@ -324,6 +329,58 @@ int mg_heat_stepper_set_coefficient(mg_heat_stepper *s, const double *a_dev)
 }
 
 int mg_heat_stepper_has_coefficient(const mg_heat_stepper *s) { return s && s->single ? mg_solver_has_coefficient(s->single) : 0; }
+
+// ------------------------------------------------------------------ boundary kinds per side (include/mg_bc.h)
+void mg_heat_rhs_boundary(int N, double L, double nu, double dt, double theta, const int *kind, const double *a_dev,
+                          const double *U, const double *Q, double *F)
+{
+    if (!require_ready("mg_heat_rhs_boundary")) return;
+    if (N < 3 || !finite_positive(L) || !U || !F) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_boundary: N = %d (at least 3), L = %g (positive, finite) or a NULL array", N, L);
+        return;
+    }
+    if (!scheme_ok("mg_heat_rhs_boundary", nu, dt, theta)) return;
+    if (!kind || ((kind[0] | kind[1] | kind[2] | kind[3]) & ~1) != 0) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_boundary: kind must be a host int[4] of MG_BC_DIRICHLET (0) / MG_BC_NEUMANN (1)");
+        return;
+    }
+    if (((uintptr_t)a_dev | (uintptr_t)U | (uintptr_t)Q | (uintptr_t)F) % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_boundary: a, U, Q and F must be 16-byte aligned");
+        return;
+    }
+    const size_t bytes = (size_t)N * N * sizeof(double);
+    if (overlap(F, U, bytes) || (Q && overlap(F, Q, bytes)) || (a_dev && overlap(F, a_dev, bytes))) {
+        fail(MG_ERR_ARG, "mg_heat_rhs_boundary: F overlaps a, U or Q");
+        return;
+    }
+    const k::HeatConsts c = heat_consts(N, L, nu, dt, theta);
+    {
+        ProfScope ps("heat_rhs_bc", N, a_dev && c.lap ? rhs_vc_bytes(N, Q != nullptr) : rhs_bytes(N, Q != nullptr));
+        k::heat_rhs_bc(ctx().stream, N, c, kind, a_dev, U, Q, F);
+    }
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+int mg_heat_stepper_set_boundary(mg_heat_stepper *s, const int *kind)
+{
+    if (!require_ready("mg_heat_stepper_set_boundary")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_heat_stepper_set_boundary: NULL stepper");
+        return MG_ERR_ARG;
+    }
+    if (!s->single) {
+        if (kind && ((kind[0] | kind[1] | kind[2] | kind[3]) == 0)) return MG_OK;   // (a batched stepper never has one)
+        if (!kind) {
+            fail(MG_ERR_ARG, "mg_heat_stepper_set_boundary: NULL kind (a host int[4]: S, N, W, E)");
+            return MG_ERR_ARG;
+        }
+        fail(MG_ERR_UNSUPPORTED, "mg_heat_stepper_set_boundary: the stepper was created with max_batch = %d; the batched solver "
+                                 "has no boundary kinds", s->max_batch);
+        return MG_ERR_UNSUPPORTED;
+    }
+    // the solver checks and keeps the kinds; its refusal -- code and text -- is the stepper's, and leaves both as they were
+    return mg_solver_set_boundary(s->single, kind);
+}
 
 void mg_heat_stepper_destroy(mg_heat_stepper *s)
 {

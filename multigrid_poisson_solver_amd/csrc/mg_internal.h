@@ -493,6 +493,29 @@ void coef_check_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *i
 // expression and its order: include/mg_heat_vc.h).  c.lap must be set: theta == 1 reads no coefficient and goes to heat_rhs.
 // F = rhs(A, U, Q) (Q == nullptr: no source); the rim of F is +0, nothing else is written
 void heat_rhs_vc(hipStream_t s, int N, const HeatConsts &c, const double *A, const double *U, const double *Q, double *F);
+// boundary kinds per side (mg_bc_kernels.hip, driven by mg_solve.cpp and mg_heat.cpp; the expressions and their order:
+// include/mg_bc.h).  kind: host int[4], S, N, W, E, each 0 (Dirichlet) or 1 (Neumann); A == nullptr: a = 1.  The `_vc`
+// launchers above with the unknowns in the interior's place and mirrored neighbours beyond a Neumann side.
+void wjacobi_bc(hipStream_t s, int N, double dx2, double sd, double omega, const int *kind, const double *A, const double *in,
+                const double *F, double *out);
+void residual_bc(hipStream_t s, int N, double inv, double sd, const int *kind, const double *A, const double *U, const double *F,
+                 double *D, int sign);
+void apply_bc(hipStream_t s, int N, double inv, double sd, const int *kind, const double *A, const double *U, double *out);
+// *out = the L2 norm of the residual over the unknowns (U == nullptr: of F), partition and order of resnorm
+void resnorm_bc(hipStream_t s, int N, double inv, double sd, const int *kind, const double *A, const double *U, const double *F,
+                double *part, double *out);
+void gauss_seidel_relative_bc(hipStream_t s, int N, double h2, double inv, double sd, const int *kind, const double *A, double *U,
+                              const double *F, double atol, double rtol, int max_iters, int *state, double *err_out);
+// Fc (M x M) = the restriction of D (N x N) at the coarse unknowns, +0 at coarse data points; t = restrict_table(N, M)
+void restrict_bc(hipStream_t s, int N, const int *kind, const double *D, int M, double *Fc, const RestrictTable &t);
+// Uout = Uin + P(Uc) at the fine unknowns, Uin at fine data points; lo, w: mg_boundary_prolongation_table(M, N) in device memory
+void prolong_add_bc(hipStream_t s, int M, const int *kind, const double *Uc, int N, const double *Uin, double *Uout, const int *lo,
+                    const double *w);
+// Fout = F - (t*a)*g at the rim unknowns of Neumann sides (G: 4 x N, rows S, N, W, E), a copy elsewhere
+void neumann_source(hipStream_t s, int N, double t, const int *kind, const double *A, const double *F, const double *G, double *Fout);
+// the heat right-hand side at the unknowns, +0 at data points (c.lap == false: no neighbour and no coefficient is read)
+void heat_rhs_bc(hipStream_t s, int N, const HeatConsts &c, const int *kind, const double *A, const double *U, const double *Q,
+                 double *F);
 // Krylov acceleration of the residual-tolerance solver (mg_krylov_kernels.hip, driven by mg_solve.cpp; the method and the
 // order of every operation: include/mg_krylov.h).  All sums run over the interior; no rim is read into a result or written.
 constexpr int KRYLOV_MAX_K = MG_KRYLOV_MAX_M - 1;   // stored directions an iteration orthogonalises against
@@ -616,6 +639,12 @@ int solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<dou
 // the level-0 coefficient of a solver, mg_solver::coef[0] (mg_solve.cpp), nullptr when none is set: the heat stepper's
 // right-hand-side kernel reads the solver's own array instead of keeping a second copy (mg_heat.cpp)
 const double *solver_coefficient(const mg_solver *s);
+// the cycle with boundary kinds per side (include/mg_bc.h): solve_vcycle_vc's node order and launch count with the `_bc`
+// kernels; coef == nullptr: a = 1; p_lo[l], p_w[l]: mg_boundary_prolongation_table(sizes[l+1], sizes[l]) in device memory
+int solve_vcycle_bc(hipStream_t st, const SolveLevels &lv, const int *kind, const std::vector<double *> *coef,
+                    const std::vector<int *> &p_lo, const std::vector<double *> &p_w, const double *F0, double *U0);
+// the four kinds of a solver (mg_solver::bc, S, N, W, E), nullptr when every side is Dirichlet
+const int *solver_boundary(const mg_solver *s);
 // what a driver over the solvers needs of their shape (mg_adjoint.cpp): N, and L / max_batch where asked for
 int solver_size(const mg_solver *s, double *L);
 int batch_solver_size(const mg_batch_solver *s, double *L, int *max_batch);

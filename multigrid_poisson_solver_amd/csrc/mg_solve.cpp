@@ -37,6 +37,11 @@ struct mg_solver {
     int *coef_flag = nullptr;                // device: the check found a value that is not finite or not > 0
     int *host_coef_flag = nullptr;           // pinned
     bool coef_set = false;
+    // boundary kinds per side (include/mg_bc.h; nothing of it is allocated before the first Neumann side is set)
+    int bc[4] = {0, 0, 0, 0};                // S, N, W, E
+    bool bc_set = false;                     // some side is Neumann
+    std::vector<int *> bc_lo;                // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
+    std::vector<double *> bc_w;
     // Krylov acceleration (include/mg_krylov.h; nothing of it is allocated before the first enabling mg_solver_set_krylov)
     int kr_m = 0;                            // 0: off
     double *kr_r = nullptr;                  // the residual r
@@ -104,6 +109,8 @@ void release(mg_solver *s)
             if (t.w) (void)hipFree(t.w);
         }
     for (double *p : s->coef) if (p) (void)hipFree(p);
+    for (int *p : s->bc_lo) if (p) (void)hipFree(p);
+    for (double *p : s->bc_w) if (p) (void)hipFree(p);
     if (s->coef_flag) (void)hipFree(s->coef_flag);
     if (s->host_coef_flag) (void)hipHostFree(s->host_coef_flag);
     for (auto *v : {&s->kr_Z, &s->kr_Q})
@@ -265,7 +272,66 @@ int mg::solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector
     return launches;
 }
 
+// the cycle above with the boundary-kind kernels (include/mg_bc.h): the same node order, ping-pong and launch count, each
+// `_vc` kernel replaced by its `_bc` form (coef == nullptr: a = 1) and the transfers by the ones that cover the rim
+int mg::solve_vcycle_bc(hipStream_t st, const SolveLevels &lv, const int *kind, const std::vector<double *> *coef,
+                        const std::vector<int *> &p_lo, const std::vector<double *> &p_w, const double *F0, double *U0)
+{
+    const mg_solve_opts &o = *lv.o;
+    const std::vector<int> &sizes = *lv.sizes;
+    const int nl = (int)sizes.size(), top = 0;
+    int launches = 0;
+    const std::vector<LevelConsts> &lc = *lv.lc;
+    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
+    auto sd = [&](int l) { return o.shift * lc[l].dx2; };
+    auto a = [&](int l) -> const double * { return coef ? (*coef)[l] : nullptr; };
+    for (int l = top; l + 1 < nl; ++l) {
+        const int N = sizes[l], M = sizes[l + 1];
+        const double dx2 = lc[l].dx2;
+        const double *F = l == top ? F0 : lv.F[l];
+        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
+        int sweeps = o.pre;
+        if (l > top) {
+            k::wjacobi_bc(st, N, dx2, sd(l), o.omega, kind, a(l), nullptr, F, cur);
+            ++launches;
+            --sweeps;
+        }
+        for (int i = 0; i < sweeps; ++i) {
+            k::wjacobi_bc(st, N, dx2, sd(l), o.omega, kind, a(l), cur, F, other);
+            ++launches;
+            std::swap(cur, other);
+        }
+        k::residual_bc(st, N, lc[l].inv, sd(l), kind, a(l), cur, F, other, -1);
+        k::restrict_bc(st, N, kind, other, M, lv.F[l + 1], restrict_table(N, M));
+        launches += 2;
+        x[l] = cur;
+        y[l] = other;
+    }
+    const int last = nl - 1, Nc = sizes[last];
+    k::gauss_seidel_relative_bc(st, Nc, lc[last].dx2, lc[last].inv, sd(last), kind, a(last), lv.A[last], lv.F[last], o.coarse_atol,
+                                o.coarse_rtol, o.coarse_max_iters, lv.gs_state, lv.gs_err);
+    ++launches;
+    x[last] = lv.A[last];
+    for (int l = nl - 2; l >= top; --l) {
+        const int N = sizes[l], Nc_l = sizes[l + 1];
+        const double *F = l == top ? F0 : lv.F[l];
+        double *cur = x[l], *other = y[l];
+        k::prolong_add_bc(st, Nc_l, kind, x[l + 1], N, cur, other, p_lo[l], p_w[l]);
+        ++launches;
+        std::swap(cur, other);
+        for (int i = 0; i < o.post; ++i) {
+            k::wjacobi_bc(st, N, lc[l].dx2, sd(l), o.omega, kind, a(l), cur, F, other);
+            ++launches;
+            std::swap(cur, other);
+        }
+        x[l] = cur;
+    }
+    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return launches;
+}
+
 const double *mg::solver_coefficient(const mg_solver *s) { return s && s->coef_set ? s->coef[0] : nullptr; }
+const int *mg::solver_boundary(const mg_solver *s) { return s && s->bc_set ? s->bc : nullptr; }
 int mg::solver_size(const mg_solver *s, double *L)
 {
     if (L) *L = s->L;
@@ -332,7 +398,10 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0, in
 
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
-    if (s->coef_set)   // (whatever mg_set_smoother says)
+    if (s->bc_set)   // (whatever mg_set_smoother says; top == 0: fmg and a boundary exclude each other)
+        (void)solve_vcycle_bc(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, s->bc,
+                              s->coef_set ? &s->coef : nullptr, s->bc_lo, s->bc_w, F0, U0);
+    else if (s->coef_set)   // (whatever mg_set_smoother says)
         (void)solve_vcycle_vc(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, s->coef,
                               F0, U0, top);
     else if (ctx().smoother == SMOOTHER_SIMPLE)
@@ -381,7 +450,10 @@ void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
     // (the reference norm ||F|| has no operator in it)
-    if (s->coef_set && U0) k::resnorm_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->part, s->dev_scal + slot);
+    if (s->bc_set)   // both norms run over the unknowns
+        k::resnorm_bc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->bc, s->coef_set ? s->coef[0] : nullptr, U0, F0, s->part,
+                      s->dev_scal + slot);
+    else if (s->coef_set && U0) k::resnorm_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->part, s->dev_scal + slot);
     else k::resnorm(st, s->N, s->lc[0].inv, U0, F0, s->part, s->dev_scal + slot, s->lc[0].sh);
 }
 
@@ -797,6 +869,200 @@ void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, 
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
 }
 
+// ------------------------------------------------------------------ boundary kinds per side (include/mg_bc.h)
+namespace {
+bool kinds_ok(const char *who, const int *kind)
+{
+    if (!kind) {
+        fail(MG_ERR_ARG, "%s: NULL kind (a host int[4]: S, N, W, E)", who);
+        return false;
+    }
+    for (int i = 0; i < 4; ++i)
+        if (kind[i] != MG_BC_DIRICHLET && kind[i] != MG_BC_NEUMANN) {
+            fail(MG_ERR_ARG, "%s: kind[%d] = %d is neither MG_BC_DIRICHLET (0) nor MG_BC_NEUMANN (1); Robin and periodic sides "
+                             "are not built", who, i, kind[i]);
+            return false;
+        }
+    return true;
+}
+
+// mg_boundary_prolongation_table(M, N) in device memory
+bool make_bc_table(int M, int N, int **lo_dev, double **w_dev)
+{
+    std::vector<int> lo((size_t)N);
+    std::vector<double> w((size_t)N);
+    mg_boundary_prolongation_table(M, N, lo.data(), w.data());
+    return dev_alloc(lo_dev, lo.size()) && dev_alloc(w_dev, w.size()) &&
+           MG_HIP(hipMemcpy(*lo_dev, lo.data(), lo.size() * sizeof(int), hipMemcpyHostToDevice)) &&
+           MG_HIP(hipMemcpy(*w_dev, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+}  // namespace
+
+void mg_boundary_prolongation_table(int M, int N, int *lo, double *w)
+{
+    if (M < 2 || N < 2 || !lo || !w) {
+        fail(MG_ERR_ARG, "mg_boundary_prolongation_table: M = %d, N = %d (at least 2 each) or a NULL array", M, N);
+        return;
+    }
+    const double h_f = 1.0 / (double)(N - 1), h_c = 1.0 / (double)(M - 1);
+    for (int k = 0; k < N; ++k) {
+        int l = (int)std::floor((double)k * h_f / h_c);
+        if (l > M - 2) l = M - 2;
+        double wt = ((double)k * h_f - (double)l * h_c) / h_c;
+        wt = wt < 0.0 ? 0.0 : (wt > 1.0 ? 1.0 : wt);
+        lo[k] = l;
+        w[k] = wt;
+    }
+    lo[0] = 0;
+    w[0] = 0.0;
+    lo[N - 1] = M - 2;
+    w[N - 1] = 1.0;
+}
+
+int mg_solver_set_boundary(mg_solver *s, const int *kind)
+{
+    if (!require_ready("mg_solver_set_boundary")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_solver_set_boundary: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (!kinds_ok("mg_solver_set_boundary", kind)) return MG_ERR_ARG;
+    const int neumann = kind[0] + kind[1] + kind[2] + kind[3];
+    if (neumann == 0) {   // back to the Dirichlet solver (the tables stay for the next boundary)
+        s->bc_set = false;
+        for (int i = 0; i < 4; ++i) s->bc[i] = 0;
+        return MG_OK;
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: the solver was created with fmg = %d; the full-multigrid start is not "
+                                 "built for boundary kinds", s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (s->kr_m > 0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: the Krylov acceleration is on (m = %d); it is not built for boundary "
+                                 "kinds", s->kr_m);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (neumann == 4 && s->o.shift == 0.0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: four Neumann sides with shift == 0 is the singular problem; fixing the "
+                                 "mean and the compatibility projection are not built");
+        return MG_ERR_UNSUPPORTED;
+    }
+    const int nl = (int)s->sizes.size();
+    if (s->bc_lo.empty()) {   // the first boundary: the prolongation tables of the hierarchy
+        std::vector<int *> lo(nl - 1, nullptr);
+        std::vector<double *> w(nl - 1, nullptr);
+        bool ok = true;
+        for (int l = 0; l + 1 < nl && ok; ++l) ok = make_bc_table(s->sizes[l + 1], s->sizes[l], &lo[l], &w[l]);
+        if (!ok) {   // the solver keeps what it had
+            for (int *p : lo) if (p) (void)hipFree(p);
+            for (double *p : w) if (p) (void)hipFree(p);
+            return MG_ERR_HIP;
+        }
+        s->bc_lo = lo;
+        s->bc_w = w;
+    }
+    for (int i = 0; i < 4; ++i) s->bc[i] = kind[i];
+    s->bc_set = true;
+    return MG_OK;
+}
+
+int mg_solver_boundary(const mg_solver *s, int *kind_out)
+{
+    if (kind_out)
+        for (int i = 0; i < 4; ++i) kind_out[i] = s ? s->bc[i] : 0;
+    return s && s->bc_set ? 1 : 0;
+}
+
+void mg_neumannSource(int N, double L, const int *kind, const double *a_dev, const double *F, const double *g, double *F_out)
+{
+    if (!require_ready("mg_neumannSource") || !vc_args_ok("mg_neumannSource", N, L, 0.0, {F, g, F_out}) ||
+        !kinds_ok("mg_neumannSource", kind))
+        return;
+    if ((uintptr_t)a_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_neumannSource: a must be 16-byte aligned");
+        return;
+    }
+    const double h = L / (double)(N - 1);
+    k::neumann_source(ctx().stream, N, 2.0 / h, kind, a_dev, F, g, F_out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_applyOperatorBoundary(int N, double L, double shift, const int *kind, const double *a_dev, const double *U, double *out)
+{
+    if (!require_ready("mg_applyOperatorBoundary") || !vc_args_ok("mg_applyOperatorBoundary", N, L, shift, {U, out}) ||
+        !kinds_ok("mg_applyOperatorBoundary", kind))
+        return;
+    if ((uintptr_t)a_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_applyOperatorBoundary: a must be 16-byte aligned");
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    k::apply_bc(ctx().stream, N, 1.0 / dx2, shift * dx2, kind, a_dev, U, out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_sweepBoundary(int N, double L, double shift, double omega, const int *kind, const double *a_dev, const double *U_in,
+                      const double *F, double *U_out)
+{
+    if (!require_ready("mg_sweepBoundary") || !vc_args_ok("mg_sweepBoundary", N, L, shift, {F, U_out}) ||
+        !kinds_ok("mg_sweepBoundary", kind))
+        return;
+    if (((uintptr_t)U_in | (uintptr_t)a_dev) % 16 != 0 || !(omega > 0.0 && omega <= 1.0)) {
+        fail(MG_ERR_ARG, "mg_sweepBoundary: a and U_in must be 16-byte aligned, omega = %g inside (0, 1]", omega);
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    k::wjacobi_bc(ctx().stream, N, dx2, shift * dx2, omega, kind, a_dev, U_in, F, U_out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_residualBoundary(int N, double L, double shift, const int *kind, const double *a_dev, const double *U, const double *F,
+                         double *D, int sign)
+{
+    if (!require_ready("mg_residualBoundary") || !vc_args_ok("mg_residualBoundary", N, L, shift, {U, F, D}) ||
+        !kinds_ok("mg_residualBoundary", kind))
+        return;
+    if ((uintptr_t)a_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_residualBoundary: a must be 16-byte aligned");
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    k::residual_bc(ctx().stream, N, 1.0 / dx2, shift * dx2, kind, a_dev, U, F, D, sign < 0 ? -1 : +1);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_restrictBoundary(int N, const int *kind, const double *D, int M, double *F_c)
+{
+    if (!require_ready("mg_restrictBoundary") || !kinds_ok("mg_restrictBoundary", kind)) return;
+    if (N < 3 || M < 2 || !D || !F_c) {
+        fail(MG_ERR_ARG, "mg_restrictBoundary: N = %d (at least 3), M = %d (at least 2) or a NULL array", N, M);
+        return;
+    }
+    const RestrictTable &t = restrict_table(N, M);   // (refuses a table that leaves the fine grid)
+    if (!t.lo) return;
+    k::restrict_bc(ctx().stream, N, kind, D, M, F_c, t);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_prolongAddBoundary(int M, const int *kind, const double *U_c, int N, const double *U_in, double *U_out)
+{
+    if (!require_ready("mg_prolongAddBoundary") || !kinds_ok("mg_prolongAddBoundary", kind)) return;
+    if (N < 3 || M < 2 || !U_c || !U_in || !U_out) {
+        fail(MG_ERR_ARG, "mg_prolongAddBoundary: M = %d (at least 2), N = %d (at least 3) or a NULL array", M, N);
+        return;
+    }
+    // (the solver keeps its tables from its first boundary on; this entry point builds the one it needs and lets go of it)
+    int *lo = nullptr;
+    double *w = nullptr;
+    if (make_bc_table(M, N, &lo, &w)) {
+        k::prolong_add_bc(ctx().stream, M, kind, U_c, N, U_in, U_out, lo, w);
+        (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+    }
+    if (lo) (void)hipFree(lo);
+    if (w) (void)hipFree(w);
+}
+
 // ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov.h)
 int mg_solver_set_krylov(mg_solver *s, int m)
 {
@@ -808,6 +1074,11 @@ int mg_solver_set_krylov(mg_solver *s, int m)
     if (s->o.fmg != 0) {
         fail(MG_ERR_UNSUPPORTED, "mg_solver_set_krylov: the solver was created with fmg = %d; the full-multigrid start is not "
                                  "combined with the Krylov acceleration", s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (m > 0 && s->bc_set) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_krylov: a boundary with a Neumann side is set; the Krylov acceleration is not built "
+                                 "for boundary kinds (its sums and its operator run over the interior)");
         return MG_ERR_UNSUPPORTED;
     }
     const int have = (int)s->kr_Z.size();
