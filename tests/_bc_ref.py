@@ -346,9 +346,30 @@ def residual_ld(a, U, F, L, shift, bc):
     return A @ np.asarray(U, dtype=LD).reshape(-1) - np.asarray(F, dtype=LD).reshape(-1)[unk]
 
 
-def residual_rounding_bound(a, U, F, L, shift, bc):
+def residual_ld_stencil(a, U, F, L, shift, bc):
+    """residual_ld without the matrix, for sizes at which the dense operator does not fit: the same faces (the mean of two
+    nodes, the mirror node beyond a Neumann side) and the same diagonal, evaluated on the padded arrays in longdouble.  Flat,
+    in the order of the unknowns.  a = None: a = 1; a scalar: that constant."""
+    N = F.shape[0]
+    u = unknowns(N, bc)
+    A = np.ones((N, N), dtype=LD) if a is None else np.broadcast_to(np.asarray(a, dtype=LD), (N, N))
+    Pa, P = pad(A, bc), pad(np.asarray(U, dtype=LD), bc)
+    half = LD(1) / LD(2)
+    c, x = Pa[1:-1, 1:-1], P[1:-1, 1:-1]
+    acc, diag = np.zeros((N, N), dtype=LD), np.zeros((N, N), dtype=LD)
+    for rows, cols in ((slice(2, None), slice(1, -1)), (slice(None, -2), slice(1, -1)), (slice(1, -1), slice(2, None)),
+                       (slice(1, -1), slice(None, -2))):
+        face = half * (c + Pa[rows, cols])
+        acc = acc + face * P[rows, cols]
+        diag = diag + face
+    r = ref._inv_ld(N, L) * (acc - diag * x) - LD(shift) * x - np.asarray(F, dtype=LD)
+    return r[u].reshape(-1)
+
+
+def residual_rounding_bound(a, U, F, L, shift, bc, r=None):
     """_solve_vc_ref.residual_rounding_bound extended to the rim unknowns: the same count of roundings per term, the
-    neighbours taken through the mirror"""
+    neighbours taken through the mirror.  r: the longdouble residual where the caller has it (residual_ld_stencil at the
+    sizes the dense operator does not reach); None: residual_ld."""
     N = F.shape[0]
     u = unknowns(N, bc)
     P = np.abs(pad(np.asarray(U, dtype=LD), bc))
@@ -357,7 +378,8 @@ def residual_rounding_bound(a, U, F, L, shift, bc):
     d = LD(4) * amax + LD(shift) / inv
     nbr = inv * amax * (P[2:, 1:-1] + P[:-2, 1:-1] + P[1:-1, 2:] + P[1:-1, :-2]) + np.abs(np.asarray(F, dtype=LD))
     mag = (11 * nbr + 16 * inv * d * P[1:-1, 1:-1])[u]
-    r = residual_ld(a, U, F, L, shift, bc)
+    if r is None:
+        r = residual_ld(a, U, F, L, shift, bc)
     return U53 * np.sqrt(np.sum(mag ** 2)) + LD(n_unknowns(N, bc)) * U53 * np.sqrt(np.sum(r ** 2))
 
 

@@ -14,6 +14,9 @@ otherwise.
   Perturbed       heat: u_0 = P + A*m with P = ref.CUBIC held steady by Q = -nu*Laplace(P) and m the discrete sine mode
                   (k, l).  The stencil is exact on P and m is its eigenvector, so the theta-scheme gives
                   u_n = P + A*rho^n*m, rho = (sigma - beta*lambda_kl)/(sigma + lambda_kl).
+  mixed_mode      boundary kinds per side (include/mg_bc.h): the eigenvectors of the 5-point Laplacian with a mirrored ghost
+                  point beyond every Neumann side, one sine or cosine factor per axis, for all 16 kinds; check_mode_solve holds
+                  a solve against one, and Perturbed(steady=False, bc=...) a heat stepper (pure decay, u_n = rho^n*u_0).
   MovingRim       heat: u = P + t*R, R = ref.HARMONIC, Q = R - nu*Laplace(P): linear in time, so every theta-scheme
                   reproduces it exactly -- when the right-hand side is formed on the old rim and the solve runs on the new one.
 
@@ -142,6 +145,101 @@ def mode_eigenvalue(N, L, k, l):
     return 4 * ref._inv_ld(N, L) * (np.sin(pi * LD(k) / LD(2 * (N - 1))) ** 2 + np.sin(pi * LD(l) / LD(2 * (N - 1))) ** 2)
 
 
+# ---------------------------------------------------------------- boundary kinds: the modes of the mirrored operator
+def _axis_kinds(bc):
+    """((low end, high end) of the column axis, of the row axis) as booleans `Neumann`, from the kinds S, N, W, E (row 0, row
+    N-1, column 0, column N-1) given as a string of 'd' / 'n' or four 0 / 1"""
+    kS, kN, kW, kE = [(ch in "nN") if isinstance(ch, str) else bool(ch) for ch in bc]
+    return (kW, kE), (kS, kN)
+
+
+def _axis_range(N, lo, hi):
+    """the admissible indices of one axis, one per unknown: d-d 1 .. N-2, n-n 0 .. N-1, mixed 0 .. N-2"""
+    if lo and hi:
+        return 0, N - 1
+    return (0, N - 2) if lo or hi else (1, N - 2)
+
+
+def _axis_factor(N, lo, hi, m):
+    """The factor of one axis (table in the docstring of mixed_mode) in longdouble.  theta*i = pi*(2m + delta)*i / (2(N-1))
+    with delta = 1 for unlike ends; the product is reduced in integers (period 4(N-1)) before it meets pi.  A Dirichlet end
+    is forced to an exact zero, as with_rim does for the sine mode: sin(pi) and cos(pi/2) round to 1e-20, not to 0."""
+    first, last = _axis_range(N, lo, hi)
+    assert first <= m <= last, f"index {m} outside {first} .. {last}"
+    i = np.arange(N, dtype=np.int64)
+    num = ((2 * m + (1 if lo != hi else 0)) * i) % (4 * (N - 1))
+    angle = ref._ld_pi() * num.astype(LD) / LD(2 * (N - 1))
+    f = np.cos(angle) if lo else np.sin(angle)
+    if not lo:
+        f[0] = 0
+    if not hi:
+        f[-1] = 0
+    return f
+
+
+def _axis_theta(N, lo, hi, m):
+    return ref._ld_pi() * (LD(2 * m + 1) / 2 if lo != hi else LD(m)) / LD(N - 1)
+
+
+def mixed_mode(N, bc, k, l):
+    """The eigenvector (k, l) of the 5-point Laplacian with a mirrored ghost point beyond every Neumann side, in longdouble:
+    one factor per axis, index k along the columns (kinds W, E), l along the rows (kinds S, N), i the index along the axis:
+
+        low end, high end    factor         theta
+        d, d                 sin(theta i)   k pi/(N-1), k >= 1
+        n, n                 cos(theta i)   k pi/(N-1), k >= 0
+        d, n                 sin(theta i)   (k + 1/2) pi/(N-1)
+        n, d                 cos(theta i)   (k + 1/2) pi/(N-1)
+
+    sin vanishes at a Dirichlet low end and cos is even about a Neumann one; theta is what makes the high end do the same.
+    Points on Dirichlet sides are exact zeros."""
+    (kW, kE), (kS, kN) = _axis_kinds(bc)
+    return _axis_factor(N, kS, kN, l)[:, None] * _axis_factor(N, kW, kE, k)[None, :]
+
+
+def mixed_mode_eigenvalue(N, L, bc, k, l):
+    """lambda of the discrete Laplacian on mixed_mode(N, bc, k, l): -(4/h^2)(sin^2(theta_x/2) + sin^2(theta_y/2)) <= 0."""
+    (kW, kE), (kS, kN) = _axis_kinds(bc)
+    return -4 * ref._inv_ld(N, L) * (np.sin(_axis_theta(N, kW, kE, k) / 2) ** 2 + np.sin(_axis_theta(N, kS, kN, l) / 2) ** 2)
+
+
+def lambda_min(N, L, bc):
+    """The smallest |lambda| over the admissible (k, l): the lowest index of each axis.  0 for four Neumann sides."""
+    (kW, kE), (kS, kN) = _axis_kinds(bc)
+    return -mixed_mode_eigenvalue(N, L, bc, _axis_range(N, kW, kE)[0], _axis_range(N, kS, kN)[0])
+
+
+def check_mode_solve(U, info, star, F, L, sigma, bc, lam_min, what, coef=None):
+    """A solve of (c*Laplace_h - sigma)U = F whose exact discrete solution is the longdouble `star` (a mixed_mode; c the
+    constant coefficient, None: 1; lam_min = c*lambda_min), in the shape of test_solve_bc_gpu.test_against_the_direct_solution.
+    diag(w)*A is symmetric for the trapezoid weights w, 1/4 <= w <= 1 on the unknowns, so ||(A - sigma)^-1|| <=
+    1/(lam_min + sigma) in the w-norm and ||x||_w <= ||x||_2 <= 2||x||_w:
+
+        max|U - U*| <= 2*(||r(U)||_2 + ||r(fp64(U*))||_2) / (lam_min + sigma)
+
+    with both residuals in longdouble against F (_bc_ref.residual_ld_stencil: the dense matrix's expressions); the reported
+    res within _bc_ref.residual_rounding_bound of ||r(U)||_2; and teeth: the bound is at most 1e-6*max|U*|.  info = None (the
+    restatement): the line on res is left out.  Returns (error, bound), relative to max|U*|."""
+    import _bc_ref as bref
+    X = r64(star)
+    rU, rX = together(lambda: bref.residual_ld_stencil(coef, U, F, L, sigma, bc), lambda: bref.residual_ld_stencil(coef, X, F, L, sigma, bc))
+    nU, nX = np.sqrt(np.sum(rU ** 2)), np.sqrt(np.sum(rX ** 2))
+    err = np.max(np.abs(np.asarray(U, dtype=LD) - X.astype(LD)))      # (against the fp64 array U* rounds to, as check_vc_truth)
+    bound = 2 * (nU + nX) / (LD(lam_min) + LD(sigma))
+    top = np.max(np.abs(star))
+    print(f"{what}: |U - U*| {float(err):.3e} <= {float(bound):.3e} (relative {float(err / top):.2e} <= {float(bound / top):.2e}), "
+          f"r(U) {float(nU):.3e}, r(U*) {float(nX):.3e}")
+    assert err <= bound, f"{what}: max|U - U*| = {float(err):.6e} above {float(bound):.6e}"
+    assert bound <= LD(1e-6) * top, f"{what}: no teeth: bound {float(bound):.3e} against max|U*| = {float(top):.3e}"
+    if info is not None:
+        a = None if coef is None else np.full(F.shape, float(coef))
+        R = bref.residual_rounding_bound(a, U, F, L, sigma, bc, r=rU)
+        print(f"{what}: {info['cycles']} cycles, res {info['res']:.6e} vs {float(nU):.6e} (bound {float(R):.3e})")
+        assert info["converged"], f"{what}: not converged after {info['cycles']} cycles"
+        assert abs(LD(info["res"]) - nU) <= R, f"{what}: res {info['res']!r} is not the residual of U, {float(nU)!r}"
+    return float(err / top), float(bound / top)
+
+
 class Perturbed:
     """u_0 = P + A*m, Q = -nu*Laplace(P) (steady=False: P = 0 and no Q, pure decay).  .U0 and .Q are the fp64 arrays a stepper
     is given (.Q None without P); exact(n) is u_n in longdouble; bound(n, rtol) is the a-priori bound on ||U_n - u_n||_2 of
@@ -156,14 +254,23 @@ class Perturbed:
     of sigma + A_h.  F*_k is the right-hand side formed in longdouble from the exact u_{k-1}, with
     Laplace_h u = Laplace(P) - lambda_kl*A*rho^{k-1}*m.  Nothing in it comes from a run."""
 
-    def __init__(self, N, L, nu, dt, theta, k, l, A, steady=True):
-        self.N, self.L = N, L
+    def __init__(self, N, L, nu, dt, theta, k, l, A, steady=True, bc=None, coef=None):
+        self.N, self.L, self.bc, self.coef = N, L, bc, coef
         if steady:
             self.P, self.lapP = cubic(N, L)
         else:
             self.P, self.lapP = np.zeros((N, N), dtype=LD), np.zeros((N, N), dtype=LD)
-        self.Am = LD(A) * sine_mode(N, k, l)
-        self.lam = mode_eigenvalue(N, L, k, l)
+        if bc is None:
+            assert coef is None
+            self.Am = LD(A) * sine_mode(N, k, l)
+            self.lam = mode_eigenvalue(N, L, k, l)
+            self.lam_min = ref.lambda_min(N, L)
+        else:
+            assert not steady, "the cubic is no solution under a Neumann side"
+            c = LD(1.0 if coef is None else float(coef))
+            self.Am = LD(A) * mixed_mode(N, bc, k, l)
+            self.lam = -c * mixed_mode_eigenvalue(N, L, bc, k, l)
+            self.lam_min = c * lambda_min(N, L, bc)
         self.sigma, self.beta, self.gamma = heat_consts(nu, dt, theta)
         self.rho = (self.sigma - self.beta * self.lam) / (self.sigma + self.lam)
         self.q = -LD(float(nu)) * self.lapP
@@ -178,7 +285,36 @@ class Perturbed:
         lap_h = self.lapP - self.lam * self.rho ** (k - 1) * self.Am
         return -self.sigma * self.exact(k - 1) - self.beta * lap_h - self.gamma * self.q
 
+    def norm(self, X):
+        """the 2-norm the bound is stated in: over the interior, or over every unknown of the boundary kinds (the data points
+        of every field here are zero, so that is the whole grid)"""
+        return ref.norm_ld(X) if self.bc is None else np.sqrt(np.sum(np.asarray(X, dtype=LD) ** 2))
+
+    def _bound_bc(self, n, rtol):
+        """bound() under boundary kinds: A_h is symmetric in the inner product of the trapezoid weights w, 1/4 <= w <= 1
+        on the unknowns, so the step operator has norm <= 1 and ||(A_h + sigma)^-1|| <= 1/(sigma + lam_min) in the w-norm, and
+        ||x||_w <= ||x||_2 <= 2||x||_w: the sum of bound(), every term in the 2-norm, times 2.  R_k is
+        _bc_ref.residual_rounding_bound; eps_k counts 16 roundings on sigma|u| + beta*inv*c*(sum|neighbours| + 4|u|), the
+        neighbours through the mirror; the rounding of u_0 to fp64 is carried along."""
+        import _bc_ref as bref
+        inv = ref._inv_ld(self.N, self.L)
+        c = LD(1.0 if self.coef is None else float(self.coef))
+        a = None if self.coef is None else np.full((self.N, self.N), float(self.coef))
+
+        def delta(k):
+            Fs, uk = self.rhs_star(k), r64(self.exact(k))
+            P = bref.pad(np.abs(self.exact(k - 1)), self.bc)
+            nbr = P[2:, 1:-1] + P[:-2, 1:-1] + P[1:-1, 2:] + P[1:-1, :-2] + 4 * P[1:-1, 1:-1]
+            r = bref.residual_ld_stencil(self.coef, uk, r64(Fs), self.L, float(self.sigma), self.bc)
+            R = bref.residual_rounding_bound(a, uk, r64(Fs), self.L, float(self.sigma), self.bc, r=r)
+            eps = 16 * U53 * self.norm(self.sigma * P[1:-1, 1:-1] + self.beta * inv * c * nbr)
+            return (LD(rtol) * self.norm(Fs) + R + eps) / (self.sigma + self.lam_min)
+
+        return 2 * (sum(together(*[lambda k=k: delta(k) for k in range(1, n + 1)]), LD(0)) + U53 * self.norm(self.exact(0)))
+
     def bound(self, n, rtol):
+        if self.bc is not None:
+            return self._bound_bc(n, rtol)
         inv = ref._inv_ld(self.N, self.L)
 
         def delta(k):
@@ -192,7 +328,7 @@ class Perturbed:
 
     def moved(self, n):
         """||u_n - u_0||_2: what the steps did to the field."""
-        return ref.norm_ld(self.exact(n) - self.exact(0))
+        return self.norm(self.exact(n) - self.exact(0))
 
 
 class MovingRim:
@@ -288,7 +424,7 @@ def check_vc_truth(a, U, exact, F, L, sigma, rtol, a_min, what, info=None, U0=No
 def check_perturbed(p, U, n, rtol, what):
     """||U_n - u_n|| <= p.bound(n, rtol), and the teeth condition bound <= 1e-4*||u_n - u_0||: a wrong sign or factor in the
     scheme moves the field differently by a fraction of ||u_n - u_0||, four orders above the bound."""
-    err = ref.norm_ld(np.asarray(U, dtype=LD) - p.exact(n))
+    err = p.norm(np.asarray(U, dtype=LD) - p.exact(n))
     bound, moved = p.bound(n, rtol), p.moved(n)
     print(f"{what}: rho^n {float(p.rho ** n):.5f}, error {float(err):.3e} bound {float(bound):.3e} "
           f"moved {float(moved):.3e} bound/moved {float(bound / moved):.1e}")
