@@ -1,5 +1,5 @@
 // mg_bc_kernels.hip -- fp64 kernels of the residual-tolerance solver with boundary kinds per side (include/mg_bc.h; driven by
-// mg_solve.cpp: solve_vcycle_bc, and by mg_heat.cpp): the weighted Jacobi sweep, the residual, the operator on its own, the
+// mg_solve.cpp: SolveOperator's members, and by mg_heat.cpp): the weighted Jacobi sweep, the residual, the operator on its own, the
 // norms over the unknowns, the heat right-hand side, the red-black coarse solve, the transfers with rim and the flux source.
 // Built with -ffp-contract=off like every kernel file.  The shapes are mg_varcoef_kernels.hip's: a lane walks 4 rows down its
 // column (any N) or its column pair (even N from PAIR_MIN_N on, 16-byte accesses) with a rolling window of three rows of U and

@@ -614,35 +614,58 @@ void eigs_start(hipStream_t s, int N, double *dst, const double *src);
 // residual-tolerance solver pieces shared by mg_solve.cpp and mg_solve_batch.cpp
 bool solve_opts_ok(const char *who, int N, double L, const mg_solve_opts &o);
 // the constants of one level, formed once at creation in fp64, each operation rounded once and in this order (include/mg_hip.h):
-// dx2 = (L/(N-1))^2, inv = 1/dx2, d = 4 + shift*dx2, q = 1/d, c = omega*q -- 4, 0.25 and 0.25*omega exactly at shift = 0
+// dx2 = (L/(N-1))^2, inv = 1/dx2, sd = shift*dx2, d = 4 + sd, q = 1/d, c = omega*q -- 4, 0.25 and 0.25*omega exactly at shift = 0
 struct LevelConsts {
-    double dx2, inv, d, q, c;
+    double dx2, inv, sd, d, q, c;
     k::Shifted sh;   // {shift != 0, d, q}
 };
 std::vector<LevelConsts> solve_level_consts(const std::vector<int> &sizes, double L, const mg_solve_opts &o);
-// the arrays of one instance's hierarchy (level 0: the caller's F and U, only B[0] is used)
+// the arrays of one instance's hierarchy, per level (level 0: the caller's F and U, only B[0] is used); the vectors are
+// their owner's
 struct SolveLevels {
-    const std::vector<int> *sizes;
-    double L;
-    const mg_solve_opts *o;
-    const std::vector<LevelConsts> *lc;
-    std::vector<double *> A, B, F;
+    const std::vector<double *> *A, *B, *F;
     int *gs_state;
     double *gs_err;   // may be nullptr
 };
-// one V(pre, post) cycle operator by operator (MG_SMOOTHER=simple); returns the kernel launches it enqueued
-// top: the level the cycle starts at, from the non-zero field U0 on the source F0 (both of size sizes[top]; 0: a solve's cycle)
-int solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0, int top = 0);
-// the same cycle -- node order, field ping-pong, launch count -- with the variable-coefficient kernels (include/mg_varcoef.h);
-// coef[l]: the nodal coefficient of level l
-int solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<double *> &coef, const double *F0, double *U0, int top = 0);
+// The operator a hierarchy's levels apply, and with it the kernel family of every operation of the cycle (mg_solve.cpp):
+//   kind set               the `_bc` kernels (include/mg_bc.h) with the level's coefficient or nullptr, restrict_bc and
+//                          prolong_add_bc with the device tables p_lo / p_w; both norms are resnorm_bc
+//   no kind, coef set      the `_vc` kernels (include/mg_varcoef.h) on (dx2, sd, omega, coef[l]), restrict_gather(+1) and prolong
+//                          with the cached tables; the norm with U is resnorm_vc, the reference norm ||F|| the constant resnorm
+//   neither                the constant kernels on cw = lc[l].c and lc[l].sh, the same transfers, resnorm
+// Every pointer is its owner's; l is a level of the hierarchy, N = sizes[l].  All members enqueue on st.
+struct SolveOperator {
+    const mg_solve_opts *o;
+    const std::vector<int> *sizes;
+    const std::vector<LevelConsts> *lc;
+    const int *kind = nullptr;                     // host int[4], S, N, W, E; nullptr: all four sides are Dirichlet
+    const std::vector<double *> *coef = nullptr;   // per level: the nodal coefficient; nullptr: a = 1
+    const std::vector<int *> *p_lo = nullptr;      // per level l < last: mg_boundary_prolongation_table(sizes[l+1], sizes[l])
+    const std::vector<double *> *p_w = nullptr;    // in device memory (read only with kind set)
+
+    const double *a(int l) const { return coef ? (*coef)[l] : nullptr; }
+    // one weighted Jacobi sweep in -> out (in == nullptr: from the zero field)
+    void sweep(hipStream_t st, int l, const double *in, const double *F, double *out) const;
+    // D = -(AU - F)
+    void residual(hipStream_t st, int l, const double *U, const double *F, double *D) const;
+    // Fc (level l + 1) = the restriction of D (level l)
+    void restrict_residual(hipStream_t st, int l, const double *D, double *Fc) const;
+    // the relative coarse solve of the last level from zero
+    void coarse_solve(hipStream_t st, double *U, const double *F, int *gs_state, double *gs_err) const;
+    // Uout (level l) = Uin + P(Uc), Uc of level l + 1
+    void prolong_add(hipStream_t st, int l, const double *Uc, const double *Uin, double *Uout) const;
+    // *out = ||F - AU|| at level 0 (U == nullptr: the reference norm ||F||); part: resnorm_partials(N) doubles
+    void norm(hipStream_t st, const double *U, const double *F, double *part, double *out) const;
+    // out = AU at level 0 for the Krylov acceleration, which boundary kinds refuse: apply_vc whatever the family
+    void apply(hipStream_t st, const double *U, double *out) const;
+};
+// one V(pre, post) cycle operator by operator, one launch per sweep, with the kernels of op; returns the kernel launches it
+// enqueued.  top: the level the cycle starts at, from the non-zero field U0 on the source F0 (both of size sizes[top]; 0: a
+// solve's cycle; above 0: the full-multigrid start, which only the constant operator has)
+int solve_vcycle(hipStream_t st, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0, int top = 0);
 // the level-0 coefficient of a solver, mg_solver::coef[0] (mg_solve.cpp), nullptr when none is set: the heat stepper's
 // right-hand-side kernel reads the solver's own array instead of keeping a second copy (mg_heat.cpp)
 const double *solver_coefficient(const mg_solver *s);
-// the cycle with boundary kinds per side (include/mg_bc.h): solve_vcycle_vc's node order and launch count with the `_bc`
-// kernels; coef == nullptr: a = 1; p_lo[l], p_w[l]: mg_boundary_prolongation_table(sizes[l+1], sizes[l]) in device memory
-int solve_vcycle_bc(hipStream_t st, const SolveLevels &lv, const int *kind, const std::vector<double *> *coef,
-                    const std::vector<int *> &p_lo, const std::vector<double *> &p_w, const double *F0, double *U0);
 // the four kinds of a solver (mg_solver::bc, S, N, W, E), nullptr when every side is Dirichlet
 const int *solver_boundary(const mg_solver *s);
 // what a driver over the solvers needs of their shape (mg_adjoint.cpp): N, and L / max_batch where asked for

@@ -19,7 +19,11 @@ struct mg_solver {
     std::vector<int> sizes;                  // N, N/2, ... >= N_min
     std::vector<LevelConsts> lc;             // per level: spacing, centre coefficient, weight
     std::vector<double *> A, B, F;           // per level (level 0: only B, the scratch field beside the caller's U)
-    double *part = nullptr;                  // norm partials
+    SolveLevels lv{};                        // the vectors above and the coarse solve's slots: set at creation
+    // the operator of the levels: set at creation; op.coef (&coef, or nullptr: none is set) and op.kind (bc, or nullptr: no
+    // side is Neumann) are the solver's state, changed by mg_solver_set_coefficient and mg_solver_set_boundary alone
+    SolveOperator op{};
+    double *part = nullptr;                 // norm partials
     double *dev_scal = nullptr;              // [4]: residual norm, reference norm, coarse err0, coarse err
     int *gs_state = nullptr;                 // [4]
     double *host_scal = nullptr;             // pinned [4]
@@ -36,11 +40,9 @@ struct mg_solver {
     std::vector<double *> coef;              // per level: the nodal coefficient a_l
     int *coef_flag = nullptr;                // device: the check found a value that is not finite or not > 0
     int *host_coef_flag = nullptr;           // pinned
-    bool coef_set = false;
     // boundary kinds per side (include/mg_bc.h; nothing of it is allocated before the first Neumann side is set)
     int bc[4] = {0, 0, 0, 0};                // S, N, W, E
-    bool bc_set = false;                     // some side is Neumann
-    std::vector<int *> bc_lo;                // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
+    std::vector<int *> bc_lo;               // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
     std::vector<double *> bc_w;
     // Krylov acceleration (include/mg_krylov.h; nothing of it is allocated before the first enabling mg_solver_set_krylov)
     int kr_m = 0;                            // 0: off
@@ -156,182 +158,121 @@ bool make_cubic_table(int N_src, int N_dst, bool for_prolongation, k::CubicTable
 
 }  // namespace
 
-// one V(pre, post) cycle from the caller's U (level `top` keeps its guess; coarser levels start from zero), operator by
-// operator: one launch per sweep (MG_SMOOTHER=simple, and the yardstick of the fused cycle below); the launches it enqueued
-int mg::solve_vcycle_simple(hipStream_t st, const SolveLevels &lv, const double *F0, double *U0, int top)
+// ------------------------------------------------------------------ the operator of a hierarchy (mg_internal.h: SolveOperator)
+void mg::SolveOperator::sweep(hipStream_t st, int l, const double *in, const double *F, double *out) const
 {
-    const mg_solve_opts &o = *lv.o;
-    const std::vector<int> &sizes = *lv.sizes;
-    const int nl = (int)sizes.size();
+    const int N = (*sizes)[l];
+    const LevelConsts &c = (*lc)[l];
+    if (kind) k::wjacobi_bc(st, N, c.dx2, c.sd, o->omega, kind, a(l), in, F, out);
+    else if (coef) k::wjacobi_vc(st, N, c.dx2, c.sd, o->omega, a(l), in, F, out);
+    else k::wjacobi(st, N, c.dx2, c.c, in, F, out, c.sh);
+}
+
+void mg::SolveOperator::residual(hipStream_t st, int l, const double *U, const double *F, double *D) const
+{
+    const int N = (*sizes)[l];
+    const LevelConsts &c = (*lc)[l];
+    if (kind) k::residual_bc(st, N, c.inv, c.sd, kind, a(l), U, F, D, -1);
+    else if (coef) k::residual_vc(st, N, c.inv, c.sd, a(l), U, F, D, -1);
+    else k::residual(st, N, c.inv, U, F, D, -1, c.sh);
+}
+
+void mg::SolveOperator::restrict_residual(hipStream_t st, int l, const double *D, double *Fc) const
+{
+    const int N = (*sizes)[l], M = (*sizes)[l + 1];
+    if (kind) k::restrict_bc(st, N, kind, D, M, Fc, restrict_table(N, M));
+    else k::restrict_gather(st, N, D, M, Fc, restrict_table(N, M), +1);
+}
+
+void mg::SolveOperator::coarse_solve(hipStream_t st, double *U, const double *F, int *gs_state, double *gs_err) const
+{
+    const int last = (int)sizes->size() - 1, N = (*sizes)[last];
+    const LevelConsts &c = (*lc)[last];
+    if (kind)
+        k::gauss_seidel_relative_bc(st, N, c.dx2, c.inv, c.sd, kind, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
+                                    gs_state, gs_err);
+    else if (coef)
+        k::gauss_seidel_relative_vc(st, N, c.dx2, c.inv, c.sd, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
+                                    gs_state, gs_err);
+    else k::gauss_seidel_relative(st, N, c.dx2, c.inv, U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters, gs_state, gs_err, c.sh);
+}
+
+void mg::SolveOperator::prolong_add(hipStream_t st, int l, const double *Uc, const double *Uin, double *Uout) const
+{
+    const int N = (*sizes)[l], M = (*sizes)[l + 1];
+    if (kind) k::prolong_add_bc(st, M, kind, Uc, N, Uin, Uout, (*p_lo)[l], (*p_w)[l]);
+    else k::prolong(st, M, Uc, N, Uin, Uout, prolong_table(M, N));
+}
+
+void mg::SolveOperator::norm(hipStream_t st, const double *U, const double *F, double *part, double *out) const
+{
+    const int N = (*sizes)[0];
+    const LevelConsts &c = (*lc)[0];
+    if (kind) k::resnorm_bc(st, N, c.inv, c.sd, kind, a(0), U, F, part, out);   // both norms run over the unknowns
+    else if (coef && U) k::resnorm_vc(st, N, c.inv, c.sd, a(0), U, F, part, out);
+    else k::resnorm(st, N, c.inv, U, F, part, out, c.sh);   // (the reference norm ||F|| has no operator in it)
+}
+
+void mg::SolveOperator::apply(hipStream_t st, const double *U, double *out) const
+{
+    k::apply_vc(st, (*sizes)[0], (*lc)[0].inv, (*lc)[0].sd, a(0), U, out);
+}
+
+// one V(pre, post) cycle from the caller's U (level `top` keeps its guess; coarser levels start from zero), operator by
+// operator: one launch per sweep (with a coefficient or a boundary kind, under MG_SMOOTHER=simple, and the yardstick of the
+// fused cycle below); the launches it enqueued
+int mg::solve_vcycle(hipStream_t st, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0, int top)
+{
+    const mg_solve_opts &o = *op.o;
+    const std::vector<double *> &A = *lv.A, &B = *lv.B, &Fl = *lv.F;
+    const int nl = (int)op.sizes->size(), last = nl - 1;
     int launches = 0;
-    const std::vector<LevelConsts> &lc = *lv.lc;
     std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
-    for (int l = top; l + 1 < nl; ++l) {
-        const int N = sizes[l], M = sizes[l + 1];
-        const double dx2 = lc[l].dx2, cw = lc[l].c;
-        const k::Shifted &sh = lc[l].sh;
-        const double *F = l == top ? F0 : lv.F[l];
-        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
+    for (int l = top; l < last; ++l) {
+        const double *F = l == top ? F0 : Fl[l];
+        double *cur = l == top ? U0 : A[l], *other = B[l];
         int sweeps = o.pre;
         if (l > top) {   // memset(U, 0) (:256) folded into the first sweep
-            k::wjacobi(st, N, dx2, cw, nullptr, F, cur, sh);
+            op.sweep(st, l, nullptr, F, cur);
             ++launches;
             --sweeps;
         }
         for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi(st, N, dx2, cw, cur, F, other, sh);
+            op.sweep(st, l, cur, F, other);
             ++launches;
             std::swap(cur, other);
         }
         // D = -getResidual(U) (:268, :277-280) into the free field, F_c = doRestriction(D) (:287)
-        k::residual(st, N, lc[l].inv, cur, F, other, -1, sh);
-        k::restrict_gather(st, N, other, M, lv.F[l + 1], restrict_table(N, M), +1);
+        op.residual(st, l, cur, F, other);
+        op.restrict_residual(st, l, other, Fl[l + 1]);
         launches += 2;
         x[l] = cur;
         y[l] = other;
     }
-    const int Nc = sizes[nl - 1];
-    k::gauss_seidel_relative(st, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, lv.A[nl - 1], lv.F[nl - 1], o.coarse_atol, o.coarse_rtol,
-                             o.coarse_max_iters, lv.gs_state, lv.gs_err, lc[nl - 1].sh);
+    op.coarse_solve(st, A[last], Fl[last], lv.gs_state, lv.gs_err);
     ++launches;
-    x[nl - 1] = lv.A[nl - 1];
-    for (int l = nl - 2; l >= top; --l) {
-        const int N = sizes[l], Nc_l = sizes[l + 1];
-        const double dx2 = lc[l].dx2, cw = lc[l].c;
-        const k::Shifted &sh = lc[l].sh;
-        const double *F = l == top ? F0 : lv.F[l];
+    x[last] = A[last];
+    for (int l = last - 1; l >= top; --l) {
+        const double *F = l == top ? F0 : Fl[l];
         double *cur = x[l], *other = y[l];
         // U = U + doProlongation(U_c) (:354, :368) into the free field
-        k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
+        op.prolong_add(st, l, x[l + 1], cur, other);
         ++launches;
         std::swap(cur, other);
         for (int i = 0; i < o.post; ++i) {
-            k::wjacobi(st, N, dx2, cw, cur, F, other, sh);
+            op.sweep(st, l, cur, F, other);
             ++launches;
             std::swap(cur, other);
         }
         x[l] = cur;
     }
-    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    const size_t n_top = (size_t)(*op.sizes)[top] * (*op.sizes)[top];
+    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], n_top * sizeof(double), hipMemcpyDeviceToDevice, st));
     return launches;
 }
 
-// the cycle above with the variable-coefficient kernels (include/mg_varcoef.h): the same node order, the same field
-// ping-pong and the same launches, each constant kernel replaced by its `_vc` form on the level's coefficient coef[l]
-int mg::solve_vcycle_vc(hipStream_t st, const SolveLevels &lv, const std::vector<double *> &coef, const double *F0, double *U0, int top)
-{
-    const mg_solve_opts &o = *lv.o;
-    const std::vector<int> &sizes = *lv.sizes;
-    const int nl = (int)sizes.size();
-    int launches = 0;
-    const std::vector<LevelConsts> &lc = *lv.lc;
-    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
-    auto sd = [&](int l) { return o.shift * lc[l].dx2; };   // (the product solve_level_consts forms)
-    for (int l = top; l + 1 < nl; ++l) {
-        const int N = sizes[l], M = sizes[l + 1];
-        const double dx2 = lc[l].dx2;
-        const double *F = l == top ? F0 : lv.F[l];
-        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
-        int sweeps = o.pre;
-        if (l > top) {
-            k::wjacobi_vc(st, N, dx2, sd(l), o.omega, coef[l], nullptr, F, cur);
-            ++launches;
-            --sweeps;
-        }
-        for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi_vc(st, N, dx2, sd(l), o.omega, coef[l], cur, F, other);
-            ++launches;
-            std::swap(cur, other);
-        }
-        k::residual_vc(st, N, lc[l].inv, sd(l), coef[l], cur, F, other, -1);
-        k::restrict_gather(st, N, other, M, lv.F[l + 1], restrict_table(N, M), +1);
-        launches += 2;
-        x[l] = cur;
-        y[l] = other;
-    }
-    const int last = nl - 1, Nc = sizes[last];
-    k::gauss_seidel_relative_vc(st, Nc, lc[last].dx2, lc[last].inv, sd(last), coef[last], lv.A[last], lv.F[last], o.coarse_atol,
-                                o.coarse_rtol, o.coarse_max_iters, lv.gs_state, lv.gs_err);
-    ++launches;
-    x[last] = lv.A[last];
-    for (int l = nl - 2; l >= top; --l) {
-        const int N = sizes[l], Nc_l = sizes[l + 1];
-        const double *F = l == top ? F0 : lv.F[l];
-        double *cur = x[l], *other = y[l];
-        k::prolong(st, Nc_l, x[l + 1], N, cur, other, prolong_table(Nc_l, N));
-        ++launches;
-        std::swap(cur, other);
-        for (int i = 0; i < o.post; ++i) {
-            k::wjacobi_vc(st, N, lc[l].dx2, sd(l), o.omega, coef[l], cur, F, other);
-            ++launches;
-            std::swap(cur, other);
-        }
-        x[l] = cur;
-    }
-    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return launches;
-}
-
-// the cycle above with the boundary-kind kernels (include/mg_bc.h): the same node order, ping-pong and launch count, each
-// `_vc` kernel replaced by its `_bc` form (coef == nullptr: a = 1) and the transfers by the ones that cover the rim
-int mg::solve_vcycle_bc(hipStream_t st, const SolveLevels &lv, const int *kind, const std::vector<double *> *coef,
-                        const std::vector<int *> &p_lo, const std::vector<double *> &p_w, const double *F0, double *U0)
-{
-    const mg_solve_opts &o = *lv.o;
-    const std::vector<int> &sizes = *lv.sizes;
-    const int nl = (int)sizes.size(), top = 0;
-    int launches = 0;
-    const std::vector<LevelConsts> &lc = *lv.lc;
-    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
-    auto sd = [&](int l) { return o.shift * lc[l].dx2; };
-    auto a = [&](int l) -> const double * { return coef ? (*coef)[l] : nullptr; };
-    for (int l = top; l + 1 < nl; ++l) {
-        const int N = sizes[l], M = sizes[l + 1];
-        const double dx2 = lc[l].dx2;
-        const double *F = l == top ? F0 : lv.F[l];
-        double *cur = l == top ? U0 : lv.A[l], *other = lv.B[l];
-        int sweeps = o.pre;
-        if (l > top) {
-            k::wjacobi_bc(st, N, dx2, sd(l), o.omega, kind, a(l), nullptr, F, cur);
-            ++launches;
-            --sweeps;
-        }
-        for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi_bc(st, N, dx2, sd(l), o.omega, kind, a(l), cur, F, other);
-            ++launches;
-            std::swap(cur, other);
-        }
-        k::residual_bc(st, N, lc[l].inv, sd(l), kind, a(l), cur, F, other, -1);
-        k::restrict_bc(st, N, kind, other, M, lv.F[l + 1], restrict_table(N, M));
-        launches += 2;
-        x[l] = cur;
-        y[l] = other;
-    }
-    const int last = nl - 1, Nc = sizes[last];
-    k::gauss_seidel_relative_bc(st, Nc, lc[last].dx2, lc[last].inv, sd(last), kind, a(last), lv.A[last], lv.F[last], o.coarse_atol,
-                                o.coarse_rtol, o.coarse_max_iters, lv.gs_state, lv.gs_err);
-    ++launches;
-    x[last] = lv.A[last];
-    for (int l = nl - 2; l >= top; --l) {
-        const int N = sizes[l], Nc_l = sizes[l + 1];
-        const double *F = l == top ? F0 : lv.F[l];
-        double *cur = x[l], *other = y[l];
-        k::prolong_add_bc(st, Nc_l, kind, x[l + 1], N, cur, other, p_lo[l], p_w[l]);
-        ++launches;
-        std::swap(cur, other);
-        for (int i = 0; i < o.post; ++i) {
-            k::wjacobi_bc(st, N, lc[l].dx2, sd(l), o.omega, kind, a(l), cur, F, other);
-            ++launches;
-            std::swap(cur, other);
-        }
-        x[l] = cur;
-    }
-    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)sizes[top] * sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return launches;
-}
-
-const double *mg::solver_coefficient(const mg_solver *s) { return s && s->coef_set ? s->coef[0] : nullptr; }
-const int *mg::solver_boundary(const mg_solver *s) { return s && s->bc_set ? s->bc : nullptr; }
+const double *mg::solver_coefficient(const mg_solver *s) { return s ? s->op.a(0) : nullptr; }
+const int *mg::solver_boundary(const mg_solver *s) { return s ? s->op.kind : nullptr; }
 int mg::solver_size(const mg_solver *s, double *L)
 {
     if (L) *L = s->L;
@@ -398,15 +339,9 @@ void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0, in
 
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
-    if (s->bc_set)   // (whatever mg_set_smoother says; top == 0: fmg and a boundary exclude each other)
-        (void)solve_vcycle_bc(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, s->bc,
-                              s->coef_set ? &s->coef : nullptr, s->bc_lo, s->bc_w, F0, U0);
-    else if (s->coef_set)   // (whatever mg_set_smoother says)
-        (void)solve_vcycle_vc(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, s->coef,
-                              F0, U0, top);
-    else if (ctx().smoother == SMOOTHER_SIMPLE)
-        (void)solve_vcycle_simple(st, SolveLevels{&s->sizes, s->L, &s->o, &s->lc, s->A, s->B, s->F, s->gs_state, s->dev_scal + 2}, F0, U0,
-                                  top);
+    // the fused nodes are the constant operator's: a boundary kind or a coefficient goes operator by operator whatever
+    // mg_set_smoother says (top == 0 with either: the full-multigrid start excludes both)
+    if (s->op.kind || s->op.coef || ctx().smoother == SMOOTHER_SIMPLE) (void)solve_vcycle(st, s->lv, s->op, F0, U0, top);
     else vcycle_fused(s, st, F0, U0, top);
 }
 
@@ -449,12 +384,7 @@ void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 // enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
-    // (the reference norm ||F|| has no operator in it)
-    if (s->bc_set)   // both norms run over the unknowns
-        k::resnorm_bc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->bc, s->coef_set ? s->coef[0] : nullptr, U0, F0, s->part,
-                      s->dev_scal + slot);
-    else if (s->coef_set && U0) k::resnorm_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->part, s->dev_scal + slot);
-    else k::resnorm(st, s->N, s->lc[0].inv, U0, F0, s->part, s->dev_scal + slot, s->lc[0].sh);
+    s->op.norm(st, U0, F0, s->part, s->dev_scal + slot);
 }
 
 bool read_back(mg_solver *s, hipStream_t st)
@@ -471,11 +401,7 @@ constexpr int KR_B = 0, KR_W = MG_KRYLOV_MAX_M, KR_ALPHA = 2 * MG_KRYLOV_MAX_M, 
 constexpr int KR_REC_MAX = MG_KRYLOV_MAX_M + 7;
 
 // r = -(inv*b(U) - F): the launch of the cycle's signed residual at level 0
-void krylov_residual(mg_solver *s, hipStream_t st, const double *F0, const double *U0)
-{
-    if (s->coef_set) k::residual_vc(st, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->coef[0], U0, F0, s->kr_r, -1);
-    else k::residual(st, s->N, s->lc[0].inv, U0, F0, s->kr_r, -1, s->lc[0].sh);
-}
+void krylov_residual(mg_solver *s, hipStream_t st, const double *F0, const double *U0) { s->op.residual(st, 0, U0, F0, s->kr_r); }
 
 // the read-back of an iteration: rho_rec and the breakdown flag, the coarse solve's state and (with_norm: a restart) dev_scal
 bool krylov_read_back(mg_solver *s, hipStream_t st, bool with_norm)
@@ -509,7 +435,7 @@ bool krylov_iterate(mg_solver *s, hipStream_t st, const double *F0, double *U0, 
         }
         if (!MG_HIP(hipMemsetAsync(z, 0, n * sizeof(double), st))) return false;
         vcycle(s, st, s->kr_r, z);
-        k::apply_vc(st, N, s->lc[0].inv, o.shift * s->lc[0].dx2, s->coef_set ? s->coef[0] : nullptr, z, q);
+        s->op.apply(st, z, q);
         if (kk > 0) {
             ProfScope ps("krylov_dots", N, pts * (8.0 + 8.0 * kk));
             k::krylov_dots(st, N, kk, q, v, s->kr_part, s->kr_scal + KR_W, s->kr_scal + KR_B, rec + 1);
@@ -566,8 +492,8 @@ std::vector<LevelConsts> mg::solve_level_consts(const std::vector<int> &sizes, d
         LevelConsts c;
         c.dx2 = spacing_sq(N, L);
         c.inv = 1.0 / c.dx2;
-        const double sd = o.shift * c.dx2;
-        c.d = 4.0 + sd;
+        c.sd = o.shift * c.dx2;
+        c.d = 4.0 + c.sd;
         c.q = 1.0 / c.d;
         c.c = o.omega * c.q;
         c.sh = k::Shifted{o.shift != 0.0, c.d, c.q};
@@ -609,6 +535,7 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
     for (int n = N; n >= o.N_min; n /= 2) s->sizes.push_back(n);   // mg_cycle_load's halving sizes (con_N = 1)
     const int nl = (int)s->sizes.size();
     s->lc = solve_level_consts(s->sizes, L, o);
+    s->op = SolveOperator{&s->o, &s->sizes, &s->lc, nullptr, nullptr, &s->bc_lo, &s->bc_w};
     if (!k::gs_relative_fits(s->sizes[nl - 1])) {   // (N_min <= 32 keeps the coarsest level below 64)
         fail(MG_ERR_UNSUPPORTED, "mg_solver_create: coarsest level %d does not fit the coarse solver", s->sizes[nl - 1]);
         release(s);
@@ -662,6 +589,7 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
         release(s);
         return nullptr;
     }
+    s->lv = SolveLevels{&s->A, &s->B, &s->F, s->gs_state, s->dev_scal + 2};
     s->history.reserve((size_t)o.max_cycles + 1);
     return s;
 }
@@ -754,7 +682,7 @@ int mg_solver_set_coefficient(mg_solver *s, const double *a_dev)
         return MG_ERR_ARG;
     }
     if (!a_dev) {   // back to the constant-coefficient solver (the level storage stays for the next coefficient)
-        s->coef_set = false;
+        s->op.coef = nullptr;
         return MG_OK;
     }
     if (s->o.fmg != 0) {
@@ -793,16 +721,16 @@ int mg_solver_set_coefficient(mg_solver *s, const double *a_dev)
     }
     // from here on the level storage is overwritten: until it is whole again the solver has NO coefficient, so a HIP error
     // below leaves the constant-coefficient solver, never one on a half-replaced coefficient
-    s->coef_set = false;
+    s->op.coef = nullptr;
     if (!MG_HIP(hipMemcpyAsync(s->coef[0], a_dev, n0 * sizeof(double), hipMemcpyDeviceToDevice, st))) return MG_ERR_HIP;
     for (int l = 0; l + 1 < nl; ++l)
         k::coef_coarsen(st, s->sizes[l], s->coef[l], s->sizes[l + 1], s->coef[l + 1], restrict_table(s->sizes[l], s->sizes[l + 1]));
     if (!MG_HIP(hipStreamSynchronize(st))) return MG_ERR_HIP;   // (the caller may free a, or solve on another stream)
-    s->coef_set = true;
+    s->op.coef = &s->coef;
     return MG_OK;
 }
 
-int mg_solver_has_coefficient(const mg_solver *s) { return s && s->coef_set ? 1 : 0; }
+int mg_solver_has_coefficient(const mg_solver *s) { return s && s->op.coef ? 1 : 0; }
 
 namespace {
 bool vc_args_ok(const char *who, int N, double L, double shift, std::initializer_list<const void *> arrays)
@@ -929,7 +857,7 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
     if (!kinds_ok("mg_solver_set_boundary", kind)) return MG_ERR_ARG;
     const int neumann = kind[0] + kind[1] + kind[2] + kind[3];
     if (neumann == 0) {   // back to the Dirichlet solver (the tables stay for the next boundary)
-        s->bc_set = false;
+        s->op.kind = nullptr;
         for (int i = 0; i < 4; ++i) s->bc[i] = 0;
         return MG_OK;
     }
@@ -963,7 +891,7 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
         s->bc_w = w;
     }
     for (int i = 0; i < 4; ++i) s->bc[i] = kind[i];
-    s->bc_set = true;
+    s->op.kind = s->bc;
     return MG_OK;
 }
 
@@ -971,7 +899,7 @@ int mg_solver_boundary(const mg_solver *s, int *kind_out)
 {
     if (kind_out)
         for (int i = 0; i < 4; ++i) kind_out[i] = s ? s->bc[i] : 0;
-    return s && s->bc_set ? 1 : 0;
+    return s && s->op.kind ? 1 : 0;
 }
 
 void mg_neumannSource(int N, double L, const int *kind, const double *a_dev, const double *F, const double *g, double *F_out)
@@ -1076,7 +1004,7 @@ int mg_solver_set_krylov(mg_solver *s, int m)
                                  "combined with the Krylov acceleration", s->o.fmg);
         return MG_ERR_UNSUPPORTED;
     }
-    if (m > 0 && s->bc_set) {
+    if (m > 0 && s->op.kind) {
         fail(MG_ERR_UNSUPPORTED, "mg_solver_set_krylov: a boundary with a Neumann side is set; the Krylov acceleration is not built "
                                  "for boundary kinds (its sums and its operator run over the interior)");
         return MG_ERR_UNSUPPORTED;

@@ -6,8 +6,8 @@
 // After each read-back the host drops the instances that met their tolerance from the active set and rebuilds and
 // uploads the tables when the set changed (the read-back already synchronises once per cycle, so one pinned staging
 // buffer serves every upload).
-// With a coefficient set (include/mg_varcoef_batch.h) the cycle is solve_vcycle_vc's instead (mg_solve.cpp), launch by launch
-// over the active set through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip): vcycle_vc_batch below.
+// With a coefficient set (include/mg_varcoef_batch.h) the cycle is solve_vcycle's on that operator instead (mg_solve.cpp),
+// launch by launch over the active set through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip): vcycle_vc_batch below.
 // With mg_batch_solver_set_krylov(m > 0) (include/mg_krylov_batch.h) the loop is restarted GCR(m) per instance around either
 // cycle: krylov_iterate_batch below, launch by launch over the active set (mg_krylov_batch_kernels.hip).
 #include <cmath>
@@ -156,7 +156,7 @@ void fill_tables(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
 // and coarser levels spend their first sweep on the zero start into P
 bool down_ends_in_p(const mg_batch_solver *s, int l) { return (l == 0 ? s->o.pre : s->o.pre - 1) % 2 == 0; }
 
-// the same for solve_vcycle_vc's dataflow (mg_solve.cpp): cur / other of every launch of one cycle, the coefficient of
+// the same for solve_vcycle's dataflow (mg_solve.cpp): cur / other of every launch of one cycle, the coefficient of
 // instance i (the one copy in shared mode) in the slot `coarse`
 void fill_tables_vc(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
 {
@@ -262,7 +262,7 @@ int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
     return launches;
 }
 
-// one V(pre, post) cycle with the coefficient: solve_vcycle_vc's node order and field ping-pong (mg_solve.cpp), each of its
+// one V(pre, post) cycle with the coefficient: solve_vcycle's node order and field ping-pong (mg_solve.cpp), each of its
 // launches ONE launch over the n active instances whose tables are uploaded; returns the launches it enqueued
 int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
 {
@@ -270,7 +270,6 @@ int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
     const int nl = (int)s->sizes.size(), mb = s->max_batch;
     const std::vector<LevelConsts> &lc = s->lc;
     auto tab = [&](int t) { return s->dev_tab + (size_t)t * mb; };
-    auto sd = [&](int l) { return o.shift * lc[l].dx2; };   // (the product solve_level_consts forms)
     std::vector<char> in_p(nl, 1);   // per level: the current iterate is in P (else in Q)
     int launches = 0;
     for (int l = 0; l + 1 < nl; ++l) {
@@ -278,22 +277,22 @@ int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
         bool p = true;
         int sweeps = o.pre;
         if (l > 0) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, true, tab(t + 2));
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, true, tab(t + 2));
             ++launches;
             --sweeps;
         }
         for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, false, tab(p ? t : t + 1));
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, false, tab(p ? t : t + 1));
             ++launches;
             p = !p;
         }
-        k::residual_vc_batch(st, n, N, lc[l].inv, sd(l), tab(t + 3), -1);
+        k::residual_vc_batch(st, n, N, lc[l].inv, lc[l].sd, tab(t + 3), -1);
         k::restrict_batch(st, n, N, M, tab(t + 4), restrict_table(N, M), +1);
         launches += 2;
         in_p[l] = p;
     }
     const int last = nl - 1;
-    k::gauss_seidel_relative_vc_batch(st, n, s->sizes[last], lc[last].dx2, lc[last].inv, sd(last), tab(v_gs(nl)), o.coarse_atol,
+    k::gauss_seidel_relative_vc_batch(st, n, s->sizes[last], lc[last].dx2, lc[last].inv, lc[last].sd, tab(v_gs(nl)), o.coarse_atol,
                                       o.coarse_rtol, o.coarse_max_iters, rb_state(s->dev_rb, mb));
     ++launches;
     for (int l = nl - 2; l >= 0; --l) {
@@ -302,7 +301,7 @@ int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
         ++launches;
         bool p = !in_p[l];
         for (int i = 0; i < o.post; ++i) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, sd(l), o.omega, false, tab(p ? t : t + 1));
+            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, false, tab(p ? t : t + 1));
             ++launches;
             p = !p;
         }
@@ -321,15 +320,16 @@ int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int
 {
     const int nl = (int)s->sizes.size();
     int launches = 0;
+    const SolveOperator op{&s->o, &s->sizes, &s->lc};   // (neither kinds nor a coefficient: the constant kernels)
+    std::vector<double *> A(nl), B(nl), F(nl);          // the instance's level arrays
     for (size_t j = 0; j < act.size(); ++j) {
         const int i = act[j];
-        SolveLevels lv{&s->sizes, s->L, &s->o, &s->lc, {}, {}, {}, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr};
         for (int l = 0; l < nl; ++l) {
-            lv.A.push_back(level(s, s->A, l, i));
-            lv.B.push_back(level(s, s->B, l, i));
-            lv.F.push_back(level(s, s->F, l, i));
+            A[l] = level(s, s->A, l, i);
+            B[l] = level(s, s->B, l, i);
+            F[l] = level(s, s->F, l, i);
         }
-        launches += solve_vcycle_simple(st, lv, F0[i], U0[i]);
+        launches += solve_vcycle(st, SolveLevels{&A, &B, &F, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr}, op, F0[i], U0[i]);
     }
     return launches;
 }
@@ -343,7 +343,7 @@ int norms(mg_batch_solver *s, hipStream_t st, int n, bool has_u, double *out)
 // the residual norm with the coefficient (the reference norm ||F|| has no operator in it: norms(..., false, ...))
 int norms_vc(mg_batch_solver *s, hipStream_t st, int n, double *out)
 {
-    k::resnorm_vc_batch(st, n, s->N, s->lc[0].inv, s->o.shift * s->lc[0].dx2, s->dev_tab, s->part, out);
+    k::resnorm_vc_batch(st, n, s->N, s->lc[0].inv, s->lc[0].sd, s->dev_tab, s->part, out);
     return 2;
 }
 
@@ -409,7 +409,7 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
     const mg_solve_opts &o = s->o;
     const int N = s->N, m = s->kr_m, rec_len = m + 7, mb = s->max_batch;
     const size_t p0 = s->pitch[0], n_part = (size_t)k::KRYLOV_MAX_K * k::krylov_blocks(N), log_stride = krylov_log_stride(s);
-    const double pts = (double)N * N, sd = o.shift * s->lc[0].dx2;
+    const double pts = (double)N * N, sd = s->lc[0].sd;
     const bool vc = s->n_coef > 0, simple = ctx().smoother == SMOOTHER_SIMPLE;
     const KrylovTables host = krylov_tables(s->kr_host_tab, mb), dev = krylov_tables(s->kr_dev_tab, mb);
     s->kr_log_m = m;

@@ -1,5 +1,5 @@
 // mg_varcoef_kernels.hip -- fp64 kernels of the residual-tolerance solver with a variable coefficient (include/mg_varcoef.h;
-// driven by mg_solve.cpp: solve_vcycle_vc): the weighted Jacobi sweep, the residual, the operator on its own, the residual
+// driven by mg_solve.cpp: SolveOperator's members): the weighted Jacobi sweep, the residual, the operator on its own, the residual
 // L2 norm, the red-black Gauss-Seidel coarse solve, the coarsening of the nodal coefficient and its check.
 // Built with -ffp-contract=off like every kernel file: the header fixes the evaluation order (every product and every sum
 // rounded once) so that numpy restates it bit for bit, and so that a == 1 gives the bits of the constant-coefficient kernels
