@@ -228,7 +228,14 @@ typedef struct mg_cycle_result {
     double *U_dev;         /* final solution (device, owned by the plan) */
     double  mg_error;      /* :434-445 */
     double  time_ms;       /* host wall clock of the reference's window :156..:429, synchronised */
-    double  device_ms;     /* hipEvent time of the same window */
+    double  device_ms;     /* hipEvent time of the last window.  A window enqueued on an idle stream: from its own start
+                            * event to its end event, as mg_cycle_execute's.  A window enqueued while the previous window
+                            * of this plan was still running or waiting (back to back): from the END of that window to the
+                            * end of this one -- the boundary between the two is included, and so is anything else the
+                            * caller put on the stream in between.  The decision is taken once, with hipEventQuery when the
+                            * window is enqueued: should the previous window finish after that query but before this
+                            * window's first launch reaches the device (a host slower than the device, small grids), the
+                            * idle time in between is counted too.  0 for a window enqueued inside a stream capture. */
     int     n_records;
     const mg_node_record *records; /* owned by the plan, valid until the next execute */
     const char *report;    /* the reference's printed report (owned by the plan) */
@@ -252,7 +259,10 @@ mg_cycle_plan *mg_cycle_load(const char *path, int flags);
 /* one run of the reference's timed window from the state right after getSource */
 int            mg_cycle_execute(mg_cycle_plan *plan, mg_cycle_result *out);
 /* the same window without host synchronisation: enqueue any number back to back, then collect
- * (waits, reports the last one).  mg_cycle_execute == sync + enqueue + sync + collect. */
+ * (waits, reports the last one).  mg_cycle_execute == sync + enqueue + sync + collect.
+ * A window leaves its smoothing errors as partial sums in the plan's own memory; mg_cycle_collect reduces those of the
+ * last window (one launch per collect, none per window: the errors of earlier windows are never reported).  Trigger mode
+ * (con_step = -1) reduces at the end of its window.  A back-to-back window records one timing event, not two: device_ms. */
 int            mg_cycle_enqueue(mg_cycle_plan *plan);
 int            mg_cycle_collect(mg_cycle_plan *plan, mg_cycle_result *out);
 /* MG_CYCLE_MIXED plans: `cycles` fp32 runs of the file per window, joined by the fp64 residual of

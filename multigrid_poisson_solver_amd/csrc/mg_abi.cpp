@@ -147,7 +147,7 @@ double *partials(size_t n)
 }
 
 // ------------------------------------------------------------------ live timing
-static bool stream_is_capturing(hipStream_t s)
+bool stream_is_capturing(hipStream_t s)
 {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) {
@@ -189,6 +189,7 @@ double *norm_partials(size_t n)
 {
     Context &c = ctx();
     if (!c.defer_norms) return partials(n);
+    if (c.norm_sink) return c.norm_sink->take(n);
     c.norm_window_total += n;
     if (c.norm_arena_used + n > c.norm_arena_cap) {
         // grow; what is pending keeps pointing into the old arena, which stays alive
@@ -212,27 +213,86 @@ void norm_finish(hipStream_t s, const double *part, size_t n, int N, double *out
         k::finish_smoothing_error(s, part, n, N, out);
         return;
     }
+    if (c.norm_sink) {
+        NormSink &ns = *c.norm_sink;
+        ns.pending.push_back(Context::PendingNorm{part, (int)n, N, out});
+        if ((int)ns.pending.size() >= k::MAX_NORMS_PER_FLUSH && !c.norms_at_window_end) ns.flush(c.stream);   // (as flush_norms: the engine's stream)
+        return;
+    }
     c.pending_norms.push_back(Context::PendingNorm{part, (int)n, N, out});
     if ((int)c.pending_norms.size() >= k::MAX_NORMS_PER_FLUSH && !c.norms_at_window_end) flush_norms();
+}
+
+// one reduction launch per MAX_NORMS_PER_FLUSH pending norms, in the order they were registered
+static void reduce_pending(hipStream_t s, const std::vector<Context::PendingNorm> &pending)
+{
+    k::NormBatch b;
+    int count = 0;
+    for (const auto &pn : pending) {
+        b.part[count] = pn.part;
+        b.out[count] = pn.out;
+        b.n[count] = pn.n;
+        b.N[count] = pn.N;
+        if (++count == k::MAX_NORMS_PER_FLUSH) {   // (only a window that held its norms back to the end has more than one batch)
+            k::finish_smoothing_errors(s, b, count);
+            count = 0;
+        }
+    }
+    if (count) k::finish_smoothing_errors(s, b, count);
+}
+
+void NormSink::begin_window()
+{
+    block = used = 0;
+    pending.clear();
+    unfinished = true;
+}
+
+double *NormSink::take(size_t n)
+{
+    for (; block < blocks.size(); ++block, used = 0) {
+        if (used + n > blocks[block].cap) continue;
+        double *p = blocks[block].p + used;
+        used += n;
+        return p;
+    }
+    // the first window that gets this far (later ones find the block): not under stream capture, where nothing may be allocated
+    const size_t cap = n > ((size_t)1 << 16) ? n : (size_t)1 << 16;
+    double *p = (double *)pool->get(cap * sizeof(double));
+    if (!p) return nullptr;
+    blocks.push_back(Block{p, cap});
+    block = blocks.size() - 1;
+    used = n;
+    return p;
+}
+
+void NormSink::flush(hipStream_t s)
+{
+    reduce_pending(s, pending);
+    pending.clear();
+}
+
+void NormSink::finish(hipStream_t s)
+{
+    if (!unfinished) return;
+    reduce_pending(s, pending);
+    unfinished = false;
+}
+
+void NormSink::release()
+{
+    for (const Block &b : blocks) pool->put(b.p);
+    blocks.clear();
+    pending.clear();
+    block = used = 0;
+    unfinished = false;
 }
 
 void flush_norms()
 {
     Context &c = ctx();
     if (c.pending_norms.empty()) return;
-    k::NormBatch b;
-    int count = 0;
-    for (const auto &pn : c.pending_norms) {
-        b.part[count] = pn.part;
-        b.out[count] = pn.out;
-        b.n[count] = pn.n;
-        b.N[count] = pn.N;
-        if (++count == k::MAX_NORMS_PER_FLUSH) {   // (only a window that held its norms back to the end has more than one batch)
-            k::finish_smoothing_errors(c.stream, b, count);
-            count = 0;
-        }
-    }
-    if (count) k::finish_smoothing_errors(c.stream, b, count);
+    reduce_pending(c.stream, c.pending_norms);
     c.pending_norms.clear();
     c.norm_arena_used = 0;  // stream order: later partials are written after this reduction ran
     // An arena that grew in mid-window holds only what came after its last growth: size it for ALL partials between two

@@ -161,7 +161,19 @@ struct mg_cycle_plan {
     hipGraphExec_t graph_exec = nullptr;
     bool graph_ready = false, graph_failed = false;
     int warm_runs = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Timing marks.  A window enqueued behind an unfinished window of this plan records no start event: the end event of
+    // that window is its start mark, so a window boundary costs ONE event record (a barrier packet with a completion
+    // signal of its own) instead of two.  Hence two end events, used in turn.  A window that finds the stream idle
+    // records ev_start as before (nothing waits behind it there).
+    hipEvent_t ev_start = nullptr, ev_end[2] = {nullptr, nullptr};
+    int end_at = 0;                  // ev_end[end_at] is the end mark of the last window ...
+    bool have_end = false;           // ... once one has been recorded ...
+    hipStream_t end_stream = nullptr;  // ... on this stream
+    hipEvent_t mark0 = nullptr, mark1 = nullptr;  // the pair the last window's device_ms is taken from (nullptr: none, it was captured by the caller)
+    NormSink norms;                  // the smoothing-error reductions of the last window: partials in the plan's pool, finished at collect
+    // the pending list of the window the graph was captured from: a replay re-runs that window's launches without the host
+    // code that builds the list, and a window run eagerly in between (smoother switched away) leaves ITS list in `norms`
+    std::vector<Context::PendingNorm> graph_norms;
     int last_status = 0;
     bool last_replayed = false;      // the last window was a hipGraph replay
     // ---- batched breadth-first schedule ------------------------------------------------------------------------------
@@ -581,6 +593,8 @@ bool try_tail(Exec &x)
     return true;
 }
 
+bool uses_trigger(const mg_cycle_plan *p);
+
 // one pass over the node program == the reference's while loop :158-426
 void run_nodes(Exec &x)
 {
@@ -589,6 +603,11 @@ void run_nodes(Exec &x)
     const bool fused = (p->flags & MG_CYCLE_FUSED) != 0;
     const bool mixed = (p->flags & MG_CYCLE_MIXED) != 0;
     x.c.defer_norms = true;
+    // the launches leave their partial sums with the plan; nothing reduces them inside the window (a trace launches nothing)
+    if (!x.tracing) {
+        p->norms.begin_window();
+        x.c.norm_sink = &p->norms;
+    }
     // what a node must be for the dataflow trace: ONE fused launch (smooth_pp records it) -- checked here wherever the
     // entry point below would otherwise fall back to operator-by-operator launches
     auto fusable_down = [&](int N, int M, int step) {
@@ -836,7 +855,10 @@ void run_nodes(Exec &x)
         else if (mixed) x.status = 15;
         else ensure_U(p, cycle.last());
     }
-    flush_norms();  // the window's smoothing errors: one reduction launch
+    // The window's smoothing errors stay as partial sums: mg_cycle_collect reduces those of the last window, the only ones
+    // that are reported.  Trigger mode reads an error per sweep on the host anyway and finishes its window at once.
+    x.c.norm_sink = nullptr;
+    if (!x.tracing && uses_trigger(p)) p->norms.finish(x.c.stream);
     x.c.defer_norms = false;
 }
 
@@ -1033,9 +1055,10 @@ void replay_schedule(mg_cycle_plan *p)
 {
     Context &c = ctx();
     c.defer_norms = true;
-    // the norms of the window are reduced at its end: a reduction in mid-window recycles the arena of partial sums, and a
-    // batch registers its instances one by one (the arena is sized for a whole window when the previous one ends)
+    // no reduction in mid-window, however many norms a batch registers: all of them wait for mg_cycle_collect
     c.norms_at_window_end = true;
+    p->norms.begin_window();
+    c.norm_sink = &p->norms;
     for (const auto &g : p->sched) {
         const NodeOp &o = p->ops[(size_t)g.first];
         const int n = (int)g.members.size();
@@ -1052,7 +1075,7 @@ void replay_schedule(mg_cycle_plan *p)
             replay_node(o, &b);
         }
     }
-    flush_norms();
+    c.norm_sink = nullptr;
     c.defer_norms = false;
     c.norms_at_window_end = false;
     // mg_lastExactSolverIterations(): the state of the LAST coarse-tail slice of the file (each instance has its own slot)
@@ -1083,6 +1106,7 @@ mg_cycle_plan *mg_cycle_load(const char *path, int flags)
     }
     mg_cycle_plan *p = new mg_cycle_plan;
     p->pool.poison(pool_poison_wanted());   // MG_POOL_POISON: every array the plan's pool hands out starts as NaN
+    p->norms.pool = &p->pool;
     p->flags = flags;
     p->path = path;
     if (!(f >> p->L >> p->min_x >> p->min_y >> p->con_step >> p->con_N >> p->N_max >> p->N_min)) {
@@ -1144,8 +1168,11 @@ mg_cycle_plan *mg_cycle_load(const char *path, int flags)
         mg_getSource(top->N, p->L, top->F, p->min_x, p->min_y);  // :153
     }
     p->F_finest = top->F;
-    (void)hipEventCreate(&p->ev0);
-    (void)hipEventCreate(&p->ev1);
+    // timing marks only: nothing is read on the strength of these events (mg_cycle_collect synchronises the stream before
+    // it looks at a result), so their records need no system-scope fence between two windows
+    // (MG_WINDOW_EVENT_FENCE=1: ordinary events, for an A/B in one process environment: profiles/window_boundary.md)
+    static const bool fenced = [] { const char *e = getenv("MG_WINDOW_EVENT_FENCE"); return e && atoi(e) != 0; }();
+    for (hipEvent_t *e : {&p->ev_start, &p->ev_end[0], &p->ev_end[1]}) (void)hipEventCreateWithFlags(e, fenced ? hipEventDefault : hipEventDisableSystemFence);
     mg_sync();
     return p;
 }
@@ -1164,7 +1191,21 @@ int mg_cycle_enqueue(mg_cycle_plan *p)
     const bool want_graph = (p->flags & MG_CYCLE_GRAPH) && (p->flags & MG_CYCLE_FUSED) && !(p->flags & MG_CYCLE_MIXED) &&
                             !uses_trigger(p) && !p->graph_failed && (!p->sched_ready || (int)c.smoother == p->sched_smoother);
     c.profile_window++;
-    (void)hipEventRecord(p->ev0, s);
+    // start mark: the end event of the previous window when that window is still running or waiting (back to back),
+    // else a record of its own.  No event inside a caller's capture.
+    const bool timed = !stream_is_capturing(s);
+    p->mark0 = p->mark1 = nullptr;
+    if (timed) {
+        hipEvent_t prev = (p->have_end && p->end_stream == s) ? p->ev_end[p->end_at] : nullptr;
+        const hipError_t q = prev ? hipEventQuery(prev) : hipSuccess;
+        if (q != hipSuccess) (void)hipGetLastError();
+        if (prev && q == hipErrorNotReady) {
+            p->mark0 = prev;
+        } else {
+            (void)hipEventRecord(p->ev_start, s);
+            p->mark0 = p->ev_start;
+        }
+    }
 
     p->last_replayed = false;
     if (want_graph && p->graph_ready) {
@@ -1172,6 +1213,8 @@ int mg_cycle_enqueue(mg_cycle_plan *p)
         // only the error values are refreshed at collect time.
         if (!MG_HIP(hipGraphLaunch(p->graph_exec, s))) status = 9;
         p->last_replayed = status == 0;
+        p->norms.pending = p->graph_norms;   // what the replayed launches leave: the captured window's partials and slots
+        p->norms.unfinished = true;
     } else {
         const bool mixed = (p->flags & MG_CYCLE_MIXED) != 0;
         const int outer = mixed ? p->refinements : 1;
@@ -1200,6 +1243,7 @@ int mg_cycle_enqueue(mg_cycle_plan *p)
                 if (e == hipSuccess && status == 0 && hipGraphInstantiate(&p->graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
                     p->graph = g;
                     p->graph_ready = true;
+                    p->graph_norms = p->norms.pending;
                     if (!MG_HIP(hipGraphLaunch(p->graph_exec, s))) status = 9;
                     p->last_replayed = status == 0;
                 } else {
@@ -1244,6 +1288,7 @@ int mg_cycle_enqueue(mg_cycle_plan *p)
                 if (dbg) fprintf(stderr, "[cycle] instantiated\n");
                 p->graph = g;
                 p->graph_ready = true;
+                p->graph_norms = p->norms.pending;
                 if (!MG_HIP(hipGraphLaunch(p->graph_exec, s))) status = 9;
                 p->last_replayed = status == 0;
                 if (dbg) fprintf(stderr, "[cycle] launched: status %d\n", status);
@@ -1276,7 +1321,13 @@ int mg_cycle_enqueue(mg_cycle_plan *p)
         }
         }
     }
-    (void)hipEventRecord(p->ev1, s);
+    if (timed) {
+        p->end_at ^= 1;
+        (void)hipEventRecord(p->ev_end[p->end_at], s);
+        p->mark1 = p->ev_end[p->end_at];
+        p->have_end = true;
+        p->end_stream = s;
+    }
     p->last_status = status;
     return status;
 }
@@ -1287,9 +1338,10 @@ int mg_cycle_collect(mg_cycle_plan *p, mg_cycle_result *out)
     if (!require_ready("mg_cycle_collect") || !p) return 1;
     Context &c = ctx();
     memset(out, 0, sizeof *out);
+    p->norms.finish(c.stream);   // the last window's smoothing errors: one reduction launch per collect, none per window
     mg_sync();
     float dev_ms = 0.f;
-    if (hipEventElapsedTime(&dev_ms, p->ev0, p->ev1) != hipSuccess) (void)hipGetLastError();
+    if (p->mark0 && p->mark1 && hipEventElapsedTime(&dev_ms, p->mark0, p->mark1) != hipSuccess) (void)hipGetLastError();
 
     // smoothing errors: one download for the whole window
     if (!p->records.empty()) {
@@ -1389,13 +1441,14 @@ void mg_cycle_destroy(mg_cycle_plan *p)
     if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
     if (p->graph) (void)hipGraphDestroy(p->graph);
-    if (p->ev0) (void)hipEventDestroy(p->ev0);
-    if (p->ev1) (void)hipEventDestroy(p->ev1);
+    for (hipEvent_t e : {p->ev_start, p->ev_end[0], p->ev_end[1]})
+        if (e) (void)hipEventDestroy(e);
     if (p->levels) {
         p->levels->clear();
         delete p->levels;
     }
     drop_schedule(p);   // (the arrays the trace set aside go back to the pool)
+    p->norms.release(); // (reductions still pending are dropped: nobody can read them any more)
     if (p->err_dev) p->pool.put(p->err_dev);
     if (p->refine_err_dev) p->pool.put(p->refine_err_dev);
     if (p->F32_res) p->pool.put(p->F32_res);

@@ -108,6 +108,7 @@ void poison_block(void *p, size_t bytes);
 enum Smoother { SMOOTHER_STREAM = 0, SMOOTHER_SIMPLE = 1, SMOOTHER_STREAM_ONLY = 2 };
 
 struct NodeOp;   // (below: one fused node launch as the cycle driver's dataflow trace records it)
+struct NormSink; // (below: a cycle plan's own store of deferred norm reductions)
 
 struct Context {
     bool ready = false;
@@ -136,6 +137,7 @@ struct Context {
     double *norm_arena = nullptr;
     size_t norm_arena_cap = 0, norm_arena_used = 0;
     size_t norm_window_total = 0;          // partials requested since the last flush (sizes the arena for the next window)
+    NormSink *norm_sink = nullptr;         // != nullptr (while a cycle plan enqueues a window): partials and pending list are the plan's
     double *scalars = nullptr;            // [64] device scalars (errors, norms)
     int *gs_state = nullptr;              // [4]: done flag, iteration count, ...
     double *host_scalars = nullptr;       // pinned [64]
@@ -178,6 +180,27 @@ Pool &scratch_pool();         // where operator-internal scratch comes from
 double *norm_partials(size_t n);
 void norm_finish(hipStream_t s, const double *part, size_t n, int N, double *out);
 void flush_norms();
+bool stream_is_capturing(hipStream_t s);
+
+// A cycle plan's own store of deferred norm reductions (mg_cycle.cpp).  The plan's launches leave their partial sums in
+// blocks from the PLAN'S pool, so nothing another plan, a Solver or an operator call enqueues can overwrite them, and the
+// list of pending reductions stays with the plan: a window enqueues no reduction launch at all, mg_cycle_collect finishes
+// the last window's -- the only ones anybody reads -- with one launch.  The launches of a plan are the same from window
+// to window, so every window walks the blocks the same way and overwrites the partials of the one before it, which
+// nobody has read (stream order: a reduction enqueued at collect runs before the next window's kernels).
+struct NormSink {
+    struct Block { double *p; size_t cap; };
+    Pool *pool = nullptr;
+    std::vector<Block> blocks;
+    size_t block = 0, used = 0;            // where the next partials go
+    std::vector<Context::PendingNorm> pending;
+    bool unfinished = false;               // a window was enqueued since the pending list was last reduced
+    void begin_window();                   // a window's launches follow: back to the first block, an empty list
+    double *take(size_t n);
+    void flush(hipStream_t s);             // reduce what is pending now and forget it (MAX_NORMS_PER_FLUSH reached in mid-window)
+    void finish(hipStream_t s);            // reduce the last window's list if that has not happened yet; the list stays (graph replay)
+    void release();                        // the blocks go back to the pool
+};
 
 const RestrictTable &restrict_table(int N, int M);
 const ProlongTable &prolong_table(int N, int M);
