@@ -500,6 +500,8 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 
 /* the building blocks of the full-multigrid start (mg_solve_opts.fmg): mg_cubic_table, mg_prolongCubic */
 #include "mg_fmg.h"
+/* the recorded V-cycle both solvers walk, as a host-only list of its launches (for tests): mg_solve_cycle_describe */
+#include "mg_solve_cycle.h"
 /* time stepping of the heat equation over the solvers (theta-scheme): mg_heat_rhs, mg_heat_stepper_* */
 #include "mg_heat.h"
 /* the solver with a variable coefficient, div(a grad U) - sigma*U = F: mg_solver_set_coefficient, mg_applyOperator, ... */

@@ -253,6 +253,12 @@ ABI_BC = {
 }
 DIRICHLET, NEUMANN = 0, 1
 
+# the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
+# ABI_FMG: a library without it still loads, solve_cycle() then raises
+ABI_SOLVE_CYCLE = {
+    "mg_solve_cycle_describe": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i]),
+}
+
 _lib = None
 hip_runtime = None   # which libamdhip64 the engine was bound to ("system", or the path of torch's copy)
 
@@ -312,7 +318,7 @@ def load_library(path=None):
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
-            list(ABI_EIGS.items()) + list(ABI_BC.items()):
+            list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SOLVE_CYCLE.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -629,6 +635,21 @@ def prolongation_table(N, M, axis):
     lo = np.empty(M)
     load_library().mg_prolongation_table(N, M, axis, owner.ctypes.data, hi.ctypes.data, lo.ctypes.data)
     return owner, hi, lo
+
+
+def solve_cycle(nl, pre, post, top=0, fused=False, down_fused=None, up_fused=None, with_coef=False):
+    """mg_solve_cycle_describe: the launches of one V(pre, post) cycle as both solvers walk them, one row of
+    MG_SOLVE_CYCLE_RECORD ints per step (include/mg_solve_cycle.h); host only."""
+    if not hasattr(load_library(), "mg_solve_cycle_describe"):
+        raise MGError(f"{LIB_PATH} does not export mg_solve_cycle_describe (a build without the recorded cycle)")
+    bits = [np.ascontiguousarray(b if b is not None else np.zeros(nl - 1), dtype=np.int32) for b in (down_fused, up_fused)]
+    args = (nl, pre, post, top, int(fused), bits[0].ctypes.data, bits[1].ctypes.data, int(with_coef))
+    n = load_library().mg_solve_cycle_describe(*args, None, 0)
+    if n < 0:
+        _check()
+    out = np.empty((n, 16), dtype=np.int32)
+    load_library().mg_solve_cycle_describe(*args, out.ctypes.data, n)
+    return out
 
 
 def cubic_table(N_src, N_dst):

@@ -55,7 +55,8 @@ def _deps():
                          os.path.join(ROOT, "include", "mg_heat_vc.h"), os.path.join(ROOT, "include", "mg_varcoef_batch.h"),
                          os.path.join(ROOT, "include", "mg_krylov.h"), os.path.join(ROOT, "include", "mg_krylov_batch.h"),
                          os.path.join(ROOT, "include", "mg_adjoint.h"), os.path.join(ROOT, "include", "mg_eigs.h"),
-                         os.path.join(ROOT, "include", "mg_bc.h"), os.path.join(CSRC, "mg_bc_impl.h"),
+                         os.path.join(ROOT, "include", "mg_bc.h"), os.path.join(ROOT, "include", "mg_solve_cycle.h"),
+                         os.path.join(CSRC, "mg_bc_impl.h"),
                          os.path.join(CSRC, "mg_varcoef_impl.h"), os.path.join(CSRC, "mg_krylov_impl.h"),
                          os.path.abspath(__file__)]
     return deps + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]

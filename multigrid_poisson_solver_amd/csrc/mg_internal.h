@@ -682,10 +682,44 @@ struct SolveOperator {
     // out = AU at level 0 for the Krylov acceleration, which boundary kinds refuse: apply_vc whatever the family
     void apply(hipStream_t st, const double *U, double *out) const;
 };
-// one V(pre, post) cycle operator by operator, one launch per sweep, with the kernels of op; returns the kernel launches it
-// enqueued.  top: the level the cycle starts at, from the non-zero field U0 on the source F0 (both of size sizes[top]; 0: a
-// solve's cycle; above 0: the full-multigrid start, which only the constant operator has)
-int solve_vcycle(hipStream_t st, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0, int top = 0);
+// One V(pre, post) cycle as data: its launches in order, each naming the level arrays it reads and writes
+// in the five roles of NodeBatchItem.  mg_solver walks it on one instance (run_solve_cycle), mg_batch_solver on its active
+// set, one table of NodeBatchItem per slot (mg_solve_batch.cpp).
+enum class Field : int { None, U0, F0, A, B, F, Coef };   // U0 / F0: the cycle's own arguments, at its top level
+struct FieldRef {
+    Field f = Field::None;
+    int level = 0;
+    bool operator==(const FieldRef &r) const { return f == r.f && level == r.level; }
+};
+struct SolveStep {
+    enum Kind : int { Node, Sweep, Residual, Restrict, Coarse, ProlongAdd, Copy } kind;
+    int level;                     // the level the launch runs on (Restrict / ProlongAdd: the fine one)
+    int steps = 0, d_sign = 0;     // Node: the sweeps in the launch, and its d_sign
+    bool fused_transfer = false;   // Node: carries the restriction (d_sign < 0) or the prolongation-add (d_sign > 0)
+    // Sweep: in (None: from zero) -> out on F; Residual: out = -(A in - F); Restrict: out (level + 1) = R in; Coarse: out
+    // solved on F from zero; ProlongAdd: out = in + P coarse; Copy: out = in.  coarse of Sweep / Residual / Coarse: the
+    // level's coefficient, or None
+    FieldRef in, F, coarse, out, Fc;
+    int slot = 0;                  // from 1 (table 0 is the norm's); steps whose five roles are equal share one
+};
+struct SolveCycle {
+    std::vector<SolveStep> steps;
+    int n_slots = 0;
+};
+// The cycle over nl levels from level `top` (0: a solve's; above 0: the full-multigrid start), whose iterate U0 keeps its
+// guess while coarser levels start from zero, folded into their first sweep.  fused: one Node per level and direction, with
+// the transfer inside where down_fused[l] / up_fused[l] (read only then), beside it elsewhere; else operator by operator,
+// one Sweep per launch.  with_coef: Sweep, Residual and Coarse name Coef[level].  Every field choice of the cycle is made
+// here; touches no table and no device.
+SolveCycle build_solve_cycle(int nl, int pre, int post, int top, bool fused, const int *down_fused, const int *up_fused, bool with_coef);
+// whether the streaming node of level l < last carries its restriction / its prolongation-add (the builder's inputs)
+void solve_fusable_levels(const std::vector<int> &sizes, std::vector<int> *down_fused, std::vector<int> *up_fused);
+// a Node step as the streaming launcher takes it, on the arrays `it` (a batched launch adds .batch)
+k::SmoothNode<double> solve_cycle_node(const SolveStep &s, const std::vector<int> &sizes, const std::vector<LevelConsts> &lc,
+                                       const NodeBatchItem &it);
+// enqueue the cycle on one instance with the kernels of op (a Node: the constant operator's streaming smoother); returns the
+// kernel launches (the final copy is none).  F0, U0: of the size of the cycle's top level
+int run_solve_cycle(hipStream_t st, const SolveCycle &c, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0);
 // the level-0 coefficient of a solver, mg_solver::coef[0] (mg_solve.cpp), nullptr when none is set: the heat stepper's
 // right-hand-side kernel reads the solver's own array instead of keeping a second copy (mg_heat.cpp)
 const double *solver_coefficient(const mg_solver *s);

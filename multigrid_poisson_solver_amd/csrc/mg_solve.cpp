@@ -23,6 +23,7 @@ struct mg_solver {
     // the operator of the levels: set at creation; op.coef (&coef, or nullptr: none is set) and op.kind (bc, or nullptr: no
     // side is Neumann) are the solver's state, changed by mg_solver_set_coefficient and mg_solver_set_boundary alone
     SolveOperator op{};
+    std::vector<SolveCycle> cyc[2];          // [fused][top]: the recorded cycles, top = 0 and (o.fmg >= 1) every level above the last
     double *part = nullptr;                 // norm partials
     double *dev_scal = nullptr;              // [4]: residual norm, reference norm, coarse err0, coarse err
     int *gs_state = nullptr;                 // [4]
@@ -218,56 +219,145 @@ void mg::SolveOperator::apply(hipStream_t st, const double *U, double *out) cons
     k::apply_vc(st, (*sizes)[0], (*lc)[0].inv, (*lc)[0].sd, a(0), U, out);
 }
 
-// one V(pre, post) cycle from the caller's U (level `top` keeps its guess; coarser levels start from zero), operator by
-// operator: one launch per sweep (with a coefficient or a boundary kind, under MG_SMOOTHER=simple, and the yardstick of the
-// fused cycle below); the launches it enqueued
-int mg::solve_vcycle(hipStream_t st, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0, int top)
+// ------------------------------------------------------------------ the recorded cycle (mg_internal.h: SolveCycle)
+SolveCycle mg::build_solve_cycle(int nl, int pre, int post, int top, bool fused, const int *down_fused, const int *up_fused, bool with_coef)
 {
-    const mg_solve_opts &o = *op.o;
-    const std::vector<double *> &A = *lv.A, &B = *lv.B, &Fl = *lv.F;
-    const int nl = (int)op.sizes->size(), last = nl - 1;
-    int launches = 0;
-    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
+    SolveCycle c;
+    const int last = nl - 1;
+    const FieldRef none{}, U0{Field::U0, top}, F0{Field::F0, top};
+    auto A = [](int l) { return FieldRef{Field::A, l}; };
+    auto B = [](int l) { return FieldRef{Field::B, l}; };
+    auto F = [&](int l) { return l == top ? F0 : FieldRef{Field::F, l}; };
+    auto a = [&](int l) { return with_coef && !fused ? FieldRef{Field::Coef, l} : none; };
+    auto emit = [&](SolveStep s) {
+        for (const SolveStep &t : c.steps)
+            if (t.in == s.in && t.F == s.F && t.coarse == s.coarse && t.out == s.out && t.Fc == s.Fc) s.slot = t.slot;
+        if (s.slot == 0) s.slot = ++c.n_slots;
+        c.steps.push_back(s);
+    };
+    auto node = [&](int l, int steps, int d_sign, bool transfer, FieldRef in, FieldRef coarse, FieldRef out, FieldRef Fc) {
+        emit({.kind = SolveStep::Node, .level = l, .steps = steps, .d_sign = d_sign, .fused_transfer = transfer, .in = in, .F = F(l),
+              .coarse = coarse, .out = out, .Fc = Fc});
+    };
+    auto sweep = [&](int l, FieldRef in, FieldRef out) {
+        emit({.kind = SolveStep::Sweep, .level = l, .in = in, .F = F(l), .coarse = a(l), .out = out});
+    };
+    std::vector<FieldRef> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
     for (int l = top; l < last; ++l) {
-        const double *F = l == top ? F0 : Fl[l];
-        double *cur = l == top ? U0 : A[l], *other = B[l];
-        int sweeps = o.pre;
-        if (l > top) {   // memset(U, 0) (:256) folded into the first sweep
-            op.sweep(st, l, nullptr, F, cur);
-            ++launches;
-            --sweeps;
-        }
-        for (int i = 0; i < sweeps; ++i) {
-            op.sweep(st, l, cur, F, other);
-            ++launches;
-            std::swap(cur, other);
+        if (fused) {
+            // level `top`: the node reads U0 and stores into B; U0 is free until the way up writes the result there
+            x[l] = l == top ? B(l) : A(l);
+            y[l] = l == top ? U0 : B(l);
+            node(l, pre, -1, down_fused[l], l == top ? U0 : none, none, x[l], down_fused[l] ? FieldRef{Field::F, l + 1} : none);
+            if (down_fused[l]) continue;
+        } else {
+            FieldRef cur = l == top ? U0 : A(l), other = B(l);
+            int sweeps = pre;
+            if (l > top) {   // memset(U, 0) (:256) folded into the first sweep
+                sweep(l, none, cur);
+                --sweeps;
+            }
+            for (int i = 0; i < sweeps; ++i) {
+                sweep(l, cur, other);
+                std::swap(cur, other);
+            }
+            x[l] = cur;
+            y[l] = other;
         }
         // D = -getResidual(U) (:268, :277-280) into the free field, F_c = doRestriction(D) (:287)
-        op.residual(st, l, cur, F, other);
-        op.restrict_residual(st, l, other, Fl[l + 1]);
-        launches += 2;
-        x[l] = cur;
-        y[l] = other;
+        emit({.kind = SolveStep::Residual, .level = l, .in = x[l], .F = F(l), .coarse = a(l), .out = y[l]});
+        emit({.kind = SolveStep::Restrict, .level = l, .in = y[l], .out = {Field::F, l + 1}});
     }
-    op.coarse_solve(st, A[last], Fl[last], lv.gs_state, lv.gs_err);
-    ++launches;
-    x[last] = A[last];
+    emit({.kind = SolveStep::Coarse, .level = last, .F = {Field::F, last}, .coarse = a(last), .out = A(last)});
+    x[last] = A(last);
     for (int l = last - 1; l >= top; --l) {
-        const double *F = l == top ? F0 : Fl[l];
-        double *cur = x[l], *other = y[l];
+        if (fused && up_fused[l]) {
+            const FieldRef out = l == top ? U0 : B(l);
+            node(l, post, +1, true, x[l], x[l + 1], out, none);
+            x[l] = out;
+            continue;
+        }
         // U = U + doProlongation(U_c) (:354, :368) into the free field
-        op.prolong_add(st, l, x[l + 1], cur, other);
-        ++launches;
+        FieldRef cur = x[l], other = fused ? (l == top ? U0 : B(l)) : y[l];
+        emit({.kind = SolveStep::ProlongAdd, .level = l, .in = cur, .coarse = x[l + 1], .out = other});
         std::swap(cur, other);
-        for (int i = 0; i < o.post; ++i) {
-            op.sweep(st, l, cur, F, other);
-            ++launches;
+        if (fused) {   // the sweeps back into the field the prolongation read
+            node(l, post, +1, false, cur, none, other, none);
             std::swap(cur, other);
+        } else {
+            for (int i = 0; i < post; ++i) {
+                sweep(l, cur, other);
+                std::swap(cur, other);
+            }
         }
         x[l] = cur;
     }
-    const size_t n_top = (size_t)(*op.sizes)[top] * (*op.sizes)[top];
-    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], n_top * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (!(x[top] == U0)) emit({.kind = SolveStep::Copy, .level = top, .in = x[top], .out = U0});
+    return c;
+}
+
+void mg::solve_fusable_levels(const std::vector<int> &sizes, std::vector<int> *down_fused, std::vector<int> *up_fused)
+{
+    for (size_t l = 0; l + 1 < sizes.size(); ++l) {
+        const int N = sizes[l], M = sizes[l + 1];
+        down_fused->push_back(k::stream_fusable(N) && restrict_table(N, M).fusable);
+        up_fused->push_back(k::stream_fusable(N) && prolong_table(M, N).fusable);
+    }
+}
+
+k::SmoothNode<double> mg::solve_cycle_node(const SolveStep &s, const std::vector<int> &sizes, const std::vector<LevelConsts> &lc,
+                                           const NodeBatchItem &it)
+{
+    const int l = s.level, N = sizes[l], M = sizes[l + 1];
+    k::SmoothNode<double> nd{.N = N, .dx2 = lc[l].dx2, .inv = lc[l].inv, .in = (const double *)it.in, .F = (const double *)it.F,
+                             .out = (double *)it.out, .steps = s.steps, .d_sign = s.d_sign, .cw = lc[l].c, .dc = lc[l].d,
+                             .shifted = lc[l].sh.on};
+    if (s.fused_transfer && s.d_sign < 0) {
+        nd.Fc = (double *)it.Fc;
+        nd.M = M;
+        nd.rt = &restrict_table(N, M);
+    } else if (s.fused_transfer) {
+        nd.coarse = (const double *)it.coarse;
+        nd.Nc = M;
+        nd.pt = &prolong_table(M, N);
+    }
+    return nd;
+}
+
+int mg::run_solve_cycle(hipStream_t st, const SolveCycle &c, const SolveLevels &lv, const SolveOperator &op, const double *F0, double *U0)
+{
+    auto at = [&](FieldRef r) -> double * {
+        switch (r.f) {
+        case Field::U0: return U0;
+        case Field::F0: return const_cast<double *>(F0);
+        case Field::A: return (*lv.A)[r.level];
+        case Field::B: return (*lv.B)[r.level];
+        case Field::F: return (*lv.F)[r.level];
+        case Field::Coef: return const_cast<double *>(op.a(r.level));
+        case Field::None: break;
+        }
+        return nullptr;
+    };
+    int launches = 0;
+    for (const SolveStep &s : c.steps) {
+        const int l = s.level;
+        double *in = at(s.in), *F = at(s.F), *coarse = at(s.coarse), *out = at(s.out);
+        ++launches;
+        switch (s.kind) {
+        case SolveStep::Node: k::jacobi_stream(st, solve_cycle_node(s, *op.sizes, *op.lc, {in, F, coarse, out, at(s.Fc)})); break;
+        case SolveStep::Sweep: op.sweep(st, l, in, F, out); break;
+        case SolveStep::Residual: op.residual(st, l, in, F, out); break;
+        case SolveStep::Restrict: op.restrict_residual(st, l, in, out); break;
+        case SolveStep::Coarse: op.coarse_solve(st, out, F, lv.gs_state, lv.gs_err); break;
+        case SolveStep::ProlongAdd: op.prolong_add(st, l, coarse, in, out); break;
+        case SolveStep::Copy: {
+            const size_t n = (size_t)(*op.sizes)[l] * (*op.sizes)[l];
+            (void)MG_HIP(hipMemcpyAsync(out, in, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            --launches;   // (no kernel)
+            break;
+        }
+        }
+    }
     return launches;
 }
 
@@ -281,68 +371,13 @@ int mg::solver_size(const mg_solver *s, double *L)
 
 namespace {
 
-// the same cycle through the fused nodes of the streaming smoother (its weighted instantiations): per level one `-1`
-// launch (all pre sweeps + the restricted residual) and one `1` launch (prolongation-add + all post sweeps) where the
-// transfer stages fuse (even N, nested tables), the sweeps in one launch and the transfers operator by operator elsewhere.
-// Level 0: the `-1` node reads the caller's U and stores into B[0]; U is free until the `1` node writes the result there.
-// top > 0 (the full-multigrid start): the cycle starts at that level from the field U0 on the source F0 in the same way.
-void vcycle_fused(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top)
-{
-    const mg_solve_opts &o = s->o;
-    const int nl = (int)s->sizes.size();
-    const std::vector<LevelConsts> &lc = s->lc;
-    std::vector<double *> x(nl);   // per level: the field holding the pre-smoothed iterate, then the result
-    for (int l = top; l + 1 < nl; ++l) {
-        const int N = s->sizes[l], M = s->sizes[l + 1];
-        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
-        const bool shifted = lc[l].sh.on;
-        const double *F = l == top ? F0 : s->F[l];
-        const double *in = l == top ? U0 : nullptr;   // coarser levels: memset(U, 0) (:256) folded into the first sweep
-        double *out = l == top ? s->B[l] : s->A[l], *scratch = l == top ? U0 : s->B[l];
-        const RestrictTable &rt = restrict_table(N, M);
-        if (k::stream_fusable(N) && rt.fusable) {
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .Fc = s->F[l + 1], .M = M,
-                                  .rt = &rt, .cw = cw, .dc = dc, .shifted = shifted});
-        } else {
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.pre, .cw = cw, .dc = dc,
-                                  .shifted = shifted});
-            k::residual(st, N, inv, out, F, scratch, -1, lc[l].sh);
-            k::restrict_gather(st, N, scratch, M, s->F[l + 1], rt, +1);
-        }
-        x[l] = out;
-    }
-    const int Nc = s->sizes[nl - 1];
-    k::gauss_seidel_relative(st, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, s->A[nl - 1], s->F[nl - 1], o.coarse_atol, o.coarse_rtol,
-                             o.coarse_max_iters, s->gs_state, s->dev_scal + 2, lc[nl - 1].sh);
-    x[nl - 1] = s->A[nl - 1];
-    for (int l = nl - 2; l >= top; --l) {
-        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
-        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c, dc = lc[l].d;
-        const bool shifted = lc[l].sh.on;
-        const double *F = l == top ? F0 : s->F[l];
-        double *in = x[l], *out = l == top ? U0 : s->B[l];
-        const ProlongTable &pt = prolong_table(Nc_l, N);
-        if (k::stream_fusable(N) && pt.fusable) {
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = in, .F = F, .out = out, .steps = o.post, .d_sign = +1,
-                                  .coarse = x[l + 1], .Nc = Nc_l, .pt = &pt, .cw = cw, .dc = dc, .shifted = shifted});
-            x[l] = out;
-        } else {
-            // U + doProlongation(U_c) (:354, :368) into `out`, the sweeps back into `in`
-            k::prolong(st, Nc_l, x[l + 1], N, in, out, pt);
-            k::jacobi_stream(st, {.N = N, .dx2 = dx2, .inv = inv, .in = out, .F = F, .out = in, .steps = o.post, .d_sign = +1, .cw = cw,
-                                  .dc = dc, .shifted = shifted});
-            x[l] = in;
-        }
-    }
-    if (x[top] != U0) (void)MG_HIP(hipMemcpyAsync(U0, x[top], (size_t)s->sizes[top] * s->sizes[top] * sizeof(double), hipMemcpyDeviceToDevice, st));
-}
-
+// one cycle from level `top`: through the fused nodes of the streaming smoother (its weighted instantiations), which are the
+// constant operator's -- a boundary kind or a coefficient goes operator by operator whatever mg_set_smoother says (top == 0
+// with either: the full-multigrid start excludes both)
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
-    // the fused nodes are the constant operator's: a boundary kind or a coefficient goes operator by operator whatever
-    // mg_set_smoother says (top == 0 with either: the full-multigrid start excludes both)
-    if (s->op.kind || s->op.coef || ctx().smoother == SMOOTHER_SIMPLE) (void)solve_vcycle(st, s->lv, s->op, F0, U0, top);
-    else vcycle_fused(s, st, F0, U0, top);
+    const bool fused = !(s->op.kind || s->op.coef || ctx().smoother == SMOOTHER_SIMPLE);
+    (void)run_solve_cycle(st, s->cyc[fused][top], s->lv, s->op, F0, U0);
 }
 
 // The full-multigrid start (include/mg_hip.h, mg_solve_opts.fmg): the interior of U0 becomes the FMG guess, its rim is
@@ -521,6 +556,33 @@ void mg_solve_opts_default(mg_solve_opts *o)
     o->fmg = 0;
 }
 
+int mg_solve_cycle_describe(int nl, int pre, int post, int top, int fused, const int *down_fused, const int *up_fused, int with_coef,
+                            int *out, int cap)
+{
+    if (nl < 2 || pre < 1 || post < 1 || top < 0 || top > nl - 2 || (fused && (!down_fused || !up_fused))) {
+        fail(MG_ERR_ARG, "mg_solve_cycle_describe: nl = %d (at least 2), pre = %d, post = %d (at least 1 each), top = %d (inside "
+                         "[0, nl - 2]), or a fused cycle without its fusable levels", nl, pre, post, top);
+        return -1;
+    }
+    const SolveCycle c = build_solve_cycle(nl, pre, post, top, fused != 0, down_fused, up_fused, with_coef != 0);
+    const int n = (int)c.steps.size();
+    for (int i = 0; out && i < n && i < cap; ++i) {
+        const SolveStep &s = c.steps[i];
+        int *r = out + (size_t)i * MG_SOLVE_CYCLE_RECORD;
+        *r++ = s.kind;
+        *r++ = s.level;
+        *r++ = s.steps;
+        *r++ = s.d_sign;
+        *r++ = s.fused_transfer;
+        for (const FieldRef &f : {s.in, s.F, s.coarse, s.out, s.Fc}) {
+            *r++ = (int)f.f;
+            *r++ = f.level;
+        }
+        *r = s.slot;
+    }
+    return n;
+}
+
 mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
 {
     if (!require_ready("mg_solver_create")) return nullptr;
@@ -590,6 +652,11 @@ mg_solver *mg_solver_create(int N, double L, const mg_solve_opts *opts)
         return nullptr;
     }
     s->lv = SolveLevels{&s->A, &s->B, &s->F, s->gs_state, s->dev_scal + 2};
+    std::vector<int> down_fused, up_fused;
+    solve_fusable_levels(s->sizes, &down_fused, &up_fused);
+    for (int top = 0; top < (o.fmg >= 1 ? nl - 1 : 1); ++top)
+        for (int fused = 0; fused < 2; ++fused)
+            s->cyc[fused].push_back(build_solve_cycle(nl, o.pre, o.post, top, fused, down_fused.data(), up_fused.data(), false));
     s->history.reserve((size_t)o.max_cycles + 1);
     return s;
 }

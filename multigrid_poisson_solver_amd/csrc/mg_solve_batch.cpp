@@ -1,15 +1,18 @@
 // mg_solve_batch.cpp -- batched residual-tolerance solver (include/mg_hip.h, "batched residual-tolerance solver"): n
 // problems of one size and one set of options in one call, each instance bit-identical to mg_solver_solve alone.
-// One cycle follows vcycle_fused's node order and choices (mg_solve.cpp) for all active instances together: each launch
-// of the single cycle becomes ONE launch over the active set, the instance taken from a NodeBatchItem table by blockIdx
-// (the weighted streaming nodes, mg_stream_impl.h; the norm, coarse solve and transfer kernels, mg_solve_kernels.hip).
+// One cycle is the recorded SolveCycle that mg_solver walks (mg_internal.h, built by build_solve_cycle in mg_solve.cpp; DESIGN.md
+// 4.3.8), for all active instances together: each of its steps becomes ONE launch over the active set, the instance taken
+// from a NodeBatchItem table by blockIdx (the weighted streaming nodes, mg_stream_impl.h; the norm, coarse solve and transfer
+// kernels, mg_solve_kernels.hip).  fill_slot writes an instance's arrays into the table of every step, run_cycle_batch issues
+// the launches; neither knows the cycle's dataflow.
 // After each read-back the host drops the instances that met their tolerance from the active set and rebuilds and
 // uploads the tables when the set changed (the read-back already synchronises once per cycle, so one pinned staging
 // buffer serves every upload).
-// With a coefficient set (include/mg_varcoef_batch.h) the cycle is solve_vcycle's on that operator instead (mg_solve.cpp),
-// launch by launch over the active set through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip): vcycle_vc_batch below.
+// With a coefficient set (include/mg_varcoef_batch.h) the recorded cycle is the operator-by-operator one with the coefficient
+// in its steps, through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip).
 // With mg_batch_solver_set_krylov(m > 0) (include/mg_krylov_batch.h) the loop is restarted GCR(m) per instance around either
 // cycle: krylov_iterate_batch below, launch by launch over the active set (mg_krylov_batch_kernels.hip).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -29,7 +32,11 @@ struct mg_batch_solver {
     std::vector<double *> A, B, F;           // per level, max_batch instances each (level 0: only B)
     double *part = nullptr;                  // norm partials, resnorm_partials(N) per instance
     void *dev_rb = nullptr, *host_rb = nullptr;   // read-back block: res[max_batch], ref[max_batch], gs_state[4*max_batch]
-    NodeBatchItem *dev_tab = nullptr, *host_tab = nullptr;   // [n_tables][max_batch]
+    // the recorded cycles from level 0, set at creation: through the fused nodes, and operator by operator with the
+    // coefficient in its steps (MG_SMOOTHER=simple walks the latter too: mg_solver's walk takes the coefficient from its
+    // operator, which has none there)
+    SolveCycle cyc_fused, cyc_ops;
+    NodeBatchItem *dev_tab = nullptr, *host_tab = nullptr;   // [n_tables][max_batch]: table 0 the norm's, then the cycle's slots
     int n_tables = 0;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_sync = nullptr;
     std::vector<std::vector<double>> history;   // per instance of the last solve
@@ -65,31 +72,6 @@ double *rb_res(void *rb) { return static_cast<double *>(rb); }
 double *rb_ref(void *rb, int mb) { return static_cast<double *>(rb) + mb; }
 int *rb_state(void *rb, int mb) { return reinterpret_cast<int *>(static_cast<double *>(rb) + 2 * (size_t)mb); }
 
-// table slots of one cycle, in launch order: the norm, per level on the way down the node (+0), residual (+1) and
-// restriction (+2), the coarse solve, per level on the way up the node (+0) and prolongation (+1), the final copy
-int t_down(int l) { return 1 + 3 * l; }
-int t_gs(int nl) { return 1 + 3 * (nl - 1); }
-int t_up(int nl, int l) { return 2 + 3 * (nl - 1) + 2 * l; }
-int t_copy(int nl) { return 2 + 5 * (nl - 1); }
-int n_tables(int nl) { return 3 + 5 * (nl - 1); }
-// table slots of one variable-coefficient cycle: the norm, per level the two sweep directions between its fields P (the
-// caller's U at level 0, A[l] below) and Q = B[l] -- P -> Q (+0), Q -> P (+1): the sweeps ping-pong, so two tables serve all
-// of them --, the zero-start sweep into P (+2), the residual (+3), its restriction (+4) and the prolongation-add (+5), then
-// the coarse solve and the final copy
-int v_level(int l) { return 1 + 6 * l; }
-int v_gs(int nl) { return 1 + 6 * (nl - 1); }
-int v_copy(int nl) { return 2 + 6 * (nl - 1); }
-int n_tables_vc(int nl) { return 3 + 6 * (nl - 1); }
-
-bool down_fused(const mg_batch_solver *s, int l)
-{
-    return k::stream_fusable(s->sizes[l]) && restrict_table(s->sizes[l], s->sizes[l + 1]).fusable;
-}
-bool up_fused(const mg_batch_solver *s, int l)
-{
-    return k::stream_fusable(s->sizes[l]) && prolong_table(s->sizes[l + 1], s->sizes[l]).fusable;
-}
-
 double *level(const mg_batch_solver *s, const std::vector<double *> &v, int l, int i) { return v[l] + (size_t)i * s->pitch[l]; }
 
 void release(mg_batch_solver *s)
@@ -117,201 +99,77 @@ void release(mg_batch_solver *s)
     delete s;
 }
 
-// the arrays of instance i (active slot j) in every launch of one cycle: vcycle_fused's dataflow
-void fill_tables(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
-{
-    const int nl = (int)s->sizes.size(), mb = s->max_batch;
-    auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * mb + j]; };
-    std::vector<double *> x(nl);
-    item(0) = NodeBatchItem{U0, F0, nullptr, nullptr, nullptr};
-    for (int l = 0; l + 1 < nl; ++l) {
-        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
-        double *out = l == 0 ? level(s, s->B, 0, i) : level(s, s->A, l, i);
-        double *scratch = l == 0 ? U0 : level(s, s->B, l, i);
-        double *Fc = level(s, s->F, l + 1, i);
-        const bool fused = down_fused(s, l);
-        item(t_down(l)) = NodeBatchItem{l == 0 ? U0 : nullptr, F, nullptr, out, fused ? Fc : nullptr};
-        item(t_down(l) + 1) = NodeBatchItem{out, F, nullptr, scratch, nullptr};      // residual into the free field
-        item(t_down(l) + 2) = NodeBatchItem{scratch, nullptr, nullptr, Fc, nullptr};  // its restriction
-        x[l] = out;
-    }
-    item(t_gs(nl)) = NodeBatchItem{nullptr, level(s, s->F, nl - 1, i), nullptr, level(s, s->A, nl - 1, i), nullptr};
-    x[nl - 1] = level(s, s->A, nl - 1, i);
-    for (int l = nl - 2; l >= 0; --l) {
-        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
-        double *in = x[l], *out = l == 0 ? U0 : level(s, s->B, l, i);
-        if (up_fused(s, l)) {
-            item(t_up(nl, l)) = NodeBatchItem{in, F, x[l + 1], out, nullptr};
-            x[l] = out;
-        } else {
-            item(t_up(nl, l) + 1) = NodeBatchItem{in, nullptr, x[l + 1], out, nullptr};   // in + P(coarse) into `out`
-            item(t_up(nl, l)) = NodeBatchItem{out, F, nullptr, in, nullptr};              // the sweeps back into `in`
-            x[l] = in;
-        }
-    }
-    item(t_copy(nl)) = NodeBatchItem{x[0], nullptr, nullptr, U0, nullptr};
-}
+// the cycle the tables are built for: with a coefficient operator by operator, whatever mg_set_smoother says
+const SolveCycle &cycle_of(const mg_batch_solver *s) { return s->n_coef > 0 ? s->cyc_ops : s->cyc_fused; }
 
-// where the pre-smoothed iterate of level l lies when the cycle has the options' sweep counts: every sweep swaps the fields,
-// and coarser levels spend their first sweep on the zero start into P
-bool down_ends_in_p(const mg_batch_solver *s, int l) { return (l == 0 ? s->o.pre : s->o.pre - 1) % 2 == 0; }
-
-// the same for solve_vcycle's dataflow (mg_solve.cpp): cur / other of every launch of one cycle, the coefficient of
-// instance i (the one copy in shared mode) in the slot `coarse`
-void fill_tables_vc(mg_batch_solver *s, int j, const double *F0, double *U0, int i)
+// the arrays of instance i (active slot j) in the table of every step of the cycle; table 0: the norm's entry.  The coefficient
+// is copy i, or the one copy in shared mode
+void fill_slot(mg_batch_solver *s, const SolveCycle &c, int j, const double *F0, double *U0, int i)
 {
-    const int nl = (int)s->sizes.size(), mb = s->max_batch;
     const int ci = s->n_coef == 1 ? 0 : i;
-    auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * mb + j]; };
-    std::vector<double *> x(nl), y(nl);   // per level: the field holding the current iterate, and the free one
-    item(0) = NodeBatchItem{U0, F0, level(s, s->coef, 0, ci), nullptr, nullptr};
-    for (int l = 0; l + 1 < nl; ++l) {
-        const double *F = l == 0 ? F0 : level(s, s->F, l, i);
-        const double *a = level(s, s->coef, l, ci);
-        double *P = l == 0 ? U0 : level(s, s->A, l, i), *Q = level(s, s->B, l, i);
-        const int t = v_level(l);
-        item(t) = NodeBatchItem{P, F, a, Q, nullptr};
-        item(t + 1) = NodeBatchItem{Q, F, a, P, nullptr};
-        item(t + 2) = NodeBatchItem{nullptr, F, a, P, nullptr};
-        x[l] = down_ends_in_p(s, l) ? P : Q;
-        y[l] = down_ends_in_p(s, l) ? Q : P;
-        item(t + 3) = NodeBatchItem{x[l], F, a, y[l], nullptr};                              // residual into the free field
-        item(t + 4) = NodeBatchItem{y[l], nullptr, nullptr, level(s, s->F, l + 1, i), nullptr};   // its restriction
-    }
-    item(v_gs(nl)) = NodeBatchItem{nullptr, level(s, s->F, nl - 1, i), level(s, s->coef, nl - 1, ci), level(s, s->A, nl - 1, i), nullptr};
-    x[nl - 1] = level(s, s->A, nl - 1, i);
-    for (int l = nl - 2; l >= 0; --l) {
-        item(v_level(l) + 5) = NodeBatchItem{x[l], nullptr, x[l + 1], y[l], nullptr};   // x + P(coarse) into the free field
-        if (s->o.post % 2 == 0) x[l] = y[l];   // (the prolongation swapped the fields, every post sweep swaps them again)
-    }
-    item(v_copy(nl)) = NodeBatchItem{x[0], nullptr, nullptr, U0, nullptr};
+    auto at = [&](FieldRef r) -> double * {
+        switch (r.f) {
+        case Field::U0: return U0;
+        case Field::F0: return const_cast<double *>(F0);
+        case Field::A: return level(s, s->A, r.level, i);
+        case Field::B: return level(s, s->B, r.level, i);
+        case Field::F: return level(s, s->F, r.level, i);
+        case Field::Coef: return level(s, s->coef, r.level, ci);
+        case Field::None: break;
+        }
+        return nullptr;
+    };
+    auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * s->max_batch + j]; };
+    item(0) = NodeBatchItem{U0, F0, s->n_coef > 0 ? level(s, s->coef, 0, ci) : nullptr, nullptr, nullptr};
+    for (const SolveStep &t : c.steps) item(t.slot) = NodeBatchItem{at(t.in), at(t.F), at(t.coarse), at(t.out), at(t.Fc)};
 }
 
-// (without a coefficient: exactly the tables, and the bytes, the solver uploaded before it knew of one)
+// (without a coefficient: no more tables, and bytes, than the solver uploaded before it knew of one)
 bool upload_tables(mg_batch_solver *s, hipStream_t st)
 {
-    const int nl = (int)s->sizes.size();
-    const int used = s->n_coef > 0 ? n_tables_vc(nl) : n_tables(nl);
-    return MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)used * s->max_batch * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st));
+    const size_t used = (size_t)cycle_of(s).n_slots + 1;
+    return MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, used * s->max_batch * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st));
 }
 
-// one V(pre, post) cycle of the n active instances whose tables are uploaded; returns the launches it enqueued
-int vcycle_batch(mg_batch_solver *s, hipStream_t st, int n)
+// one cycle of the n active instances whose tables are uploaded: every step ONE launch over them from the table of its slot,
+// with the `_vc` kernels when a coefficient is set; returns the launches it enqueued
+int run_cycle_batch(mg_batch_solver *s, hipStream_t st, const SolveCycle &c, int n)
 {
     const mg_solve_opts &o = s->o;
     const int nl = (int)s->sizes.size(), mb = s->max_batch;
-    const std::vector<LevelConsts> &lc = s->lc;
-    const NodeBatchItem *h = s->host_tab, *d = s->dev_tab;   // (slot 0 of a host table: the shape of a node)
-    auto node = [&](int t) { return NodeBatch{n, d + (size_t)t * mb, nullptr}; };
-    int launches = 0;
-    for (int l = 0; l + 1 < nl; ++l) {
-        const int N = s->sizes[l], M = s->sizes[l + 1];
-        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c;
-        const int t = t_down(l);
-        const NodeBatchItem &it = h[(size_t)t * mb];
-        const NodeBatch nb = node(t);
-        const RestrictTable &rt = restrict_table(N, M);
-        k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
-                                 .out = (double *)it.out, .steps = o.pre, .batch = &nb, .cw = cw, .dc = lc[l].d,
-                                 .shifted = lc[l].sh.on};
-        if (down_fused(s, l)) {
-            nd.Fc = (double *)it.Fc;
-            nd.M = M;
-            nd.rt = &rt;
+    const bool vc = s->n_coef > 0;
+    for (const SolveStep &t : c.steps) {
+        const int l = t.level, N = s->sizes[l], M = l + 1 < nl ? s->sizes[l + 1] : 0;   // (M: the coarse size of a transfer)
+        const LevelConsts &lc = s->lc[l];
+        const NodeBatchItem *tab = s->dev_tab + (size_t)t.slot * mb;
+        switch (t.kind) {
+        case SolveStep::Node: {
+            const NodeBatch nb{n, tab, nullptr};
+            // (active slot 0 of the host table: the shape of the node)
+            k::SmoothNode<double> nd = solve_cycle_node(t, s->sizes, s->lc, s->host_tab[(size_t)t.slot * mb]);
+            nd.batch = &nb;
             k::jacobi_stream(st, nd);
-            launches += 1;
-        } else {
-            k::jacobi_stream(st, nd);
-            k::residual_batch(st, n, N, inv, d + (size_t)(t + 1) * mb, -1, lc[l].sh);
-            k::restrict_batch(st, n, N, M, d + (size_t)(t + 2) * mb, rt, +1);
-            launches += 3;
+            break;
+        }
+        case SolveStep::Sweep: k::wjacobi_vc_batch(st, n, N, lc.dx2, lc.sd, o.omega, t.in.f == Field::None, tab); break;
+        case SolveStep::Residual:
+            if (vc) k::residual_vc_batch(st, n, N, lc.inv, lc.sd, tab, -1);
+            else k::residual_batch(st, n, N, lc.inv, tab, -1, lc.sh);
+            break;
+        case SolveStep::Restrict: k::restrict_batch(st, n, N, M, tab, restrict_table(N, M), +1); break;
+        case SolveStep::Coarse:
+            if (vc)
+                k::gauss_seidel_relative_vc_batch(st, n, N, lc.dx2, lc.inv, lc.sd, tab, o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                                                  rb_state(s->dev_rb, mb));
+            else
+                k::gauss_seidel_relative_batch(st, n, N, lc.dx2, lc.inv, tab, o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                                               rb_state(s->dev_rb, mb), lc.sh);
+            break;
+        case SolveStep::ProlongAdd: k::prolong_add_batch(st, n, M, N, tab, prolong_table(M, N)); break;
+        case SolveStep::Copy: k::copy_batch(st, n, (size_t)N * N, tab); break;
         }
     }
-    const int Nc = s->sizes[nl - 1];
-    k::gauss_seidel_relative_batch(st, n, Nc, lc[nl - 1].dx2, lc[nl - 1].inv, d + (size_t)t_gs(nl) * mb, o.coarse_atol,
-                                   o.coarse_rtol, o.coarse_max_iters, rb_state(s->dev_rb, mb), lc[nl - 1].sh);
-    launches += 1;
-    bool copy = false;
-    for (int l = nl - 2; l >= 0; --l) {
-        const int N = s->sizes[l], Nc_l = s->sizes[l + 1];
-        const double dx2 = lc[l].dx2, inv = lc[l].inv, cw = lc[l].c;
-        const int t = t_up(nl, l);
-        const NodeBatchItem &it = h[(size_t)t * mb];
-        const NodeBatch nb = node(t);
-        const ProlongTable &pt = prolong_table(Nc_l, N);
-        k::SmoothNode<double> nd{.N = N, .dx2 = dx2, .inv = inv, .in = (const double *)it.in, .F = (const double *)it.F,
-                                 .out = (double *)it.out, .steps = o.post, .d_sign = +1, .batch = &nb, .cw = cw,
-                                 .dc = lc[l].d, .shifted = lc[l].sh.on};
-        if (up_fused(s, l)) {
-            nd.coarse = (const double *)it.coarse;
-            nd.Nc = Nc_l;
-            nd.pt = &pt;
-            k::jacobi_stream(st, nd);
-            launches += 1;
-        } else {
-            k::prolong_add_batch(st, n, Nc_l, N, d + (size_t)(t + 1) * mb, pt);
-            k::jacobi_stream(st, nd);
-            launches += 2;
-            copy = l == 0;   // the result is in B[0], not in the caller's U
-        }
-    }
-    if (copy) {
-        k::copy_batch(st, n, (size_t)s->N * s->N, d + (size_t)t_copy(nl) * mb);
-        launches += 1;
-    }
-    return launches;
-}
-
-// one V(pre, post) cycle with the coefficient: solve_vcycle's node order and field ping-pong (mg_solve.cpp), each of its
-// launches ONE launch over the n active instances whose tables are uploaded; returns the launches it enqueued
-int vcycle_vc_batch(mg_batch_solver *s, hipStream_t st, int n)
-{
-    const mg_solve_opts &o = s->o;
-    const int nl = (int)s->sizes.size(), mb = s->max_batch;
-    const std::vector<LevelConsts> &lc = s->lc;
-    auto tab = [&](int t) { return s->dev_tab + (size_t)t * mb; };
-    std::vector<char> in_p(nl, 1);   // per level: the current iterate is in P (else in Q)
-    int launches = 0;
-    for (int l = 0; l + 1 < nl; ++l) {
-        const int N = s->sizes[l], M = s->sizes[l + 1], t = v_level(l);
-        bool p = true;
-        int sweeps = o.pre;
-        if (l > 0) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, true, tab(t + 2));
-            ++launches;
-            --sweeps;
-        }
-        for (int i = 0; i < sweeps; ++i) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, false, tab(p ? t : t + 1));
-            ++launches;
-            p = !p;
-        }
-        k::residual_vc_batch(st, n, N, lc[l].inv, lc[l].sd, tab(t + 3), -1);
-        k::restrict_batch(st, n, N, M, tab(t + 4), restrict_table(N, M), +1);
-        launches += 2;
-        in_p[l] = p;
-    }
-    const int last = nl - 1;
-    k::gauss_seidel_relative_vc_batch(st, n, s->sizes[last], lc[last].dx2, lc[last].inv, lc[last].sd, tab(v_gs(nl)), o.coarse_atol,
-                                      o.coarse_rtol, o.coarse_max_iters, rb_state(s->dev_rb, mb));
-    ++launches;
-    for (int l = nl - 2; l >= 0; --l) {
-        const int N = s->sizes[l], Nc_l = s->sizes[l + 1], t = v_level(l);
-        k::prolong_add_batch(st, n, Nc_l, N, tab(t + 5), prolong_table(Nc_l, N));
-        ++launches;
-        bool p = !in_p[l];
-        for (int i = 0; i < o.post; ++i) {
-            k::wjacobi_vc_batch(st, n, N, lc[l].dx2, lc[l].sd, o.omega, false, tab(p ? t : t + 1));
-            ++launches;
-            p = !p;
-        }
-        in_p[l] = p;
-    }
-    if (!in_p[0]) {   // the result is in B[0], not in the caller's U
-        k::copy_batch(st, n, (size_t)s->N * s->N, tab(v_copy(nl)));
-        ++launches;
-    }
-    return launches;
+    return (int)c.steps.size();
 }
 
 // the same cycle operator by operator, instance by instance (MG_SMOOTHER=simple): the yardstick of the batched launches
@@ -329,7 +187,8 @@ int vcycle_simple_each(mg_batch_solver *s, hipStream_t st, const std::vector<int
             B[l] = level(s, s->B, l, i);
             F[l] = level(s, s->F, l, i);
         }
-        launches += solve_vcycle(st, SolveLevels{&A, &B, &F, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr}, op, F0[i], U0[i]);
+        const SolveLevels lv{&A, &B, &F, rb_state(s->dev_rb, s->max_batch) + 4 * j, nullptr};
+        launches += run_solve_cycle(st, s->cyc_ops, lv, op, F0[i], U0[i]);
     }
     return launches;
 }
@@ -465,7 +324,7 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
             double *ri = s->kr_r + (size_t)i * p0, *z = s->kr_Z[kk] + (size_t)i * p0, *q = s->kr_Q[kk] + (size_t)i * p0;
             s->kr_F[i] = ri;
             s->kr_U[i] = z;
-            (vc ? fill_tables_vc : fill_tables)(s, j, ri, z, i);
+            fill_slot(s, cycle_of(s), j, ri, z, i);
             host.act[j] = k::KrylovBatchItem{U_dev[i], ri, z, q, s->kr_scal + (size_t)i * k::KRYLOV_SCAL_COUNT,
                                              s->kr_part + (size_t)i * n_part, rec_of(i), (size_t)i * p0, kk, 0};
             host.apply[j] = NodeBatchItem{z, nullptr, coef_of(i), q, nullptr};
@@ -481,8 +340,8 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
             k::krylov_zero_batch(st, na, N, dev.act);
         }
         bs.launches += 1;
-        bs.launches += vc ? vcycle_vc_batch(s, st, na)
-                          : simple ? vcycle_simple_each(s, st, act, s->kr_F.data(), s->kr_U.data()) : vcycle_batch(s, st, na);
+        bs.launches += simple && !vc ? vcycle_simple_each(s, st, act, s->kr_F.data(), s->kr_U.data())
+                                     : run_cycle_batch(s, st, cycle_of(s), na);
         {
             ProfScope ps("krylov_apply_batch", N, pts * na * (vc ? 24.0 : 16.0));
             k::apply_vc_batch(st, na, N, s->lc[0].inv, sd, dev.apply);
@@ -560,15 +419,14 @@ const double *mg::batch_solver_coefficient(const mg_batch_solver *s, int i)
 
 int mg::batch_solver_cycle(mg_batch_solver *s, hipStream_t st, int n, const double *const *F0, double *const *U0)
 {
-    const bool vc = s->n_coef > 0;
     std::vector<int> act(n);
     for (int i = 0; i < n; ++i) {
         act[i] = i;
-        (vc ? fill_tables_vc : fill_tables)(s, i, F0[i], U0[i], i);
+        fill_slot(s, cycle_of(s), i, F0[i], U0[i], i);
     }
     if (!upload_tables(s, st)) return -1;
-    if (vc) return vcycle_vc_batch(s, st, n);
-    return ctx().smoother == SMOOTHER_SIMPLE ? vcycle_simple_each(s, st, act, F0, U0) : vcycle_batch(s, st, n);
+    if (s->n_coef == 0 && ctx().smoother == SMOOTHER_SIMPLE) return vcycle_simple_each(s, st, act, F0, U0);
+    return run_cycle_batch(s, st, cycle_of(s), n);
 }
 
 bool mg::batch_solver_enqueue_state(mg_batch_solver *s, hipStream_t st)
@@ -631,7 +489,15 @@ mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg
         const int Nf = s->sizes[l], Nc = s->sizes[l + 1];
         ok = restrict_table(Nf, Nc).lo != nullptr && prolong_table(Nc, Nf).owner_row != nullptr;
     }
-    s->n_tables = n_tables_vc(nl);   // (the larger set: a coefficient may be set later, and a solve allocates nothing)
+    if (ok) {
+        std::vector<int> down_fused, up_fused;
+        solve_fusable_levels(s->sizes, &down_fused, &up_fused);
+        s->cyc_fused = build_solve_cycle(nl, o.pre, o.post, 0, true, down_fused.data(), up_fused.data(), false);
+        s->cyc_ops = build_solve_cycle(nl, o.pre, o.post, 0, false, nullptr, nullptr, true);
+    }
+    // the norm's table and the slots of the larger cycle (a coefficient may be set later, and a solve allocates nothing); at
+    // least nl tables, which mg_batch_solver_set_coefficient borrows for its check and coarsening launches
+    s->n_tables = std::max(nl, std::max(s->cyc_fused.n_slots, s->cyc_ops.n_slots) + 1);
     const size_t tab_bytes = (size_t)s->n_tables * max_batch * sizeof(NodeBatchItem);
     ok = ok && MG_HIP(hipMalloc((void **)&s->part, k::resnorm_partials(N) * max_batch * sizeof(double))) &&
          MG_HIP(hipMalloc(&s->dev_rb, rb_bytes(max_batch))) &&
@@ -719,7 +585,7 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
     for (int i = 0; i < n; ++i) act[i] = i;
     auto build = [&]() {
         for (size_t j = 0; j < act.size(); ++j)
-            (vc ? fill_tables_vc : fill_tables)(s, (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
+            fill_slot(s, cycle_of(s), (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
         return upload_tables(s, st);
     };
     if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
@@ -745,7 +611,7 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
             if (!build()) return finish(MG_ERR_HIP);
         }
         const int na = (int)act.size();
-        bs.launches += vc ? vcycle_vc_batch(s, st, na) : simple ? vcycle_simple_each(s, st, act, F_dev, U_dev) : vcycle_batch(s, st, na);
+        bs.launches += simple && !vc ? vcycle_simple_each(s, st, act, F_dev, U_dev) : run_cycle_batch(s, st, cycle_of(s), na);
         bs.launches += vc ? norms_vc(s, st, na, rb_res(s->dev_rb)) : norms(s, st, na, true, rb_res(s->dev_rb));
         if (!read_back(s, st)) return finish(MG_ERR_HIP);
         next.clear();

@@ -1,5 +1,5 @@
 // mg_varcoef_batch_kernels.hip -- batched forms of the variable-coefficient kernels (include/mg_varcoef_batch.h; driven by
-// mg_solve_batch.cpp: vcycle_vc_batch): ONE launch runs a kernel of mg_varcoef_kernels.hip for every active instance.  The
+// mg_solve_batch.cpp: run_cycle_batch): ONE launch runs a kernel of mg_varcoef_kernels.hip for every active instance.  The
 // __device__ bodies are the ones of mg_varcoef_impl.h, compiled here with the same flags (-ffp-contract=off): an instance
 // runs the code, the block partition (grid x, y) and the summation order of its single launch, so its bits are the single
 // solve's.  Which instance a block works on: blockIdx.z for the streaming kernels, whose single grids are (column blocks,
