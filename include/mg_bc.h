@@ -68,9 +68,9 @@
  * Memory contract (mg_hip.h): every function below reads its const arrays and writes its output array and nothing else.
  * Device arrays are 16-byte aligned, N >= 3, no output overlaps an input.
  *
- * Not built, each refused with a message that names it: the pure Neumann problem at sigma = 0 (mean fixing and the
- * compatibility projection), boundary kinds in the batched solver, the eigen-solver, the full-multigrid start, the Krylov
- * acceleration and the adjoint, Robin and periodic sides.
+ * Not built, each refused with a message that names it: boundary kinds in the batched solver, the eigen-solver, the
+ * full-multigrid start, the Krylov acceleration and the adjoint, Robin and periodic sides.  The pure Neumann problem at
+ * sigma = 0 (mean fixing and the compatibility projection) is mg_singular.h's, and is refused here until it is switched on there.
  */
 #ifndef MG_BC_H
 #define MG_BC_H
@@ -86,7 +86,7 @@ extern "C" {
  * call with a Neumann side builds the prolongation tables of the hierarchy on the device.  Returns 0, or (mg_last_error; the
  * solver keeps the state it had, the earlier kinds included, and stays usable):
  *   MG_ERR_ARG (2)          NULL solver or kind, or a kind outside {0, 1}
- *   MG_ERR_UNSUPPORTED (3)  four Neumann sides with shift == 0 (the singular problem: fixing the mean is not built); a solver
+ *   MG_ERR_UNSUPPORTED (3)  four Neumann sides with shift == 0 (the singular problem) without mg_solver_set_mean; a solver
  *                           created with fmg != 0; the Krylov acceleration switched on
  * While a boundary is set, mg_solver_set_krylov(m > 0) and mg_solver_adjoint are refused with MG_ERR_UNSUPPORTED. */
 int  mg_solver_set_boundary(mg_solver *s, const int *kind);
@@ -124,4 +124,6 @@ int  mg_heat_stepper_set_boundary(mg_heat_stepper *st, const int *kind);
 #ifdef __cplusplus
 }
 #endif
+/* the pure Neumann problem (four flux sides at sigma = 0, mean fixed): mg_solver_set_mean, mg_weightedMean, mg_projectMean */
+#include "mg_singular.h"
 #endif /* MG_BC_H */

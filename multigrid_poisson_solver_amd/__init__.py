@@ -253,6 +253,17 @@ ABI_BC = {
 }
 DIRICHLET, NEUMANN = 0, 1
 
+# the symbols include/mg_singular.h declares (the pure Neumann problem: four flux sides at sigma = 0, the mean fixed); bound like
+# ABI_FMG: a library without them still loads, Solver.set_mean() / weighted_mean() / project_mean() / ... then raise
+ABI_SINGULAR = {
+    "mg_solver_set_mean": (_i, [_vp, _i, _d]),
+    "mg_solver_mean": (_i, [_vp, _vp]),
+    "mg_solver_singular_info": (None, [_vp, _vp]),
+    "mg_weightedMean": (None, [_i, _vp, _vp]),
+    "mg_projectMean": (None, [_i, _vp, _d, _vp, _vp]),
+    "mg_coarseSolveMean": (None, [_i, _d, _vp, _vp, _vp, _d, _d, _i, _vp, _vp]),
+}
+
 # the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
 # ABI_FMG: a library without it still loads, solve_cycle() then raises
 ABI_SOLVE_CYCLE = {
@@ -318,7 +329,7 @@ def load_library(path=None):
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
-            list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SOLVE_CYCLE.items()):
+            list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -828,6 +839,100 @@ def prolongAddBoundary(M, bc, U_c, N, U_in, U_out):
     _check()
 
 
+def _need_singular(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the pure Neumann problem)")
+    return getattr(_lib, name)
+
+
+def _on_array_stream(arrays, call):
+    """call() with the engine on torch.cuda.current_stream() when any of `arrays` is a torch tensor, as neumann_source does"""
+    ts = [t for t in arrays if _is_torch(t)]
+    if not ts:
+        return call()
+    import torch
+    prev = _lib.mg_get_stream()
+    _lib.mg_set_stream(torch.cuda.current_stream(ts[0].device).cuda_stream)
+    try:
+        return call()
+    finally:
+        _lib.mg_set_stream(prev)
+
+
+def _square_address(X, what, keep, N=None):
+    """(N, device address) of a square fp64 field for the length of a call, by neumann_source's rules: a float64 torch CUDA
+    tensor (contiguous, 16-byte aligned), a DeviceGrid (anything with .ptr and .shape), or a numpy array, which is uploaded into
+    a DeviceGrid appended to `keep` (the caller frees it)."""
+    shape = tuple(X.shape)
+    if len(shape) != 2 or shape[0] != shape[1] or (N is not None and shape[0] != N):
+        raise MGError(f"{what}: shape {shape}, expected a square array" + (f" of size {N}" if N is not None else ""))
+    if _is_torch(X):
+        import torch
+        if not (X.is_cuda and X.dtype == torch.float64 and X.is_contiguous() and X.data_ptr() % 16 == 0):
+            raise MGError(f"{what}: expected a contiguous, 16-byte aligned float64 CUDA tensor")
+        return shape[0], X.data_ptr()
+    if hasattr(X, "ptr"):
+        return shape[0], X.ptr
+    keep.append(DeviceGrid.from_host(np.asarray(X, dtype=np.float64)))
+    return shape[0], keep[-1].ptr
+
+
+def weighted_mean(X):
+    """mg_weightedMean: the trapezoid-weighted mean of a square field, (sum of w*X)/(N-1)^2 with w = 1 inside, 1/2 on a side and
+    1/4 in a corner, summed in the fixed order of include/mg_singular.h (the same bits every run).  With four Neumann sides at
+    sigma = 0 it is the compatibility defect of a right-hand side and the gauge of a solution.  X: numpy array, DeviceGrid or
+    float64 torch CUDA tensor (on torch.cuda.current_stream())."""
+    fn = _need_singular("mg_weightedMean")
+    keep, out = [], C.c_double(0.0)
+    try:
+        N, ptr = _square_address(X, "X", keep)
+        _on_array_stream([X], lambda: fn(N, ptr, C.byref(out)))
+        _check()
+        return float(out.value)
+    finally:
+        for k in keep:
+            k.free()
+
+
+def project_mean(X, mean=0.0, out=None, want_removed=False):
+    """mg_projectMean: out = X - (weighted_mean(X) - mean) at every point, so that weighted_mean(out) is `mean` up to rounding.
+    X: numpy array (the result is a new numpy array), DeviceGrid (out = None: a new DeviceGrid) or float64 torch CUDA tensor (on
+    torch.cuda.current_stream(); out = None: a new tensor); out may be X itself.  want_removed: returns (out, weighted_mean(X))."""
+    fn = _need_singular("mg_projectMean")
+    keep, removed = [], C.c_double(0.0)
+    host = not (_is_torch(X) or hasattr(X, "ptr"))
+    try:
+        N, ptr = _square_address(X, "X", keep)
+        if out is None:
+            if _is_torch(X):
+                import torch
+                out = torch.empty_like(X)
+            else:
+                out = DeviceGrid((N, N))
+                if host:
+                    keep.append(out)
+        elif host:
+            raise MGError("out: a numpy X gives a new numpy array; pass DeviceGrids or tensors to name the output")
+        _, optr = _square_address(out, "out", keep, N)
+        _on_array_stream([X, out], lambda: fn(N, ptr, float(mean), optr, C.byref(removed)))
+        _check()
+        res = out.to_host() if host else out
+        return (res, float(removed.value)) if want_removed else res
+    finally:
+        for k in keep:
+            k.free()
+
+
+def coarseSolveMean(N, L, bc, a, F, atol, rtol, max_iters, U_out):
+    """Test hook (include/mg_singular.h).  The projected coarse solve alone on DeviceGrids: U_out = the red-black solve from
+    zero on F minus its weighted mean, N <= 63, bc four Neumann sides, a = None is a = 1.  Returns (removed mean, iterations)."""
+    removed = C.c_double(0.0)
+    _need_singular("mg_coarseSolveMean")(int(N), float(L), _kinds(bc), _opt(a), F.ptr, float(atol), float(rtol), int(max_iters),
+                                         U_out.ptr, C.byref(removed))
+    _check()
+    return float(removed.value), lastExactSolverIterations()
+
+
 def _need_krylov(name):
     if not hasattr(lib(), name):
         raise MGError(f"{LIB_PATH} does not export {name} (a build without the Krylov acceleration)")
@@ -1267,10 +1372,15 @@ class Solver:
     recomputed residual, never on the recurred norm; info gains `breakdown`.  krylov=0 (the default) is the plain solver, bit for bit.
     bc=kinds (or set_boundary(kinds)) makes sides Neumann (include/mg_bc.h): four kinds in the order S, N, W, E -- row 0, row
     N-1, column 0, column N-1 -- as a sequence of DIRICHLET / NEUMANN or a string such as "ndnd".  On Neumann sides the rim of
-    U is part of the guess and is written; flux data goes into F with neumann_source()."""
+    U is part of the guess and is written; flux data goes into F with neumann_source().
+    mean=m (or set_mean(m)) opens the pure Neumann problem, bc="nnnn" at shift == 0 (include/mg_singular.h): the solve removes
+    the weighted mean of F (info["compat_defect"]: what the data lacked in compatibility), runs the cycles with a projected
+    coarse solve, and returns the solution whose weighted mean is m (info["mean_before"]: what it was before that shift).
+    With any other boundary or shift the setting is dormant."""
 
     def __init__(self, N, L=1.0, coef=None, krylov=0, **opts):
         bc = opts.pop("bc", None)   # (the boundary kinds travel beside the solve options, not in mg_solve_opts)
+        mean = opts.pop("mean", None)
         self.N, self.L = int(N), float(L)
         self.opts = solve_opts(**opts)
         self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
@@ -1282,11 +1392,31 @@ class Solver:
                 self.set_coefficient(coef)
             if krylov:
                 self.set_krylov(krylov)
+            if mean is not None:
+                self.set_mean(mean)
             if bc is not None:
                 self.set_boundary(bc)
         except Exception:
             self.close()
             raise
+
+    def set_mean(self, mean):
+        """mean: the weighted mean (weighted_mean) the solution of a singular solve gets, which also lets set_boundary("nnnn")
+        through at shift == 0 (include/mg_singular.h); None: off.  Dormant while the operator is not singular: the solver then
+        enqueues what it enqueues without it.  A refusal (MGError) leaves the solver as it was: "[2]" a mean that is not
+        finite; "[3]" None while four Neumann sides at shift == 0 are set."""
+        fn = _need_singular("mg_solver_set_mean")
+        status = fn(self._s, 0, 0.0) if mean is None else fn(self._s, 1, float(mean))
+        if status:
+            _check()
+            raise MGError(f"mg_solver_set_mean failed with status {status}")
+
+    @property
+    def mean(self):
+        """the target of set_mean, or None while it is off"""
+        out = C.c_double(0.0)
+        on = _need_singular("mg_solver_mean")(self._s, C.byref(out))
+        return float(out.value) if on else None
 
     def set_krylov(self, m):
         """m = 1 .. 16: restarted GCR(m) around the cycle (include/mg_krylov.h), m directions kept between restarts; m = 0:
@@ -1365,6 +1495,11 @@ class Solver:
         if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
             self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))
             info["breakdown"] = bool(_lib.mg_solver_krylov_breakdown(self._s))
+        if hasattr(_lib, "mg_solver_mean") and _lib.mg_solver_mean(self._s, None) and self.boundary == (1, 1, 1, 1) \
+                and self.opts.shift == 0.0:   # a singular solve (include/mg_singular.h)
+            three = (C.c_double * 3)()
+            _lib.mg_solver_singular_info(self._s, three)
+            info["compat_defect"], info["mean_before"], info["mean"] = float(three[0]), float(three[1]), float(three[2])
         return info
 
     def solve(self, F, U=None):
@@ -1506,7 +1641,9 @@ def solve(F, U=None, L=1.0, **opts):
     krylov=m (1..16) wraps the cycle in restarted GCR(m) (Solver.set_krylov, include/mg_krylov.h): (2m + 1)*N^2 doubles of
     memory more, a residual norm that cannot grow, and convergence stated on a recomputed residual only.
     bc=kinds makes sides Neumann (Solver.set_boundary): four kinds in the order S, N, W, E (row 0, row N-1, column 0, column
-    N-1), e.g. "ndnd"; on Neumann sides the rim of U is part of the guess and is written."""
+    N-1), e.g. "ndnd"; on Neumann sides the rim of U is part of the guess and is written.
+    bc="nnnn" with mean=m at shift == 0 is the pure Neumann problem (Solver.set_mean): F is projected onto the compatible
+    right-hand sides and the solution returned has the weighted mean m."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:

@@ -218,9 +218,21 @@ __device__ __forceinline__ void bc_pairs(const BcArgs &b)
 // gs_relative_vc_body (mg_varcoef_impl.h) on the unknowns with mirrored neighbours: ONE workgroup, U and F in LDS, zero
 // start, colour 0 = (row + col) even then colour 1, the same stopping rule and state[].  A thread keeps the LDS indices of
 // its points' four neighbours beside their face coefficients; Ag == nullptr: a = 1.
+// MEAN (include/mg_singular.h, four Neumann sides at shift == 0): the right-hand side first loses its weighted mean m_c, summed
+// in the header's order from the values on their way into LDS; err0, the target and the iteration see the projected values,
+// Fg itself is not written.  mean_out (may be null): m_c.  Without MEAN the body is what it was, statement for statement.
+
+// the trapezoid weight of point (r, c) of an N x N grid: 1/2 on a side, 1/4 in a corner
+__device__ __forceinline__ double mean_weight(int r, int c, int N)
+{
+    return (r == 0 || r == N - 1 ? 0.5 : 1.0) * (c == 0 || c == N - 1 ? 0.5 : 1.0);
+}
+
+template <bool MEAN>
 __device__ __forceinline__ void gs_relative_bc_body(int N, BcGeom g, double h2, double inv, double sd, const double *__restrict__ Ag,
                                                     double *__restrict__ Ug, const double *__restrict__ Fg, double atol, double rtol,
-                                                    int max_iters, int *__restrict__ state, double *__restrict__ err_out)
+                                                    int max_iters, int *__restrict__ state, double *__restrict__ err_out,
+                                                    double *__restrict__ mean_out = nullptr)
 {
     extern __shared__ __align__(16) double lds[];
     __shared__ double s_val;
@@ -232,6 +244,7 @@ __device__ __forceinline__ void gs_relative_bc_body(int N, BcGeom g, double h2, 
     int colour_of[GS_PTS];   // 0 / 1: an unknown of that colour; -1: a data point, or beyond the grid
     int pN[GS_PTS], pS[GS_PTS], pE[GS_PTS], pW[GS_PTS];
     double acc = 0.0;
+    [[maybe_unused]] double wacc = 0.0;
 #pragma unroll
     for (int j = 0; j < GS_PTS; ++j) {
         const int p = threadIdx.x + j * blockDim.x;
@@ -244,8 +257,9 @@ __device__ __forceinline__ void gs_relative_bc_body(int N, BcGeom g, double h2, 
             F[p] = f;
             U[p] = 0.0;
             const int r = p / N, c = p - r * N;
+            if constexpr (MEAN) wacc = wacc + mean_weight(r, c, N) * f;
             if (r >= g.r_lo && r <= g.r_hi && c >= g.c_lo && c <= g.c_hi) {
-                acc = acc + fabs(f);
+                if constexpr (!MEAN) acc = acc + fabs(f);
                 colour_of[j] = (r + c) & 1;
                 pN[j] = (r + 1 < N ? r + 1 : g.above) * N + c;
                 pS[j] = (r > 0 ? r - 1 : g.below) * N + c;
@@ -254,6 +268,25 @@ __device__ __forceinline__ void gs_relative_bc_body(int N, BcGeom g, double h2, 
                 if (Ag) fc[j] = faces(Ag[p], Ag[pN[j]], Ag[pS[j]], Ag[pE[j]], Ag[pW[j]], sd);
                 else fc[j] = faces(1.0, 1.0, 1.0, 1.0, 1.0, sd);
                 qc[j] = 1.0 / fc[j].d;
+            }
+        }
+    }
+    if constexpr (MEAN) {
+        const double ws = block_sum(wacc);
+        if (threadIdx.x == 0) {
+            s_val = ws / ((double)(N - 1) * (double)(N - 1));
+            if (mean_out) *mean_out = s_val;
+        }
+        __syncthreads();
+        const double m = s_val;
+        __syncthreads();   // every thread has read s_val before thread 0 writes err0 into it
+#pragma unroll
+        for (int j = 0; j < GS_PTS; ++j) {
+            const int p = threadIdx.x + j * blockDim.x;
+            if (p < n) {   // (a thread's own points, here and in every loop below)
+                const double f = F[p] - m;
+                F[p] = f;
+                if (colour_of[j] >= 0) acc = acc + fabs(f);
             }
         }
     }

@@ -34,7 +34,17 @@ __global__ __launch_bounds__(1024) void k_gs_relative_bc(int N, BcGeom g, double
                                                          const double *__restrict__ Fg, double atol, double rtol, int max_iters,
                                                          int *__restrict__ state, double *__restrict__ err_out)
 {
-    gs_relative_bc_body(N, g, h2, inv, sd, Ag, Ug, Fg, atol, rtol, max_iters, state, err_out);
+    gs_relative_bc_body<false>(N, g, h2, inv, sd, Ag, Ug, Fg, atol, rtol, max_iters, state, err_out);
+}
+
+// its twin for the singular problem (include/mg_singular.h): the right-hand side loses its weighted mean first
+__global__ __launch_bounds__(1024) void k_gs_relative_bc_mean(int N, BcGeom g, double h2, double inv, double sd,
+                                                              const double *__restrict__ Ag, double *__restrict__ Ug,
+                                                              const double *__restrict__ Fg, double atol, double rtol, int max_iters,
+                                                              int *__restrict__ state, double *__restrict__ err_out,
+                                                              double *__restrict__ mean_out)
+{
+    gs_relative_bc_body<true>(N, g, h2, inv, sd, Ag, Ug, Fg, atol, rtol, max_iters, state, err_out, mean_out);
 }
 
 __global__ __launch_bounds__(TB) void k_restrict_bc(int N, const double *__restrict__ D, int M, BcGeom g, double *__restrict__ Fc,
@@ -129,6 +139,18 @@ void gauss_seidel_relative_bc(hipStream_t s, int N, double h2, double inv, doubl
     if (threads > 1024) threads = 1024;          // (n <= 63^2 = 3969 <= GS_PTS * 1024)
     hipLaunchKernelGGL(k_gs_relative_bc, dim3(1), dim3(threads), lds, s, N, bc_geom(N, kind), h2, inv, sd, A, U, F, atol, rtol,
                        max_iters, state, err_out);
+}
+
+void gauss_seidel_relative_bc_mean(hipStream_t s, int N, double h2, double inv, const int *kind, const double *A, double *U,
+                                   const double *F, double atol, double rtol, int max_iters, int *state, double *err_out,
+                                   double *mean_out)
+{
+    const size_t n = (size_t)N * N;
+    const size_t lds = 2 * n * sizeof(double);   // (as gauss_seidel_relative_bc)
+    int threads = (int)((n + 63) / 64 * 64);
+    if (threads > 1024) threads = 1024;
+    hipLaunchKernelGGL(k_gs_relative_bc_mean, dim3(1), dim3(threads), lds, s, N, bc_geom(N, kind), h2, inv, 0.0, A, U, F, atol, rtol,
+                       max_iters, state, err_out, mean_out);
 }
 
 void restrict_bc(hipStream_t s, int N, const int *kind, const double *D, int M, double *Fc, const RestrictTable &t)

@@ -529,6 +529,16 @@ void resnorm_bc(hipStream_t s, int N, double inv, double sd, const int *kind, co
                 double *part, double *out);
 void gauss_seidel_relative_bc(hipStream_t s, int N, double h2, double inv, double sd, const int *kind, const double *A, double *U,
                               const double *F, double atol, double rtol, int max_iters, int *state, double *err_out);
+// the singular problem (include/mg_singular.h; kind: four Neumann sides, sd = 0): the same solve on F minus its weighted mean
+// m_c, which goes to *mean_out (device memory, may be nullptr); F itself is not written
+void gauss_seidel_relative_bc_mean(hipStream_t s, int N, double h2, double inv, const int *kind, const double *A, double *U,
+                                   const double *F, double atol, double rtol, int max_iters, int *state, double *err_out,
+                                   double *mean_out);
+// the weighted mean and the shift of include/mg_singular.h (mg_singular_kernels.hip).  weighted_mean: out[0] = mean_w(X),
+// out[1] = mean_w(X) - target, summed over part (resnorm_partials(N) doubles) in the header's order; shift_by: Xout = Xin - *c
+// (Xout may be Xin)
+void weighted_mean(hipStream_t s, int N, const double *X, double target, double *part, double *out);
+void shift_by(hipStream_t s, int N, const double *Xin, const double *c, double *Xout);
 // Fc (M x M) = the restriction of D (N x N) at the coarse unknowns, +0 at coarse data points; t = restrict_table(N, M)
 void restrict_bc(hipStream_t s, int N, const int *kind, const double *D, int M, double *Fc, const RestrictTable &t);
 // Uout = Uin + P(Uc) at the fine unknowns, Uin at fine data points; lo, w: mg_boundary_prolongation_table(M, N) in device memory
@@ -653,6 +663,8 @@ struct SolveLevels {
 // The operator a hierarchy's levels apply, and with it the kernel family of every operation of the cycle (mg_solve.cpp):
 //   kind set               the `_bc` kernels (include/mg_bc.h) with the level's coefficient or nullptr, restrict_bc and
 //                          prolong_add_bc with the device tables p_lo / p_w; both norms are resnorm_bc
+//     and project_coarse   (include/mg_singular.h: four Neumann sides at shift == 0) the coarse solve is its projecting twin,
+//                          gauss_seidel_relative_bc_mean; every other operation is the line above
 //   no kind, coef set      the `_vc` kernels (include/mg_varcoef.h) on (dx2, sd, omega, coef[l]), restrict_gather(+1) and prolong
 //                          with the cached tables; the norm with U is resnorm_vc, the reference norm ||F|| the constant resnorm
 //   neither                the constant kernels on cw = lc[l].c and lc[l].sh, the same transfers, resnorm
@@ -665,6 +677,7 @@ struct SolveOperator {
     const std::vector<double *> *coef = nullptr;   // per level: the nodal coefficient; nullptr: a = 1
     const std::vector<int *> *p_lo = nullptr;      // per level l < last: mg_boundary_prolongation_table(sizes[l+1], sizes[l])
     const std::vector<double *> *p_w = nullptr;    // in device memory (read only with kind set)
+    bool project_coarse = false;                   // the singular problem (include/mg_singular.h): the coarse solve projects its F
 
     const double *a(int l) const { return coef ? (*coef)[l] : nullptr; }
     // one weighted Jacobi sweep in -> out (in == nullptr: from the zero field)

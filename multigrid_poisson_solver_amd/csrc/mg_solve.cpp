@@ -45,6 +45,14 @@ struct mg_solver {
     int bc[4] = {0, 0, 0, 0};                // S, N, W, E
     std::vector<int *> bc_lo;               // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
     std::vector<double *> bc_w;
+    // the pure Neumann problem (include/mg_singular.h; nothing of it is allocated before the first singular boundary is set).
+    // op.project_coarse says whether the boundary that is set is the singular one
+    bool mean_on = false;                    // mg_solver_set_mean
+    double mean = 0.0;                       // the target of the solution's weighted mean
+    double *sing_F = nullptr;                // Ft = F - c_F, N^2
+    double *sing_scal = nullptr;             // device [4]: c_F, c_F - 0, mean_w(U), mean_w(U) - mean
+    double *sing_host = nullptr;             // pinned [4]
+    double sing_info[3] = {0.0, 0.0, 0.0};   // the last solve's c_F, mean_w(U) before the shift, target
     // Krylov acceleration (include/mg_krylov.h; nothing of it is allocated before the first enabling mg_solver_set_krylov)
     int kr_m = 0;                            // 0: off
     double *kr_r = nullptr;                  // the residual r
@@ -114,6 +122,9 @@ void release(mg_solver *s)
     for (double *p : s->coef) if (p) (void)hipFree(p);
     for (int *p : s->bc_lo) if (p) (void)hipFree(p);
     for (double *p : s->bc_w) if (p) (void)hipFree(p);
+    if (s->sing_F) (void)hipFree(s->sing_F);
+    if (s->sing_scal) (void)hipFree(s->sing_scal);
+    if (s->sing_host) (void)hipHostFree(s->sing_host);
     if (s->coef_flag) (void)hipFree(s->coef_flag);
     if (s->host_coef_flag) (void)hipHostFree(s->host_coef_flag);
     for (auto *v : {&s->kr_Z, &s->kr_Q})
@@ -189,7 +200,10 @@ void mg::SolveOperator::coarse_solve(hipStream_t st, double *U, const double *F,
 {
     const int last = (int)sizes->size() - 1, N = (*sizes)[last];
     const LevelConsts &c = (*lc)[last];
-    if (kind)
+    if (kind && project_coarse)   // (four Neumann sides at shift == 0: c.sd == 0)
+        k::gauss_seidel_relative_bc_mean(st, N, c.dx2, c.inv, kind, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
+                                         gs_state, gs_err, nullptr);
+    else if (kind)
         k::gauss_seidel_relative_bc(st, N, c.dx2, c.inv, c.sd, kind, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
                                     gs_state, gs_err);
     else if (coef)
@@ -419,6 +433,8 @@ void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 // enqueue ||F - AU|| (U == nullptr: ||F||) into dev_scal[slot]
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
+    // (timed for scripts/bench_solve_singular.py, the yardstick of the weighted sum: U, F and, with one, the coefficient)
+    ProfScope ps(U0 ? "resnorm" : "refnorm", s->N, (double)s->N * s->N * (U0 ? (s->op.coef ? 24.0 : 16.0) : 8.0), st);
     s->op.norm(st, U0, F0, s->part, s->dev_scal + slot);
 }
 
@@ -686,6 +702,14 @@ int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_r
     const mg_solve_opts &o = s->o;
     if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
     if (!MG_HIP(hipMemsetAsync(s->gs_state, 0, 4 * sizeof(int), st))) return finish(MG_ERR_HIP);
+    // the singular problem (include/mg_singular.h): everything below works on Ft = F - mean_w(F) in the solver's own buffer
+    const bool singular = s->op.kind && s->op.project_coarse;
+    s->sing_info[0] = s->sing_info[1] = s->sing_info[2] = 0.0;
+    if (singular) {
+        k::weighted_mean(st, s->N, F_dev, 0.0, s->part, s->sing_scal);
+        k::shift_by(st, s->N, F_dev, s->sing_scal + 1, s->sing_F);
+        F_dev = s->sing_F;
+    }
     norm(s, st, F_dev, nullptr, 1);
     norm(s, st, F_dev, U_dev, 0);
     if (!read_back(s, st)) return finish(MG_ERR_HIP);
@@ -710,10 +734,20 @@ int mg_solver_solve(mg_solver *s, const double *F_dev, double *U_dev, mg_solve_r
         r.cycles += 1;
         if (s->host_state[2]) r.coarse_capped = 1;
     }
+    if (singular) {   // the gauge, after the last cycle: U <- U - (mean_w(U) - mean), the constant staying on the device
+        k::weighted_mean(st, s->N, U_dev, s->mean, s->part, s->sing_scal + 2);
+        k::shift_by(st, s->N, U_dev, s->sing_scal + 3, U_dev);
+        if (!MG_HIP(hipMemcpyAsync(s->sing_host, s->sing_scal, 4 * sizeof(double), hipMemcpyDeviceToHost, st))) return finish(MG_ERR_HIP);
+    }
     if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return finish(MG_ERR_HIP);
     float ms = 0.0f;
     if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) r.device_ms = ms;
     if (fmg && *s->host_fmg_capped) r.coarse_capped = 1;
+    if (singular) {   // (the copy was enqueued before ev_end, which has been waited for)
+        s->sing_info[0] = s->sing_host[0];
+        s->sing_info[1] = s->sing_host[2];
+        s->sing_info[2] = s->mean;
+    }
     r.res = res;
     r.converged = res <= tol ? 1 : 0;
     return finish(r.converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED);
@@ -925,6 +959,7 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
     const int neumann = kind[0] + kind[1] + kind[2] + kind[3];
     if (neumann == 0) {   // back to the Dirichlet solver (the tables stay for the next boundary)
         s->op.kind = nullptr;
+        s->op.project_coarse = false;
         for (int i = 0; i < 4; ++i) s->bc[i] = 0;
         return MG_OK;
     }
@@ -938,10 +973,27 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
                                  "kinds", s->kr_m);
         return MG_ERR_UNSUPPORTED;
     }
-    if (neumann == 4 && s->o.shift == 0.0) {
-        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: four Neumann sides with shift == 0 is the singular problem; fixing the "
-                                 "mean and the compatibility projection are not built");
+    const bool singular = neumann == 4 && s->o.shift == 0.0;
+    if (singular && !s->mean_on) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: four Neumann sides with shift == 0 is the singular problem; switch the "
+                                 "mean fixing on first (mg_solver_set_mean, include/mg_singular.h)");
         return MG_ERR_UNSUPPORTED;
+    }
+    if (singular && !s->sing_F) {   // the first singular boundary: the projected right-hand side and the scalars
+        const size_t n0 = (size_t)s->N * s->N;
+        double *f = nullptr, *sc = nullptr, *h = nullptr;
+        if (!dev_alloc(&f, n0) || !dev_alloc(&sc, 4) || !MG_HIP(hipHostMalloc((void **)&h, 4 * sizeof(double), hipHostMallocDefault))) {
+            if (f) (void)hipFree(f);    // the solver keeps what it had
+            if (sc) (void)hipFree(sc);
+            return MG_ERR_HIP;
+        }
+        if (pool_poison_wanted()) {
+            poison_block(f, n0 * sizeof(double));
+            (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+        }
+        s->sing_F = f;
+        s->sing_scal = sc;
+        s->sing_host = h;
     }
     const int nl = (int)s->sizes.size();
     if (s->bc_lo.empty()) {   // the first boundary: the prolongation tables of the hierarchy
@@ -959,6 +1011,7 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
     }
     for (int i = 0; i < 4; ++i) s->bc[i] = kind[i];
     s->op.kind = s->bc;
+    s->op.project_coarse = singular;
     return MG_OK;
 }
 
@@ -967,6 +1020,132 @@ int mg_solver_boundary(const mg_solver *s, int *kind_out)
     if (kind_out)
         for (int i = 0; i < 4; ++i) kind_out[i] = s ? s->bc[i] : 0;
     return s && s->op.kind ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ the pure Neumann problem (include/mg_singular.h)
+int mg_solver_set_mean(mg_solver *s, int on, double mean)
+{
+    if (!require_ready("mg_solver_set_mean")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_solver_set_mean: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (on && !std::isfinite(mean)) {
+        fail(MG_ERR_ARG, "mg_solver_set_mean: mean = %g must be finite", mean);
+        return MG_ERR_ARG;
+    }
+    if (!on && s->op.kind && s->op.project_coarse) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_mean: four Neumann sides with shift == 0 are set, the singular problem, which "
+                                 "needs the mean fixed; set another boundary first");
+        return MG_ERR_UNSUPPORTED;
+    }
+    s->mean_on = on != 0;
+    s->mean = on ? mean : 0.0;
+    return MG_OK;
+}
+
+int mg_solver_mean(const mg_solver *s, double *mean_out)
+{
+    if (mean_out) *mean_out = s ? s->mean : 0.0;
+    return s && s->mean_on ? 1 : 0;
+}
+
+void mg_solver_singular_info(const mg_solver *s, double *out)
+{
+    if (!out) return;
+    for (int i = 0; i < 3; ++i) out[i] = s ? s->sing_info[i] : 0.0;
+}
+
+namespace {
+// X (N x N) and the other device arrays of a building block: N >= 3, non-NULL, 16-byte aligned
+bool mean_args_ok(const char *who, int N, std::initializer_list<const void *> arrays)
+{
+    if (N < 3 || N > 46340) {
+        fail(MG_ERR_ARG, "%s: N = %d outside [3, 46340]", who, N);
+        return false;
+    }
+    for (const void *a : arrays)
+        if (!a || (uintptr_t)a % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: a NULL array, or one that is not 16-byte aligned", who);
+            return false;
+        }
+    return true;
+}
+
+// mean_w(X) -> scalars[32], mean_w(X) - target -> scalars[33] of the engine, enqueued; false without scratch for the partials
+bool enqueue_mean(int N, const double *X, double target, double **part_out)
+{
+    Context &c = ctx();
+    double *part = (double *)scratch_pool().get(k::resnorm_partials(N) * sizeof(double));
+    if (!part) return false;
+    k::weighted_mean(c.stream, N, X, target, part, c.scalars + 32);
+    *part_out = part;
+    return true;
+}
+}  // namespace
+
+void mg_weightedMean(int N, const double *X_dev, double *out_host)
+{
+    if (!require_ready("mg_weightedMean") || !mean_args_ok("mg_weightedMean", N, {X_dev})) return;
+    if (!out_host) {
+        fail(MG_ERR_ARG, "mg_weightedMean: NULL out_host");
+        return;
+    }
+    Context &c = ctx();
+    double *part = nullptr;
+    {
+        ProfScope ps("wsum", N, (double)N * N * 8.0);
+        if (!enqueue_mean(N, X_dev, 0.0, &part)) return;
+    }
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars + 32, c.scalars + 32, sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)))
+        *out_host = c.host_scalars[32];
+    scratch_pool().put(part);
+}
+
+void mg_projectMean(int N, const double *X_in, double mean, double *X_out, double *removed_host)
+{
+    if (!require_ready("mg_projectMean") || !mean_args_ok("mg_projectMean", N, {X_in, X_out})) return;
+    if (!std::isfinite(mean)) {
+        fail(MG_ERR_ARG, "mg_projectMean: mean = %g must be finite", mean);
+        return;
+    }
+    Context &c = ctx();
+    double *part = nullptr;
+    {
+        ProfScope ps("wsum", N, (double)N * N * 8.0);
+        if (!enqueue_mean(N, X_in, mean, &part)) return;
+    }
+    {
+        ProfScope ps("shift", N, (double)N * N * 16.0);
+        k::shift_by(c.stream, N, X_in, c.scalars + 33, X_out);
+    }
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars + 32, c.scalars + 32, sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)) && removed_host)
+        *removed_host = c.host_scalars[32];
+    scratch_pool().put(part);
+}
+
+void mg_coarseSolveMean(int N, double L, const int *kind, const double *a_dev, const double *F, double atol, double rtol,
+                        int max_iters, double *U_out, double *removed_host)
+{
+    if (!require_ready("mg_coarseSolveMean") || !mean_args_ok("mg_coarseSolveMean", N, {F, U_out}) ||
+        !kinds_ok("mg_coarseSolveMean", kind))
+        return;
+    if (kind[0] + kind[1] + kind[2] + kind[3] != 4 || !k::gs_relative_fits(N) || (uintptr_t)a_dev % 16 != 0 || !(L > 0.0) ||
+        !std::isfinite(L) || !(atol >= 0.0) || !(rtol >= 0.0) || !std::isfinite(atol) || !std::isfinite(rtol) || max_iters < 1) {
+        fail(MG_ERR_ARG, "mg_coarseSolveMean: four Neumann sides, 3 <= N = %d < %d, a 16-byte aligned, L > 0, atol, rtol >= 0 and "
+                         "finite, max_iters >= 1", N, k::GS_RELATIVE_MAX_N);
+        return;
+    }
+    Context &c = ctx();
+    const double dx2 = spacing_sq(N, L);
+    if (!MG_HIP(hipMemsetAsync(c.gs_state, 0, 4 * sizeof(int), c.stream))) return;
+    k::gauss_seidel_relative_bc_mean(c.stream, N, dx2, 1.0 / dx2, kind, a_dev, U_out, F, atol, rtol, max_iters, c.gs_state, nullptr,
+                                     c.scalars + 32);
+    if (MG_HIP(hipMemcpyAsync(c.host_scalars + 32, c.scalars + 32, sizeof(double), hipMemcpyDeviceToHost, c.stream)) &&
+        MG_HIP(hipStreamSynchronize(c.stream)) && removed_host)
+        *removed_host = c.host_scalars[32];
 }
 
 void mg_neumannSource(int N, double L, const int *kind, const double *a_dev, const double *F, const double *g, double *F_out)
