@@ -240,6 +240,57 @@ def check_mode_solve(U, info, star, F, L, sigma, bc, lam_min, what, coef=None):
     return float(err / top), float(bound / top)
 
 
+def check_singular_mode_solve(U, info, star, F, L, d, mean, lam_plus, what, coef=None, teeth=1e-6):
+    """A singular solve (four Neumann sides, sigma = 0, include/mg_singular.h) of c*Laplace_h U = F with F = fp64(c*lambda*U*) + d,
+    `star` a mixed_mode of "nnnn" other than (0, 0) in longdouble: its weighted mean vanishes, so the answer with the target
+    `mean` is X = fp64(U*) + mean whatever the incompatibility d.  check_mode_solve cannot serve, its lam_min is 0 for this
+    kind.  diag(w)*A is symmetric, so A is self-adjoint in the w-inner product, and on the w-orthogonal complement of the
+    constants ||A^-1||_w <= 1/lam_plus, lam_plus the smallest non-zero eigenvalue of -A (c times that of mode (0, 1));
+    ||x||_w <= ||x||_2 <= 2||x||_w as in check_mode_solve, and the component of U - X along the constants is the difference
+    of the two weighted means:
+
+        max|U - X| <= 2*(||r(U)||_2 + ||r(X)||_2) / lam_plus + |mean_w(U) - mean_w(X)|
+
+    both residuals in longdouble against Ft = F - mean_w(F), the fp64 array the solver itself works on
+    (_singular_ref.project_mean), the means in longdouble.  Also: compat_defect is the restatement's mean_w(F), bit for bit,
+    and within gamma(N^2)*mean_w(|F|) of d; teeth: the bound is at most teeth*max|U*|; converged; the reported res within
+    _bc_ref.residual_rounding_bound of ||r(U)||_2; mean_w(U) within gamma(N^2)*mean_w(|U|) + 2u|mean| of the target.
+    info: the solver's, or for the restatement dict(compat_defect, converged, cycles) without res (that line is left out).
+    Returns (error, bound), relative to max|U*|."""
+    import _bc_ref as bref
+    import _singular_ref as sing
+    bc = "nnnn"
+    n = F.shape[0] * F.shape[0]
+    Ft, c_F = sing.project_mean(F)
+    X = r64(star) + float(mean)
+    rU, rX, mU, mX, mF = together(lambda: bref.residual_ld_stencil(coef, U, Ft, L, 0.0, bc), lambda: bref.residual_ld_stencil(coef, X, Ft, L, 0.0, bc),
+                                  lambda: (sing.weighted_mean_ld(U), sing.weighted_mean_ld(np.abs(U))), lambda: sing.weighted_mean_ld(X),
+                                  lambda: sing.weighted_mean_ld(np.abs(F)))
+    mU, mabsU = mU
+    print(f"{what}: compat_defect {info['compat_defect']!r} for d = {d!r}, |difference| {abs(info['compat_defect'] - d):.3e} <= {float(sing.gamma(n) * mF):.3e}")
+    assert info["compat_defect"] == c_F, f"{what}: compat_defect {info['compat_defect']!r} is not the restatement's mean_w(F) = {c_F!r}"
+    assert abs(LD(info["compat_defect"]) - LD(d)) <= sing.gamma(n) * mF, f"{what}: compat_defect {info['compat_defect']!r} for d = {d!r}"
+    nU, nX = np.sqrt(np.sum(rU ** 2)), np.sqrt(np.sum(rX ** 2))
+    err = np.max(np.abs(np.asarray(U, dtype=LD) - X.astype(LD)))
+    gauge = abs(mU - mX)
+    bound = 2 * (nU + nX) / LD(lam_plus) + gauge
+    top = np.max(np.abs(star))
+    print(f"{what}: |U - X| {float(err):.3e} <= {float(bound):.3e} (relative {float(err / top):.2e} <= {float(bound / top):.2e}), "
+          f"r(U) {float(nU):.3e}, r(X) {float(nX):.3e}, gauge term {float(gauge):.3e}, {info['cycles']} cycles")
+    assert err <= bound, f"{what}: max|U - X| = {float(err):.6e} above {float(bound):.6e}"
+    assert bound <= LD(teeth) * top, f"{what}: no teeth: bound {float(bound):.3e} against max|U*| = {float(top):.3e}"
+    assert info["converged"], f"{what}: not converged after {info['cycles']} cycles"
+    if "res" in info:
+        a = None if coef is None else np.full(F.shape, float(coef))
+        R = bref.residual_rounding_bound(a, U, Ft, L, 0.0, bc, r=rU)
+        print(f"{what}: res {info['res']:.6e} vs {float(nU):.6e} (bound {float(R):.3e})")
+        assert abs(LD(info["res"]) - nU) <= R, f"{what}: res {info['res']!r} is not the residual of U, {float(nU)!r}"
+    slack = sing.gamma(n) * mabsU + 2 * U53 * abs(LD(mean))
+    print(f"{what}: |mean_w(U) - mean| {float(abs(mU - LD(mean))):.3e} <= {float(slack):.3e}")
+    assert abs(mU - LD(mean)) <= slack, f"{what}: mean_w(U) = {float(mU)!r} for the target {mean!r}"
+    return float(err / top), float(bound / top)
+
+
 class Perturbed:
     """u_0 = P + A*m, Q = -nu*Laplace(P) (steady=False: P = 0 and no Q, pure decay).  .U0 and .Q are the fp64 arrays a stepper
     is given (.Q None without P); exact(n) is u_n in longdouble; bound(n, rtol) is the a-priori bound on ||U_n - u_n||_2 of
