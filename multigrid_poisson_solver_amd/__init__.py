@@ -264,6 +264,17 @@ ABI_SINGULAR = {
     "mg_coarseSolveMean": (None, [_i, _d, _vp, _vp, _vp, _d, _d, _i, _vp, _vp]),
 }
 
+# the symbols include/mg_reaction.h declares (the solver with a variable reaction term, div(a grad U) - (sigma + s)*U = F);
+# bound like ABI_FMG: a library without them still loads, Solver.set_reaction() / applyOperatorReaction() / ... then raise
+ABI_REACTION = {
+    "mg_solver_set_reaction": (_i, [_vp, _vp]),
+    "mg_solver_has_reaction": (_i, [_vp]),
+    "mg_applyOperatorReaction": (None, [_i, _d, _d, _vp, _vp, _vp, _vp]),
+    "mg_sweepReaction": (None, [_i, _d, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "mg_residualReaction": (None, [_i, _d, _d, _vp, _vp, _vp, _vp, _vp, _i]),
+    "mg_coarseSolveReaction": (None, [_i, _d, _d, _vp, _vp, _vp, _d, _d, _i, _vp]),
+}
+
 # the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
 # ABI_FMG: a library without it still loads, solve_cycle() then raises
 ABI_SOLVE_CYCLE = {
@@ -329,7 +340,8 @@ def load_library(path=None):
         raise MGError(f"{path} does not export: {missing}")
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
-            list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()):
+            list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()) + \
+            list(ABI_REACTION.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -711,6 +723,41 @@ def residualCoefficient(N, L, shift, a, U, F, D, sign=1):
     """Test hook (include/mg_varcoef.h).  mg_residualCoefficient on DeviceGrids: D = sign*(inv*b(U) - F) inside, sign*0 on the rim."""
     _need_vc("mg_residualCoefficient")(N, L, shift, a.ptr, U.ptr, F.ptr, D.ptr, sign)
     _check()
+
+
+def _need_reaction(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the reaction term)")
+    return getattr(_lib, name)
+
+
+def applyOperatorReaction(N, L, shift, a, s, U, out):
+    """mg_applyOperatorReaction on DeviceGrids: out = inv*b(U) of div(a grad U) - (shift + s)*U inside, +0 on the rim
+    (include/mg_reaction.h); a = None is a = 1."""
+    _need_reaction("mg_applyOperatorReaction")(N, L, shift, _opt(a), s.ptr, U.ptr, out.ptr)
+    _check()
+
+
+def sweepReaction(N, L, shift, omega, a, s, U_in, F, U_out):
+    """Test hook (include/mg_reaction.h).  mg_sweepReaction on DeviceGrids: one weighted Jacobi sweep of the operator with the
+    reaction term s (U_in = None: from zero; a = None: a = 1)."""
+    _need_reaction("mg_sweepReaction")(N, L, shift, omega, _opt(a), s.ptr, _opt(U_in), F.ptr, U_out.ptr)
+    _check()
+
+
+def residualReaction(N, L, shift, a, s, U, F, D, sign=1):
+    """Test hook (include/mg_reaction.h).  mg_residualReaction on DeviceGrids: D = sign*(inv*b(U) - F) inside, sign*0 on the rim."""
+    _need_reaction("mg_residualReaction")(N, L, shift, _opt(a), s.ptr, U.ptr, F.ptr, D.ptr, sign)
+    _check()
+
+
+def coarseSolveReaction(N, L, shift, a, s, F, atol, rtol, max_iters, U_out):
+    """Test hook (include/mg_reaction.h).  The coarse solve alone on DeviceGrids: U_out = the red-black solve from zero on F
+    with the reaction term s, N <= 63, a = None is a = 1.  Returns the iterations."""
+    _need_reaction("mg_coarseSolveReaction")(int(N), float(L), float(shift), _opt(a), s.ptr, F.ptr, float(atol), float(rtol),
+                                             int(max_iters), U_out.ptr)
+    _check()
+    return lastExactSolverIterations()
 
 
 def _need_bc(name):
@@ -1321,8 +1368,9 @@ def _coefficient_address(N, a, keep):
     return g.ptr
 
 
-def _set_coefficient(fn, handle, N, a):
-    """The argument handling of Solver.set_coefficient and HeatStepper.set_coefficient: fn(handle, device address of a) with a
+def _set_coefficient(fn, handle, N, a, what="coef"):
+    """The argument handling of Solver.set_coefficient, Solver.set_reaction and HeatStepper.set_coefficient (`what` names the
+    array in messages): fn(handle, device address of a) with a
     an N x N numpy array (uploaded for the call), a DeviceGrid, or a float64 torch CUDA tensor (read on
     torch.cuda.current_stream()); None takes the coefficient away.  A refusal raises MGError."""
     if a is None:
@@ -1332,7 +1380,7 @@ def _set_coefficient(fn, handle, N, a):
     if _is_torch(a):
         import torch
         if not (a.is_cuda and a.dtype == torch.float64 and tuple(a.shape) == (N, N) and a.is_contiguous()):
-            raise MGError(f"coef: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            raise MGError(f"{what}: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
         prev = _lib.mg_get_stream()
         _lib.mg_set_stream(torch.cuda.current_stream(a.device).cuda_stream)
         try:
@@ -1341,12 +1389,12 @@ def _set_coefficient(fn, handle, N, a):
             _lib.mg_set_stream(prev)
     elif hasattr(a, "ptr") and hasattr(a, "shape"):
         if tuple(a.shape) != (N, N):
-            raise MGError(f"coef: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+            raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
         status = fn(handle, a.ptr)
     else:
         a = np.asarray(a, dtype=np.float64)
         if a.shape != (N, N):
-            raise MGError(f"coef: array of shape {a.shape}, expected ({N}, {N})")
+            raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
         g = DeviceGrid.from_host(a)
         try:
             status = fn(handle, g.ptr)
@@ -1376,11 +1424,17 @@ class Solver:
     mean=m (or set_mean(m)) opens the pure Neumann problem, bc="nnnn" at shift == 0 (include/mg_singular.h): the solve removes
     the weighted mean of F (info["compat_defect"]: what the data lacked in compatibility), runs the cycles with a projected
     coarse solve, and returns the solution whose weighted mean is m (info["mean_before"]: what it was before that shift).
-    With any other boundary or shift the setting is dormant."""
+    With any other boundary or shift the setting is dormant.
+    reaction=s (or set_reaction(s)) solves div(a grad U) - (sigma + s)*U = F with s >= 0 given at the grid points
+    (include/mg_reaction.h), with or without coef: the linearised Poisson-Boltzmann equation, a Newton step with s = g'(u), an
+    absorbing region.  s == 0 everywhere is the solver without it, s == c at shift == 0 the solver with shift=c, bit for bit.
+    A discontinuous or strongly varying s slows the plain cycle down; krylov=m is supported with it and is what to use then.
+    Refused together with fmg, a Neumann side and adjoint()."""
 
     def __init__(self, N, L=1.0, coef=None, krylov=0, **opts):
         bc = opts.pop("bc", None)   # (the boundary kinds travel beside the solve options, not in mg_solve_opts)
         mean = opts.pop("mean", None)
+        reaction = opts.pop("reaction", None)
         self.N, self.L = int(N), float(L)
         self.opts = solve_opts(**opts)
         self._s = lib().mg_solver_create(self.N, self.L, C.byref(self.opts))
@@ -1390,6 +1444,8 @@ class Solver:
         try:
             if coef is not None:
                 self.set_coefficient(coef)
+            if reaction is not None:
+                self.set_reaction(reaction)
             if krylov:
                 self.set_krylov(krylov)
             if mean is not None:
@@ -1459,6 +1515,20 @@ class Solver:
     @property
     def has_coefficient(self):
         return bool(_need_vc("mg_solver_has_coefficient")(self._s))
+
+    def set_reaction(self, s):
+        """s: N x N values of the reaction term at the grid points, rim included, finite and >= 0 (numpy array, DeviceGrid or
+        float64 torch CUDA tensor, which is read on torch.cuda.current_stream()); None: the solver without it, enqueueing what
+        it enqueued before.  The centre of the operator becomes d = aN + aS + aE + aW + (sigma + s[p])*dx2; coarse levels sample
+        s as they sample a (include/mg_reaction.h).  s is copied: it may be freed after the call.  Works with and without a
+        coefficient and with krylov, in any order.  A refusal (MGError) leaves the solver as it was: "[2]" a negative or not
+        finite value, a misaligned array; "[3]" a solver created with fmg != 0, a Neumann side set.  While a reaction is set,
+        set_boundary with a Neumann side and adjoint() are refused."""
+        _set_coefficient(_need_reaction("mg_solver_set_reaction"), self._s, self.N, s, what="reaction")
+
+    @property
+    def has_reaction(self):
+        return bool(_need_reaction("mg_solver_has_reaction")(self._s))
 
     def set_boundary(self, bc):
         """bc: the four kinds in the order S, N, W, E (row 0, row N-1, column 0, column N-1), a sequence of DIRICHLET (0) /
@@ -1643,7 +1713,9 @@ def solve(F, U=None, L=1.0, **opts):
     bc=kinds makes sides Neumann (Solver.set_boundary): four kinds in the order S, N, W, E (row 0, row N-1, column 0, column
     N-1), e.g. "ndnd"; on Neumann sides the rim of U is part of the guess and is written.
     bc="nnnn" with mean=m at shift == 0 is the pure Neumann problem (Solver.set_mean): F is projected onto the compatible
-    right-hand sides and the solution returned has the weighted mean m."""
+    right-hand sides and the solution returned has the weighted mean m.
+    reaction=s (N x N, >= 0, at the grid points) solves div(a grad U) - (sigma + s)*U = F (Solver.set_reaction,
+    include/mg_reaction.h), with or without coef; with a discontinuous s add krylov=m."""
     N = int(F.shape[0])
     s = Solver(N, L, **opts)
     try:

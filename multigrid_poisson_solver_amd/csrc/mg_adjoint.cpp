@@ -208,6 +208,10 @@ int mg_solver_adjoint(mg_solver *s, const double *Ubar, const double *U, double 
         fail(MG_ERR_UNSUPPORTED, "mg_solver_adjoint: a boundary with a Neumann side is set; the adjoint is not built for boundary kinds");
         return refuse(MG_ERR_UNSUPPORTED);
     }
+    if (mg_solver_has_reaction(s)) {   // (include/mg_reaction.h: no gradient in s is built, the rest is not offered without it)
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_adjoint: a reaction term is set; the adjoint is not built for a reaction");
+        return refuse(MG_ERR_UNSUPPORTED);
+    }
     double L = 1.0;
     const int N = solver_size(s, &L);
     const double *coef = solver_coefficient(s);   // (the solver's own level-0 array: what the solve itself reads)

@@ -549,6 +549,21 @@ void neumann_source(hipStream_t s, int N, double t, const int *kind, const doubl
 // the heat right-hand side at the unknowns, +0 at data points (c.lap == false: no neighbour and no coefficient is read)
 void heat_rhs_bc(hipStream_t s, int N, const HeatConsts &c, const int *kind, const double *A, const double *U, const double *Q,
                  double *F);
+// the residual-tolerance solver with a variable reaction term (mg_reaction_kernels.hip, driven by mg_solve.cpp; the expressions
+// and their order: include/mg_reaction.h).  The `_vc` launchers above with the centre's shift term formed per point, sd + S*dx2:
+// S is the level's nodal reaction term, A its coefficient or nullptr (a = 1 through the same expressions, nothing streamed
+// for it); every launcher takes dx2 beside inv for that product.
+void wjacobi_rx(hipStream_t s, int N, double dx2, double sd, double omega, const double *A, const double *S, const double *in,
+                const double *F, double *out);
+void residual_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U,
+                 const double *F, double *D, int sign);
+void apply_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U, double *out);
+void resnorm_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U,
+                const double *F, double *part, double *out);
+void gauss_seidel_relative_rx(hipStream_t s, int N, double h2, double inv, double sd, const double *A, const double *S, double *U,
+                              const double *F, double atol, double rtol, int max_iters, int *state, double *err_out);
+// *flag = 1 when a value of S[0..n) is not finite or not >= 0 (the caller zeroes the flag)
+void reaction_check(hipStream_t s, const double *S, size_t n, int *flag);
 // Krylov acceleration of the residual-tolerance solver (mg_krylov_kernels.hip, driven by mg_solve.cpp; the method and the
 // order of every operation: include/mg_krylov.h).  All sums run over the interior; no rim is read into a result or written.
 constexpr int KRYLOV_MAX_K = MG_KRYLOV_MAX_M - 1;   // stored directions an iteration orthogonalises against
@@ -665,9 +680,12 @@ struct SolveLevels {
 //                          prolong_add_bc with the device tables p_lo / p_w; both norms are resnorm_bc
 //     and project_coarse   (include/mg_singular.h: four Neumann sides at shift == 0) the coarse solve is its projecting twin,
 //                          gauss_seidel_relative_bc_mean; every other operation is the line above
-//   no kind, coef set      the `_vc` kernels (include/mg_varcoef.h) on (dx2, sd, omega, coef[l]), restrict_gather(+1) and prolong
+//   no kind, react set     the `_rx` kernels (include/mg_reaction.h) on (dx2, sd, omega, coef[l] or nullptr, react[l]), with or
+//                          without a coefficient; the transfers and the reference norm of the next line, the norm with U is
+//                          resnorm_rx.  (A kind and a reaction are never set together: the setters refuse it.)
+//   neither of them, coef  the `_vc` kernels (include/mg_varcoef.h) on (dx2, sd, omega, coef[l]), restrict_gather(+1) and prolong
 //                          with the cached tables; the norm with U is resnorm_vc, the reference norm ||F|| the constant resnorm
-//   neither                the constant kernels on cw = lc[l].c and lc[l].sh, the same transfers, resnorm
+//   none of the three      the constant kernels on cw = lc[l].c and lc[l].sh, the same transfers, resnorm
 // Every pointer is its owner's; l is a level of the hierarchy, N = sizes[l].  All members enqueue on st.
 struct SolveOperator {
     const mg_solve_opts *o;
@@ -678,8 +696,10 @@ struct SolveOperator {
     const std::vector<int *> *p_lo = nullptr;      // per level l < last: mg_boundary_prolongation_table(sizes[l+1], sizes[l])
     const std::vector<double *> *p_w = nullptr;    // in device memory (read only with kind set)
     bool project_coarse = false;                   // the singular problem (include/mg_singular.h): the coarse solve projects its F
+    const std::vector<double *> *react = nullptr;  // per level: the nodal reaction term; nullptr: none (checked before coef)
 
     const double *a(int l) const { return coef ? (*coef)[l] : nullptr; }
+    const double *s(int l) const { return react ? (*react)[l] : nullptr; }
     // one weighted Jacobi sweep in -> out (in == nullptr: from the zero field)
     void sweep(hipStream_t st, int l, const double *in, const double *F, double *out) const;
     // D = -(AU - F)
@@ -692,7 +712,7 @@ struct SolveOperator {
     void prolong_add(hipStream_t st, int l, const double *Uc, const double *Uin, double *Uout) const;
     // *out = ||F - AU|| at level 0 (U == nullptr: the reference norm ||F||); part: resnorm_partials(N) doubles
     void norm(hipStream_t st, const double *U, const double *F, double *part, double *out) const;
-    // out = AU at level 0 for the Krylov acceleration, which boundary kinds refuse: apply_vc whatever the family
+    // out = AU at level 0 for the Krylov acceleration, which boundary kinds refuse: apply_rx with a reaction, else apply_vc
     void apply(hipStream_t st, const double *U, double *out) const;
 };
 // One V(pre, post) cycle as data: its launches in order, each naming the level arrays it reads and writes

@@ -41,6 +41,11 @@ struct mg_solver {
     std::vector<double *> coef;              // per level: the nodal coefficient a_l
     int *coef_flag = nullptr;                // device: the check found a value that is not finite or not > 0
     int *host_coef_flag = nullptr;           // pinned
+    // variable reaction term (include/mg_reaction.h; nothing of it is allocated before the first mg_solver_set_reaction);
+    // op.react is &react, or nullptr: none is set
+    std::vector<double *> react;             // per level: the nodal reaction term s_l
+    int *react_flag = nullptr;               // device: the check found a value that is negative or not finite
+    int *host_react_flag = nullptr;          // pinned
     // boundary kinds per side (include/mg_bc.h; nothing of it is allocated before the first Neumann side is set)
     int bc[4] = {0, 0, 0, 0};                // S, N, W, E
     std::vector<int *> bc_lo;               // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
@@ -125,6 +130,9 @@ void release(mg_solver *s)
     if (s->sing_F) (void)hipFree(s->sing_F);
     if (s->sing_scal) (void)hipFree(s->sing_scal);
     if (s->sing_host) (void)hipHostFree(s->sing_host);
+    for (double *p : s->react) if (p) (void)hipFree(p);
+    if (s->react_flag) (void)hipFree(s->react_flag);
+    if (s->host_react_flag) (void)hipHostFree(s->host_react_flag);
     if (s->coef_flag) (void)hipFree(s->coef_flag);
     if (s->host_coef_flag) (void)hipHostFree(s->host_coef_flag);
     for (auto *v : {&s->kr_Z, &s->kr_Q})
@@ -176,6 +184,7 @@ void mg::SolveOperator::sweep(hipStream_t st, int l, const double *in, const dou
     const int N = (*sizes)[l];
     const LevelConsts &c = (*lc)[l];
     if (kind) k::wjacobi_bc(st, N, c.dx2, c.sd, o->omega, kind, a(l), in, F, out);
+    else if (react) k::wjacobi_rx(st, N, c.dx2, c.sd, o->omega, a(l), s(l), in, F, out);
     else if (coef) k::wjacobi_vc(st, N, c.dx2, c.sd, o->omega, a(l), in, F, out);
     else k::wjacobi(st, N, c.dx2, c.c, in, F, out, c.sh);
 }
@@ -185,6 +194,7 @@ void mg::SolveOperator::residual(hipStream_t st, int l, const double *U, const d
     const int N = (*sizes)[l];
     const LevelConsts &c = (*lc)[l];
     if (kind) k::residual_bc(st, N, c.inv, c.sd, kind, a(l), U, F, D, -1);
+    else if (react) k::residual_rx(st, N, c.dx2, c.inv, c.sd, a(l), s(l), U, F, D, -1);
     else if (coef) k::residual_vc(st, N, c.inv, c.sd, a(l), U, F, D, -1);
     else k::residual(st, N, c.inv, U, F, D, -1, c.sh);
 }
@@ -206,6 +216,9 @@ void mg::SolveOperator::coarse_solve(hipStream_t st, double *U, const double *F,
     else if (kind)
         k::gauss_seidel_relative_bc(st, N, c.dx2, c.inv, c.sd, kind, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
                                     gs_state, gs_err);
+    else if (react)
+        k::gauss_seidel_relative_rx(st, N, c.dx2, c.inv, c.sd, a(last), s(last), U, F, o->coarse_atol, o->coarse_rtol,
+                                    o->coarse_max_iters, gs_state, gs_err);
     else if (coef)
         k::gauss_seidel_relative_vc(st, N, c.dx2, c.inv, c.sd, a(last), U, F, o->coarse_atol, o->coarse_rtol, o->coarse_max_iters,
                                     gs_state, gs_err);
@@ -224,13 +237,16 @@ void mg::SolveOperator::norm(hipStream_t st, const double *U, const double *F, d
     const int N = (*sizes)[0];
     const LevelConsts &c = (*lc)[0];
     if (kind) k::resnorm_bc(st, N, c.inv, c.sd, kind, a(0), U, F, part, out);   // both norms run over the unknowns
+    else if (react && U) k::resnorm_rx(st, N, c.dx2, c.inv, c.sd, a(0), s(0), U, F, part, out);
     else if (coef && U) k::resnorm_vc(st, N, c.inv, c.sd, a(0), U, F, part, out);
     else k::resnorm(st, N, c.inv, U, F, part, out, c.sh);   // (the reference norm ||F|| has no operator in it)
 }
 
 void mg::SolveOperator::apply(hipStream_t st, const double *U, double *out) const
 {
-    k::apply_vc(st, (*sizes)[0], (*lc)[0].inv, (*lc)[0].sd, a(0), U, out);
+    const LevelConsts &c = (*lc)[0];
+    if (react) k::apply_rx(st, (*sizes)[0], c.dx2, c.inv, c.sd, a(0), s(0), U, out);
+    else k::apply_vc(st, (*sizes)[0], c.inv, c.sd, a(0), U, out);
 }
 
 // ------------------------------------------------------------------ the recorded cycle (mg_internal.h: SolveCycle)
@@ -386,11 +402,11 @@ int mg::solver_size(const mg_solver *s, double *L)
 namespace {
 
 // one cycle from level `top`: through the fused nodes of the streaming smoother (its weighted instantiations), which are the
-// constant operator's -- a boundary kind or a coefficient goes operator by operator whatever mg_set_smoother says (top == 0
-// with either: the full-multigrid start excludes both)
+// constant operator's -- a boundary kind, a coefficient or a reaction goes operator by operator whatever mg_set_smoother says
+// (top == 0 with any of them: the full-multigrid start excludes all three)
 void vcycle(mg_solver *s, hipStream_t st, const double *F0, double *U0, int top = 0)
 {
-    const bool fused = !(s->op.kind || s->op.coef || ctx().smoother == SMOOTHER_SIMPLE);
+    const bool fused = !(s->op.kind || s->op.coef || s->op.react || ctx().smoother == SMOOTHER_SIMPLE);
     (void)run_solve_cycle(st, s->cyc[fused][top], s->lv, s->op, F0, U0);
 }
 
@@ -434,7 +450,7 @@ void fmg_start(mg_solver *s, hipStream_t st, const double *F0, double *U0)
 void norm(mg_solver *s, hipStream_t st, const double *F0, const double *U0, int slot)
 {
     // (timed for scripts/bench_solve_singular.py, the yardstick of the weighted sum: U, F and, with one, the coefficient)
-    ProfScope ps(U0 ? "resnorm" : "refnorm", s->N, (double)s->N * s->N * (U0 ? (s->op.coef ? 24.0 : 16.0) : 8.0), st);
+    ProfScope ps(U0 ? "resnorm" : "refnorm", s->N, (double)s->N * s->N * (U0 ? 16.0 + (s->op.coef ? 8.0 : 0.0) + (s->op.react ? 8.0 : 0.0) : 8.0), st);
     s->op.norm(st, U0, F0, s->part, s->dev_scal + slot);
 }
 
@@ -883,7 +899,10 @@ void mg_sweepCoefficient(int N, double L, double shift, double omega, const doub
         return;
     }
     const double dx2 = spacing_sq(N, L);
-    k::wjacobi_vc(ctx().stream, N, dx2, shift * dx2, omega, a_dev, U_in, F, U_out);
+    {
+        ProfScope ps("wjacobi_vc", N, (double)N * N * 32.0);   // (the yardstick of scripts/bench_solve_reaction.py)
+        k::wjacobi_vc(ctx().stream, N, dx2, shift * dx2, omega, a_dev, U_in, F, U_out);
+    }
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
 }
 
@@ -896,6 +915,135 @@ void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, 
         k::residual_vc(ctx().stream, N, 1.0 / dx2, shift * dx2, a_dev, U, F, D, sign < 0 ? -1 : +1);
     }
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+// ------------------------------------------------------------------ variable reaction term (include/mg_reaction.h)
+int mg_solver_set_reaction(mg_solver *s, const double *s_dev)
+{
+    if (!require_ready("mg_solver_set_reaction")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_solver_set_reaction: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (!s_dev) {   // the solver without a reaction again (the level storage stays for the next one)
+        s->op.react = nullptr;
+        return MG_OK;
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_reaction: the solver was created with fmg = %d; the full-multigrid start is not "
+                                 "built for a reaction term", s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (s->op.kind) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_reaction: a boundary with a Neumann side is set; a reaction together with boundary "
+                                 "kinds is not built");
+        return MG_ERR_UNSUPPORTED;
+    }
+    if ((uintptr_t)s_dev % 16 != 0) {
+        fail(MG_ERR_ARG, "mg_solver_set_reaction: s must be 16-byte aligned");
+        return MG_ERR_ARG;
+    }
+    const hipStream_t st = ctx().stream;
+    const int nl = (int)s->sizes.size();
+    if (s->react.empty()) {   // the first reaction: level storage, about 4/3 N^2 doubles
+        s->react.assign(nl, nullptr);
+        bool ok = dev_alloc(&s->react_flag, 1) && MG_HIP(hipHostMalloc((void **)&s->host_react_flag, sizeof(int), hipHostMallocDefault));
+        for (int l = 0; l < nl && ok; ++l) ok = dev_alloc(&s->react[l], (size_t)s->sizes[l] * s->sizes[l]);
+        if (!ok) {   // (the next call starts over)
+            for (double *&p : s->react) if (p) { (void)hipFree(p); p = nullptr; }
+            s->react.clear();
+            if (s->react_flag) { (void)hipFree(s->react_flag); s->react_flag = nullptr; }
+            if (s->host_react_flag) { (void)hipHostFree(s->host_react_flag); s->host_react_flag = nullptr; }
+            return MG_ERR_HIP;
+        }
+    }
+    // the check comes first and reads the CALLER's array: a refused reaction leaves the solver's own untouched
+    const size_t n0 = (size_t)s->N * s->N;
+    if (!MG_HIP(hipMemsetAsync(s->react_flag, 0, sizeof(int), st))) return MG_ERR_HIP;
+    k::reaction_check(st, s_dev, n0, s->react_flag);
+    if (!MG_HIP(hipMemcpyAsync(s->host_react_flag, s->react_flag, sizeof(int), hipMemcpyDeviceToHost, st)) ||
+        !MG_HIP(hipStreamSynchronize(st)))
+        return MG_ERR_HIP;
+    if (*s->host_react_flag) {
+        fail(MG_ERR_ARG, "mg_solver_set_reaction: every value of s must be finite and >= 0 (a negative or not finite value found)");
+        return MG_ERR_ARG;
+    }
+    // from here on the level storage is overwritten: until it is whole again the solver has NO reaction
+    s->op.react = nullptr;
+    if (!MG_HIP(hipMemcpyAsync(s->react[0], s_dev, n0 * sizeof(double), hipMemcpyDeviceToDevice, st))) return MG_ERR_HIP;
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen(st, s->sizes[l], s->react[l], s->sizes[l + 1], s->react[l + 1], restrict_table(s->sizes[l], s->sizes[l + 1]));
+    if (!MG_HIP(hipStreamSynchronize(st))) return MG_ERR_HIP;   // (the caller may free s, or solve on another stream)
+    s->op.react = &s->react;
+    return MG_OK;
+}
+
+int mg_solver_has_reaction(const mg_solver *s) { return s && s->op.react ? 1 : 0; }
+
+namespace {
+// the optional coefficient of a reaction hook: NULL, or 16-byte aligned
+bool rx_coef_ok(const char *who, const double *a_dev)
+{
+    if ((uintptr_t)a_dev % 16 == 0) return true;
+    fail(MG_ERR_ARG, "%s: a must be 16-byte aligned", who);
+    return false;
+}
+}  // namespace
+
+void mg_applyOperatorReaction(int N, double L, double shift, const double *a_dev, const double *s_dev, const double *U, double *out)
+{
+    if (!require_ready("mg_applyOperatorReaction") || !vc_args_ok("mg_applyOperatorReaction", N, L, shift, {s_dev, U, out}) ||
+        !rx_coef_ok("mg_applyOperatorReaction", a_dev))
+        return;
+    const double dx2 = spacing_sq(N, L);
+    k::apply_rx(ctx().stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U, out);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_sweepReaction(int N, double L, double shift, double omega, const double *a_dev, const double *s_dev, const double *U_in,
+                      const double *F, double *U_out)
+{
+    if (!require_ready("mg_sweepReaction") || !vc_args_ok("mg_sweepReaction", N, L, shift, {s_dev, F, U_out}) ||
+        !rx_coef_ok("mg_sweepReaction", a_dev))
+        return;
+    if ((uintptr_t)U_in % 16 != 0 || !(omega > 0.0 && omega <= 1.0)) {
+        fail(MG_ERR_ARG, "mg_sweepReaction: U_in must be 16-byte aligned, omega = %g inside (0, 1]", omega);
+        return;
+    }
+    const double dx2 = spacing_sq(N, L);
+    {
+        ProfScope ps(a_dev ? "wjacobi_rx_a" : "wjacobi_rx", N, (double)N * N * (a_dev ? 40.0 : 32.0));   // (scripts/bench_solve_reaction.py)
+        k::wjacobi_rx(ctx().stream, N, dx2, shift * dx2, omega, a_dev, s_dev, U_in, F, U_out);
+    }
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_residualReaction(int N, double L, double shift, const double *a_dev, const double *s_dev, const double *U, const double *F,
+                         double *D, int sign)
+{
+    if (!require_ready("mg_residualReaction") || !vc_args_ok("mg_residualReaction", N, L, shift, {s_dev, U, F, D}) ||
+        !rx_coef_ok("mg_residualReaction", a_dev))
+        return;
+    const double dx2 = spacing_sq(N, L);
+    k::residual_rx(ctx().stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U, F, D, sign < 0 ? -1 : +1);
+    (void)MG_HIP(hipStreamSynchronize(ctx().stream));
+}
+
+void mg_coarseSolveReaction(int N, double L, double shift, const double *a_dev, const double *s_dev, const double *F, double atol,
+                            double rtol, int max_iters, double *U_out)
+{
+    if (!require_ready("mg_coarseSolveReaction") || !vc_args_ok("mg_coarseSolveReaction", N, L, shift, {s_dev, F, U_out}) ||
+        !rx_coef_ok("mg_coarseSolveReaction", a_dev))
+        return;
+    if (!k::gs_relative_fits(N) || !(atol >= 0.0) || !(rtol >= 0.0) || !std::isfinite(atol) || !std::isfinite(rtol) || max_iters < 1) {
+        fail(MG_ERR_ARG, "mg_coarseSolveReaction: 3 <= N = %d < %d, atol, rtol >= 0 and finite, max_iters >= 1", N, k::GS_RELATIVE_MAX_N);
+        return;
+    }
+    Context &c = ctx();
+    const double dx2 = spacing_sq(N, L);
+    if (!MG_HIP(hipMemsetAsync(c.gs_state, 0, 4 * sizeof(int), c.stream))) return;
+    k::gauss_seidel_relative_rx(c.stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U_out, F, atol, rtol, max_iters, c.gs_state, nullptr);
+    (void)MG_HIP(hipStreamSynchronize(c.stream));
 }
 
 // ------------------------------------------------------------------ boundary kinds per side (include/mg_bc.h)
@@ -971,6 +1119,11 @@ int mg_solver_set_boundary(mg_solver *s, const int *kind)
     if (s->kr_m > 0) {
         fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: the Krylov acceleration is on (m = %d); it is not built for boundary "
                                  "kinds", s->kr_m);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (s->op.react) {
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_set_boundary: a reaction term is set; a Neumann side together with a reaction is not "
+                                 "built (include/mg_reaction.h)");
         return MG_ERR_UNSUPPORTED;
     }
     const bool singular = neumann == 4 && s->o.shift == 0.0;
