@@ -275,6 +275,32 @@ ABI_REACTION = {
     "mg_coarseSolveReaction": (None, [_i, _d, _d, _vp, _vp, _vp, _d, _d, _i, _vp]),
 }
 
+# the symbols include/mg_newton.h declares (the semilinear problem div(a grad U) - sigma*U - kappa*w*g(U) = F, Newton around the
+# solver); bound like ABI_FMG: a library without them still loads, Solver.newton() / nonlinear_residual() / ... then raise
+class NewtonOpts(C.Structure):
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_iters", C.c_int), ("max_backtracks", C.c_int)]
+
+
+class NewtonResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("n_history", C.c_int),
+                ("res0", C.c_double), ("res", C.c_double), ("inner_cycles", C.c_int), ("trials", C.c_int)]
+
+
+class NewtonIter(C.Structure):
+    _fields_ = [("res", C.c_double), ("t", C.c_double), ("backtracks", C.c_int), ("inner_cycles", C.c_int),
+                ("inner_converged", C.c_int), ("inner_capped", C.c_int)]
+
+
+ABI_NEWTON = {
+    "mg_newton_opts_default": (None, [C.POINTER(NewtonOpts)]),
+    "mg_solver_newton": (_i, [_vp, _i, _d, _vp, _vp, _vp, C.POINTER(NewtonOpts), C.POINTER(NewtonResult)]),
+    "mg_solver_newton_history": (_i, [_vp, C.POINTER(NewtonIter), _i]),
+    "mg_solver_newton_inner_history": (_i, [_vp, _vp, _i]),
+    "mg_nonlinearResidual": (_i, [_i, _d, _d, _vp, _i, _d, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+}
+NEWTON_KINDS = {"cubic": 0, "sinh": 1, "exp": 2}
+NEWTON_CONVERGED, NEWTON_NOT_CONVERGED, NEWTON_STALLED = 0, -1, -2
+
 # the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
 # ABI_FMG: a library without it still loads, solve_cycle() then raises
 ABI_SOLVE_CYCLE = {
@@ -341,7 +367,7 @@ def load_library(path=None):
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
             list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()) + \
-            list(ABI_REACTION.items()):
+            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -758,6 +784,35 @@ def coarseSolveReaction(N, L, shift, a, s, F, atol, rtol, max_iters, U_out):
                                              int(max_iters), U_out.ptr)
     _check()
     return lastExactSolverIterations()
+
+
+def _need_newton(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name} (a build without the semilinear solve)")
+    return getattr(_lib, name)
+
+
+def _newton_kind(kind):
+    if kind in NEWTON_KINDS:
+        return NEWTON_KINDS[kind]
+    if isinstance(kind, str):
+        raise MGError(f"kind {kind!r}: expected one of {sorted(NEWTON_KINDS)}")
+    return int(kind)   # (a number goes to the library, which refuses one it does not know)
+
+
+def nonlinear_residual(N, L, shift, a, kind, kappa, w, U, F, D, S, dlt=None, t=1.0, V=None):
+    """The pass of the semilinear solve on DeviceGrids (include/mg_newton.h: mg_nonlinearResidual), the building block of
+    Solver.newton: with v = U (dlt = None) or v = U + t*dlt inside and U on the rim (written to V), S = kappa*w*g'(v) on every
+    point, D = (F + kappa*w*g(v)) - A v inside and +0 on the rim, where A v = div(a grad v) - shift*v; returns
+    sqrt(sum of D^2) in the order of the solver's residual norm.  a = None: a = 1; w = None: w = 1; kind: "cubic", "sinh"
+    or "exp".  D is the right-hand side and S the reaction of the Newton equation, Solver(..., reaction=S).solve(D)."""
+    out = C.c_double(0.0)
+    status = _need_newton("mg_nonlinearResidual")(int(N), float(L), float(shift), _opt(a), _newton_kind(kind), float(kappa), _opt(w),
+                                                  U.ptr, _opt(dlt), float(t), F.ptr, _opt(V), D.ptr, S.ptr, C.byref(out))
+    if status:
+        _check()
+        raise MGError(f"mg_nonlinearResidual failed with status {status}")
+    return float(out.value)
 
 
 def _need_bc(name):
@@ -1429,7 +1484,9 @@ class Solver:
     (include/mg_reaction.h), with or without coef: the linearised Poisson-Boltzmann equation, a Newton step with s = g'(u), an
     absorbing region.  s == 0 everywhere is the solver without it, s == c at shift == 0 the solver with shift=c, bit for bit.
     A discontinuous or strongly varying s slows the plain cycle down; krylov=m is supported with it and is what to use then.
-    Refused together with fmg, a Neumann side and adjoint()."""
+    Refused together with fmg, a Neumann side and adjoint().
+    newton(F, U, kind=..., kappa=..., weight=w) solves the semilinear problem div(a grad U) - sigma*U - kappa*w*g(U) = F by
+    Newton's method around this solver (include/mg_newton.h); it sets and removes a reaction of its own."""
 
     def __init__(self, N, L=1.0, coef=None, krylov=0, **opts):
         bc = opts.pop("bc", None)   # (the boundary kinds travel beside the solve options, not in mg_solve_opts)
@@ -1612,6 +1669,79 @@ class Solver:
         info = self.solve_ptr(Fd.ptr, Ud.ptr)
         return (Ud.to_host() if host_U else Ud), info
 
+    def newton_ptr(self, F_ptr, U_ptr, kind="sinh", kappa=1.0, w_ptr=None, rtol=1e-8, atol=0.0, max_iters=20, max_backtracks=12):
+        """mg_solver_newton on device addresses of N x N fp64 arrays (U in/out, w_ptr = None: w = 1), on the engine stream."""
+        fn = _need_newton("mg_solver_newton")
+        o = NewtonOpts(float(rtol), float(atol), int(max_iters), int(max_backtracks))
+        res = NewtonResult()
+        status = fn(self._s, _newton_kind(kind), float(kappa), w_ptr, F_ptr, U_ptr, C.byref(o), C.byref(res))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_solver_newton failed with status {status}")
+        recs = (NewtonIter * max(res.n_history, 1))()
+        n = _lib.mg_solver_newton_history(self._s, recs, res.n_history)
+        iters = [dict(res=r.res, t=r.t, backtracks=r.backtracks, inner_cycles=r.inner_cycles,
+                      inner_converged=bool(r.inner_converged), inner_capped=bool(r.inner_capped)) for r in recs[:n]]
+        return dict(status=res.status, iterations=res.iterations, converged=bool(res.converged), stalled=res.status == NEWTON_STALLED,
+                    res0=res.res0, res=res.res, inner_cycles=res.inner_cycles, trials=res.trials,
+                    history=[res.res0] + [r["res"] for r in iters[:res.iterations]], steps=iters,
+                    last_inner_history=self._inner_history() if iters else [])
+
+    def _inner_history(self):
+        n = _lib.mg_solver_newton_inner_history(self._s, None, 0)
+        buf = np.zeros(max(n, 1))
+        got = _lib.mg_solver_newton_inner_history(self._s, buf.ctypes.data, n)
+        return [float(v) for v in buf[:got]]
+
+    def newton(self, F, U=None, kind="sinh", kappa=1.0, weight=None, rtol=1e-8, atol=0.0, max_iters=20, max_backtracks=12):
+        """Solve the semilinear problem div(a grad U) - sigma*U - kappa*w*g(U) = F by Newton's method with a backtracking line
+        search around this solver (include/mg_newton.h): g = u^3 ("cubic"), sinh u ("sinh") or e^u ("exp"), kappa >= 0,
+        weight = w >= 0 at the grid points (None: w = 1), a and sigma the solver's coefficient and shift, Dirichlet values on
+        the rim of U.  Every Newton step is one solve of this solver with the reaction kappa*w*g'(U), to the solver's own
+        rtol / atol / max_cycles (with krylov if it is on); the outer iteration stops at ||N(U)|| <= max(atol, rtol*||N(U_0)||),
+        after max_iters accepted steps, or when max_backtracks halvings of a step do not lower the norm (info["stalled"]).
+        F, U, weight: numpy arrays, DeviceGrids or float64 torch CUDA tensors, as solve() takes them.  Returns (U, info);
+        info["history"] holds the norms, info["steps"] one dict per iteration (res, t, backtracks, inner_cycles,
+        inner_converged, inner_capped).  Refused ("[3]") while a reaction or a Neumann side is set and with fmg; the solver
+        has no reaction afterwards, as before."""
+        N = self.N
+        opts = dict(kind=kind, kappa=kappa, rtol=rtol, atol=atol, max_iters=max_iters, max_backtracks=max_backtracks)
+        if _is_torch(F) or _is_torch(U) or _is_torch(weight):
+            import torch
+            if U is None:
+                U = torch.zeros((N, N), dtype=torch.float64, device=F.device)
+            for name, t in (("F", F), ("U", U)) + ((("weight", weight),) if weight is not None else ()):
+                if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (N, N)
+                        and t.is_contiguous()):
+                    raise MGError(f"{name}: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            prev = _lib.mg_get_stream()
+            _lib.mg_set_stream(torch.cuda.current_stream(F.device).cuda_stream)
+            try:
+                info = self.newton_ptr(F.data_ptr(), U.data_ptr(), w_ptr=None if weight is None else weight.data_ptr(), **opts)
+            finally:
+                _lib.mg_set_stream(prev)
+            return U, info
+        keep = []
+
+        def dev(a, what):
+            if isinstance(a, DeviceGrid):
+                if a.shape != (N, N):
+                    raise MGError(f"{what}: DeviceGrid of shape {a.shape}, expected ({N}, {N})")
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (N, N):
+                raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+            g = DeviceGrid.from_host(a)
+            keep.append(g)
+            return g
+
+        Fd = dev(F, "F")
+        wd = None if weight is None else dev(weight, "weight")
+        host_U = U is None or not isinstance(U, DeviceGrid)
+        Ud = DeviceGrid.zeros((N, N)) if U is None else dev(U, "U")
+        info = self.newton_ptr(Fd.ptr, Ud.ptr, w_ptr=None if wd is None else wd.ptr, **opts)
+        return (Ud.to_host() if host_U else Ud), info
+
     def adjoint_ptr(self, Ubar_ptr, U_ptr, lam_ptr, gA_ptr=None, gU_ptr=None):
         """mg_solver_adjoint on device addresses of N x N fp64 arrays, on the engine stream: lam (out) = the adjoint field of
         the right-hand side Ubar, gA (out, or None) = the gradient in the coefficient from lam and the forward solution U,
@@ -1720,6 +1850,25 @@ def solve(F, U=None, L=1.0, **opts):
     s = Solver(N, L, **opts)
     try:
         return s.solve(F, U)
+    finally:
+        s.close()
+
+
+def solve_semilinear(F, U=None, L=1.0, kind="sinh", kappa=1.0, weight=None, coef=None, krylov=0, rtol=1e-8, atol=0.0, max_iters=20,
+                     max_backtracks=12, inner_rtol=None, inner_atol=None, **opts):
+    """Solve div(a grad U) - sigma*U - kappa*w*g(U) = F on the N x N grid of F (Dirichlet values on U's rim) by Newton's method
+    around the multigrid solver (Solver.newton, include/mg_newton.h); returns (U, info).  kind, kappa, weight, rtol, atol,
+    max_iters and max_backtracks are the Newton iteration's; coef, krylov and **opts (shift, max_cycles, omega, ...) make the
+    Solver every Newton step runs on, inner_rtol / inner_atol being that Solver's rtol / atol (the forcing term; None: the
+    Solver's defaults).  With a discontinuous weight add krylov=m."""
+    N = int(F.shape[0])
+    for name, v in (("rtol", inner_rtol), ("atol", inner_atol)):
+        if v is not None:
+            opts[name] = v
+    s = Solver(N, L, coef=coef, krylov=krylov, **opts)
+    try:
+        return s.newton(F, U, kind=kind, kappa=kappa, weight=weight, rtol=rtol, atol=atol, max_iters=max_iters,
+                        max_backtracks=max_backtracks)
     finally:
         s.close()
 

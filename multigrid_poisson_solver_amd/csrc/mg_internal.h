@@ -564,6 +564,13 @@ void gauss_seidel_relative_rx(hipStream_t s, int N, double h2, double inv, doubl
                               const double *F, double atol, double rtol, int max_iters, int *state, double *err_out);
 // *flag = 1 when a value of S[0..n) is not finite or not >= 0 (the caller zeroes the flag)
 void reaction_check(hipStream_t s, const double *S, size_t n, int *flag);
+// the pass of the semilinear solve (mg_newton_kernels.hip, driven by mg_solve.cpp; the expressions and their order:
+// include/mg_newton.h): V = U + t*dlt (dlt == nullptr: no step, V not written), S = kappa*W*g'(V) on all N^2 points,
+// D = (F + kappa*W*g(V)) - inv*b(V) inside and +0 on the rim, *out = sqrt(sum of D^2) in the partition and order of resnorm
+// (part: resnorm_partials(N)).  kind: MG_NEWTON_*; A, W: nullptr for a = 1, w = 1, nothing streamed for either.
+void newton_residual(hipStream_t s, int N, double inv, double sd, int kind, double kappa, const double *A, const double *W,
+                     const double *U, const double *dlt, double t, const double *F, double *V, double *D, double *S, double *part,
+                     double *out);
 // Krylov acceleration of the residual-tolerance solver (mg_krylov_kernels.hip, driven by mg_solve.cpp; the method and the
 // order of every operation: include/mg_krylov.h).  All sums run over the interior; no rim is read into a result or written.
 constexpr int KRYLOV_MAX_K = MG_KRYLOV_MAX_M - 1;   // stored directions an iteration orthogonalises against

@@ -46,6 +46,9 @@ struct mg_solver {
     std::vector<double *> react;             // per level: the nodal reaction term s_l
     int *react_flag = nullptr;               // device: the check found a value that is negative or not finite
     int *host_react_flag = nullptr;          // pinned
+    // semilinear driver (include/mg_newton.h; nothing of it is allocated before the first mg_solver_newton)
+    double *nw_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // V, D, D', S', delta: N^2 doubles each
+    std::vector<mg_newton_iter> nw_hist;     // the last call's iterations
     // boundary kinds per side (include/mg_bc.h; nothing of it is allocated before the first Neumann side is set)
     int bc[4] = {0, 0, 0, 0};                // S, N, W, E
     std::vector<int *> bc_lo;               // per level l < last: mg_boundary_prolongation_table(N_{l+1}, N_l) on the device
@@ -131,6 +134,7 @@ void release(mg_solver *s)
     if (s->sing_scal) (void)hipFree(s->sing_scal);
     if (s->sing_host) (void)hipHostFree(s->sing_host);
     for (double *p : s->react) if (p) (void)hipFree(p);
+    for (double *p : s->nw_buf) if (p) (void)hipFree(p);
     if (s->react_flag) (void)hipFree(s->react_flag);
     if (s->host_react_flag) (void)hipHostFree(s->host_react_flag);
     if (s->coef_flag) (void)hipFree(s->coef_flag);
@@ -918,6 +922,26 @@ void mg_residualCoefficient(int N, double L, double shift, const double *a_dev, 
 }
 
 // ------------------------------------------------------------------ variable reaction term (include/mg_reaction.h)
+namespace {
+// the reaction's level storage, about 4/3 N^2 doubles, and the flag of its check: allocated by the first call that needs them
+// (mg_solver_set_reaction, mg_solver_newton) and reused; false on a HIP error (the next call starts over)
+bool react_storage(mg_solver *s)
+{
+    if (!s->react.empty()) return true;
+    const int nl = (int)s->sizes.size();
+    s->react.assign(nl, nullptr);
+    bool ok = dev_alloc(&s->react_flag, 1) && MG_HIP(hipHostMalloc((void **)&s->host_react_flag, sizeof(int), hipHostMallocDefault));
+    for (int l = 0; l < nl && ok; ++l) ok = dev_alloc(&s->react[l], (size_t)s->sizes[l] * s->sizes[l]);
+    if (!ok) {
+        for (double *&p : s->react) if (p) { (void)hipFree(p); p = nullptr; }
+        s->react.clear();
+        if (s->react_flag) { (void)hipFree(s->react_flag); s->react_flag = nullptr; }
+        if (s->host_react_flag) { (void)hipHostFree(s->host_react_flag); s->host_react_flag = nullptr; }
+    }
+    return ok;
+}
+}  // namespace
+
 int mg_solver_set_reaction(mg_solver *s, const double *s_dev)
 {
     if (!require_ready("mg_solver_set_reaction")) return MG_ERR_NOT_INIT;
@@ -945,18 +969,7 @@ int mg_solver_set_reaction(mg_solver *s, const double *s_dev)
     }
     const hipStream_t st = ctx().stream;
     const int nl = (int)s->sizes.size();
-    if (s->react.empty()) {   // the first reaction: level storage, about 4/3 N^2 doubles
-        s->react.assign(nl, nullptr);
-        bool ok = dev_alloc(&s->react_flag, 1) && MG_HIP(hipHostMalloc((void **)&s->host_react_flag, sizeof(int), hipHostMallocDefault));
-        for (int l = 0; l < nl && ok; ++l) ok = dev_alloc(&s->react[l], (size_t)s->sizes[l] * s->sizes[l]);
-        if (!ok) {   // (the next call starts over)
-            for (double *&p : s->react) if (p) { (void)hipFree(p); p = nullptr; }
-            s->react.clear();
-            if (s->react_flag) { (void)hipFree(s->react_flag); s->react_flag = nullptr; }
-            if (s->host_react_flag) { (void)hipHostFree(s->host_react_flag); s->host_react_flag = nullptr; }
-            return MG_ERR_HIP;
-        }
-    }
+    if (!react_storage(s)) return MG_ERR_HIP;
     // the check comes first and reads the CALLER's array: a refused reaction leaves the solver's own untouched
     const size_t n0 = (size_t)s->N * s->N;
     if (!MG_HIP(hipMemsetAsync(s->react_flag, 0, sizeof(int), st))) return MG_ERR_HIP;
@@ -1025,7 +1038,10 @@ void mg_residualReaction(int N, double L, double shift, const double *a_dev, con
         !rx_coef_ok("mg_residualReaction", a_dev))
         return;
     const double dx2 = spacing_sq(N, L);
-    k::residual_rx(ctx().stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U, F, D, sign < 0 ? -1 : +1);
+    {
+        ProfScope ps(a_dev ? "residual_rx_a" : "residual_rx", N, (double)N * N * (a_dev ? 40.0 : 32.0));   // (the yardstick of scripts/bench_newton.py)
+        k::residual_rx(ctx().stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U, F, D, sign < 0 ? -1 : +1);
+    }
     (void)MG_HIP(hipStreamSynchronize(ctx().stream));
 }
 
@@ -1044,6 +1060,212 @@ void mg_coarseSolveReaction(int N, double L, double shift, const double *a_dev, 
     if (!MG_HIP(hipMemsetAsync(c.gs_state, 0, 4 * sizeof(int), c.stream))) return;
     k::gauss_seidel_relative_rx(c.stream, N, dx2, 1.0 / dx2, shift * dx2, a_dev, s_dev, U_out, F, atol, rtol, max_iters, c.gs_state, nullptr);
     (void)MG_HIP(hipStreamSynchronize(c.stream));
+}
+
+// ------------------------------------------------------------------ semilinear problem (include/mg_newton.h)
+namespace {
+bool newton_kind_ok(const char *who, int kind, double kappa)
+{
+    if (kind != MG_NEWTON_CUBIC && kind != MG_NEWTON_SINH && kind != MG_NEWTON_EXP) {
+        fail(MG_ERR_ARG, "%s: unknown kind %d (MG_NEWTON_CUBIC = 0, MG_NEWTON_SINH = 1, MG_NEWTON_EXP = 2)", who, kind);
+        return false;
+    }
+    if (!(kappa >= 0.0) || !finite(kappa)) {
+        fail(MG_ERR_ARG, "%s: kappa = %g must be finite and >= 0", who, kappa);
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+void mg_newton_opts_default(mg_newton_opts *o)
+{
+    if (!o) return;
+    o->rtol = 1e-8;
+    o->atol = 0.0;
+    o->max_iters = 20;
+    o->max_backtracks = 12;
+}
+
+int mg_solver_newton(mg_solver *s, int kind, double kappa, const double *w_dev, const double *F_dev, double *U_dev,
+                     const mg_newton_opts *opts, mg_newton_result *out)
+{
+    const char *who = "mg_solver_newton";
+    mg_newton_result r;
+    std::memset(&r, 0, sizeof r);
+    auto finish = [&](int status) {
+        r.status = status;
+        r.n_history = s ? (int)s->nw_hist.size() : 0;
+        if (out) *out = r;
+        return status;
+    };
+    if (!require_ready(who)) return finish(MG_ERR_NOT_INIT);
+    if (!s || !F_dev || !U_dev) {
+        fail(MG_ERR_ARG, "%s: NULL solver or array", who);
+        return finish(MG_ERR_ARG);
+    }
+    if (s->op.react) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the driver installs the Newton matrix's own (take yours away with "
+                                 "mg_solver_set_reaction(NULL), or put it into w)", who);
+        return finish(MG_ERR_UNSUPPORTED);
+    }
+    if (s->op.kind) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a boundary with a Neumann side is set; the semilinear solve is built for Dirichlet sides", who);
+        return finish(MG_ERR_UNSUPPORTED);
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "%s: the solver was created with fmg = %d; the full-multigrid start is not built for a reaction term",
+             who, s->o.fmg);
+        return finish(MG_ERR_UNSUPPORTED);
+    }
+    if (!newton_kind_ok(who, kind, kappa)) return finish(MG_ERR_ARG);
+    if (((uintptr_t)F_dev | (uintptr_t)U_dev | (uintptr_t)w_dev) % 16 != 0) {
+        fail(MG_ERR_ARG, "%s: F, U and w must be 16-byte aligned", who);
+        return finish(MG_ERR_ARG);
+    }
+    mg_newton_opts o;
+    mg_newton_opts_default(&o);
+    if (opts) o = *opts;
+    if (!(o.rtol >= 0.0) || !(o.atol >= 0.0) || !std::isfinite(o.rtol) || !std::isfinite(o.atol) || o.max_iters < 0 || o.max_backtracks < 0) {
+        fail(MG_ERR_ARG, "%s: rtol = %g, atol = %g (non-negative, finite), max_iters = %d, max_backtracks = %d (>= 0 each)", who, o.rtol,
+             o.atol, o.max_iters, o.max_backtracks);
+        return finish(MG_ERR_ARG);
+    }
+    const hipStream_t st = ctx().stream;
+    const int N = s->N, nl = (int)s->sizes.size();
+    const size_t n0 = (size_t)N * N;
+    if (!react_storage(s)) return finish(MG_ERR_HIP);
+    for (double *&p : s->nw_buf)
+        if (!p && !dev_alloc(&p, n0)) return finish(MG_ERR_HIP);
+    if (w_dev) {   // one launch, a flag, one read-back, as mg_solver_set_reaction checks s
+        if (!MG_HIP(hipMemsetAsync(s->react_flag, 0, sizeof(int), st))) return finish(MG_ERR_HIP);
+        k::reaction_check(st, w_dev, n0, s->react_flag);
+        if (!MG_HIP(hipMemcpyAsync(s->host_react_flag, s->react_flag, sizeof(int), hipMemcpyDeviceToHost, st)) ||
+            !MG_HIP(hipStreamSynchronize(st)))
+            return finish(MG_ERR_HIP);
+        if (*s->host_react_flag) {
+            fail(MG_ERR_ARG, "%s: every value of w must be finite and >= 0 (a negative or not finite value found)", who);
+            return finish(MG_ERR_ARG);
+        }
+    }
+    s->nw_hist.clear();
+    const LevelConsts &c0 = s->lc[0];
+    const double *A = s->op.a(0);
+    // cur holds the last accepted iterate, D its right-hand side and react[0] its S; oth, D2 and S2 take the next trial.
+    // U_dev is one of (cur, oth): when the call ends on the other one, the iterate is copied home.
+    double *cur = U_dev, *oth = s->nw_buf[0], *D = s->nw_buf[1], *D2 = s->nw_buf[2], *dlt = s->nw_buf[4];
+    double *&S2 = s->nw_buf[3];
+    auto home = [&]() {
+        s->op.react = nullptr;
+        if (cur == U_dev) return true;
+        return MG_HIP(hipMemcpyAsync(U_dev, cur, n0 * sizeof(double), hipMemcpyDeviceToDevice, st)) && MG_HIP(hipStreamSynchronize(st));
+    };
+    k::newton_residual(st, N, c0.inv, c0.sd, kind, kappa, A, w_dev, cur, nullptr, 0.0, F_dev, nullptr, D, s->react[0], s->part, s->dev_scal);
+    if (!read_back(s, st)) return finish(MG_ERR_HIP);
+    double rn = s->host_scal[0];
+    if (!std::isfinite(rn)) {
+        fail(MG_ERR_ARG, "%s: the residual of the start is not finite (%g)", who, rn);
+        return finish(MG_ERR_ARG);
+    }
+    r.res0 = r.res = rn;
+    const double tol = std::fmax(o.atol, o.rtol * rn);
+    bool stalled = false;
+    while (!(rn <= tol) && r.iterations < o.max_iters) {
+        for (int l = 0; l + 1 < nl; ++l)
+            k::coef_coarsen(st, s->sizes[l], s->react[l], s->sizes[l + 1], s->react[l + 1], restrict_table(s->sizes[l], s->sizes[l + 1]));
+        if (!MG_HIP(hipMemsetAsync(dlt, 0, n0 * sizeof(double), st))) {
+            (void)home();
+            return finish(MG_ERR_HIP);
+        }
+        s->op.react = &s->react;
+        mg_solve_result in;
+        const int in_status = mg_solver_solve(s, D, dlt, &in);
+        s->op.react = nullptr;
+        if (in_status > 0) {
+            (void)home();
+            return finish(in_status);
+        }
+        mg_newton_iter it{rn, 0.0, 0, in.cycles, in.converged, in.coarse_capped};
+        r.inner_cycles += in.cycles;
+        double t = 1.0;
+        bool accepted = false;
+        for (;;) {
+            k::newton_residual(st, N, c0.inv, c0.sd, kind, kappa, A, w_dev, cur, dlt, t, F_dev, oth, D2, S2, s->part, s->dev_scal);
+            r.trials += 1;
+            if (!read_back(s, st)) {
+                (void)home();
+                return finish(MG_ERR_HIP);
+            }
+            const double rt = s->host_scal[0];
+            if (std::isfinite(rt) && rt < (1.0 - 1e-4 * t) * rn) {
+                std::swap(cur, oth);
+                std::swap(D, D2);
+                std::swap(s->react[0], S2);
+                rn = rt;
+                it.res = rt;
+                it.t = t;
+                accepted = true;
+                break;
+            }
+            it.backtracks += 1;
+            if (it.backtracks > o.max_backtracks) break;
+            t *= 0.5;
+        }
+        s->nw_hist.push_back(it);
+        if (!accepted) {
+            stalled = true;
+            break;
+        }
+        r.iterations += 1;
+    }
+    if (!home()) return finish(MG_ERR_HIP);
+    r.res = rn;
+    r.converged = rn <= tol ? 1 : 0;
+    return finish(r.converged ? MG_NEWTON_CONVERGED : stalled ? MG_NEWTON_STALLED : MG_NEWTON_NOT_CONVERGED);
+}
+
+int mg_solver_newton_history(const mg_solver *s, mg_newton_iter *out, int cap)
+{
+    if (!s) return 0;
+    const int n = (int)s->nw_hist.size();
+    for (int i = 0; out && i < n && i < cap; ++i) out[i] = s->nw_hist[i];
+    return n;
+}
+
+int mg_solver_newton_inner_history(const mg_solver *s, double *out, int cap)
+{
+    if (!s) return 0;
+    const int n = (int)s->history.size();
+    for (int i = 0; out && i < n && i < cap; ++i) out[i] = s->history[i];
+    return n;
+}
+
+int mg_nonlinearResidual(int N, double L, double shift, const double *a_dev, int kind, double kappa, const double *w_dev,
+                         const double *U, const double *dlt, double t, const double *F, double *V, double *D, double *S, double *norm_out)
+{
+    const char *who = "mg_nonlinearResidual";
+    if (!require_ready(who)) return MG_ERR_NOT_INIT;
+    if (!vc_args_ok(who, N, L, shift, {U, F, D, S}) || !rx_coef_ok(who, a_dev) || !newton_kind_ok(who, kind, kappa)) return MG_ERR_ARG;
+    if (((uintptr_t)w_dev | (uintptr_t)dlt | (uintptr_t)V) % 16 != 0 || (dlt && (!V || !std::isfinite(t)))) {
+        fail(MG_ERR_ARG, "%s: w, dlt and V must be 16-byte aligned; with dlt, V must be there and t = %g finite", who, t);
+        return MG_ERR_ARG;
+    }
+    const hipStream_t st = ctx().stream;
+    const size_t np = k::resnorm_partials(N);
+    const double dx2 = spacing_sq(N, L), pts = (double)N * N;
+    double *buf = nullptr;   // the partials and, behind them, the norm
+    if (!dev_alloc(&buf, np + 1)) return MG_ERR_HIP;
+    {
+        // (timed for scripts/bench_newton.py: U, F in, D, S out, + a, + w, + dlt in and V out)
+        ProfScope ps(dlt ? "newton_step" : "newton_residual", N, pts * (32.0 + (a_dev ? 8.0 : 0.0) + (w_dev ? 8.0 : 0.0) + (dlt ? 16.0 : 0.0)));
+        k::newton_residual(st, N, 1.0 / dx2, shift * dx2, kind, kappa, a_dev, w_dev, U, dlt, t, F, dlt ? V : nullptr, D, S, buf, buf + np);
+    }
+    double host = 0.0;
+    const bool ok = MG_HIP(hipMemcpyAsync(&host, buf + np, sizeof(double), hipMemcpyDeviceToHost, st)) && MG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(buf);
+    if (!ok) return MG_ERR_HIP;
+    if (norm_out) *norm_out = host;
+    return MG_OK;
 }
 
 // ------------------------------------------------------------------ boundary kinds per side (include/mg_bc.h)
