@@ -33,7 +33,8 @@
  * What a reaction refuses (MG_ERR_UNSUPPORTED, the solver stays as it was): a solver created with fmg != 0; a boundary with
  * a Neumann side, in either order (mg_solver_set_reaction while one is set, mg_solver_set_boundary while a reaction is set) --
  * the combination would also give Robin sides and is not built; mg_solver_adjoint while a reaction is set.  The batched
- * solver, the heat stepper and the eigensolver have no reaction.
+ * solver takes one reaction term per instance, or one shared, through mg_rx_batch.h, every instance bit-identical to this
+ * solver on it alone; the heat stepper and the eigensolver have no reaction.
  *
  * Memory contract (mg_hip.h): every function below reads its const arrays and writes its output array and nothing else.
  * Device arrays are 16-byte aligned.

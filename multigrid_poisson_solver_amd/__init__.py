@@ -275,6 +275,13 @@ ABI_REACTION = {
     "mg_coarseSolveReaction": (None, [_i, _d, _d, _vp, _vp, _vp, _d, _d, _i, _vp]),
 }
 
+# the symbols include/mg_rx_batch.h declares (the batched solver with a reaction term per instance, or one shared); bound like
+# ABI_VC_BATCH: a library without them still loads, BatchSolver.set_reaction() / solve_batched_reaction() then raise
+ABI_RX_BATCH = {
+    "mg_batch_solver_set_reaction": (_i, [_vp, _i, _vp]),
+    "mg_batch_solver_has_reaction": (_i, [_vp]),
+}
+
 # the symbols include/mg_newton.h declares (the semilinear problem div(a grad U) - sigma*U - kappa*w*g(U) = F, Newton around the
 # solver); bound like ABI_FMG: a library without them still loads, Solver.newton() / nonlinear_residual() / ... then raise
 class NewtonOpts(C.Structure):
@@ -367,7 +374,7 @@ def load_library(path=None):
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
             list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()) + \
-            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()):
+            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()) + list(ABI_RX_BATCH.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -1911,7 +1918,10 @@ class BatchSolver:
     instance bit-identical to Solver(coef=a_i) on it alone (include/mg_varcoef_batch.h):
         b = BatchSolver(N, L, max_batch=B); b.set_coefficient(a); U, infos = b.solve(F, U0); b.set_coefficient(None)
     set_krylov(m) wraps the cycle of every instance in restarted GCR(m) (include/mg_krylov_batch.h), every instance
-    bit-identical to Solver(krylov=m) on it alone: for coefficients on which the plain cycle crawls or diverges."""
+    bit-identical to Solver(krylov=m) on it alone: for coefficients on which the plain cycle crawls or diverges.
+    set_reaction(s) solves div(a_i grad U_i) - (sigma + s_i)*U_i = F_i, one reaction term per instance or one shared by all,
+    with or without a coefficient and with set_krylov, every instance bit-identical to Solver(reaction=s_i, coef=a_i) on it
+    alone (include/mg_rx_batch.h)."""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -1930,7 +1940,10 @@ class BatchSolver:
         everywhere is the solver without a coefficient, bit for bit.  The arrays are copied: they may be freed after the
         call.  A refused coefficient (MGError "[2] ...": a wrong shape, more than max_batch coefficients, a bad value, whose
         instance the message names) leaves the solver as it was."""
-        fn = _need_vc_batch("mg_batch_solver_set_coefficient")
+        self._set_arrays(_need_vc_batch("mg_batch_solver_set_coefficient"), "mg_batch_solver_set_coefficient", a, "coef", "coefficient")
+
+    def _set_arrays(self, fn, name, a, what, noun):
+        """the argument handling of set_coefficient and set_reaction: fn(handle, n, the device addresses of the n arrays)"""
         if a is None:
             status = fn(self._s, 0, None)
         else:
@@ -1942,9 +1955,9 @@ class BatchSolver:
             elif len(a.shape) == 2:
                 items = [a]
             else:
-                raise MGError(f"[2] coef: expected (N, N), (n, N, N) or a sequence of (N, N) arrays, got shape {tuple(a.shape)}")
+                raise MGError(f"[2] {what}: expected (N, N), (n, N, N) or a sequence of (N, N) arrays, got shape {tuple(a.shape)}")
             if not items:
-                raise MGError("[2] coef: an empty sequence (None takes the coefficient away)")
+                raise MGError(f"[2] {what}: an empty sequence (None takes the {noun} away)")
             keep, prev = [], None
             torch_item = next((t for t in items if _is_torch(t)), None)
             try:
@@ -1955,7 +1968,7 @@ class BatchSolver:
                 try:
                     ptrs = [_coefficient_address(N, t, keep) for t in items]
                 except MGError as e:   # (a wrong shape or type is an argument error like the library's own: code 2)
-                    raise MGError(f"[2] {e}") from None
+                    raise MGError("[2] " + str(e).replace("coef:", what + ":", 1)) from None
                 status = fn(self._s, len(ptrs), (C.c_void_p * len(ptrs))(*ptrs))
             finally:
                 if torch_item is not None:
@@ -1964,7 +1977,7 @@ class BatchSolver:
                     g.free()
         if status:
             _check()
-            raise MGError(f"mg_batch_solver_set_coefficient failed with status {status}")
+            raise MGError(f"{name} failed with status {status}")
 
     @property
     def has_coefficient(self):
@@ -1975,6 +1988,31 @@ class BatchSolver:
     def n_coefficients(self):
         """0 without a coefficient, 1 with one shared by every instance, else the number of per-instance coefficients."""
         return int(_need_vc_batch("mg_batch_solver_has_coefficient")(self._s))
+
+    def set_reaction(self, s):
+        """s of shape (N, N): one reaction term shared by every instance (one copy is stored).  s of shape (n, N, N), or a
+        sequence of n (N, N) arrays, DeviceGrids or tensors, n <= max_batch: instance i of a solve uses s[i], and a solve
+        then takes at most n instances.  None: the solver without a reaction again, enqueueing what it enqueued before.
+        Values at the grid points, rim included, finite and >= 0; numpy arrays, DeviceGrids or float64 torch CUDA tensors
+        (read on torch.cuda.current_stream()), as set_coefficient takes them.  Every instance then solves
+        div(a_i grad U_i) - (sigma + s_i)*U_i = F_i as Solver(reaction=s[i], coef=a_i) solves it alone, bit for bit (U,
+        history, cycles, flags), with set_krylov(m) as Solver(krylov=m, reaction=s[i], coef=a_i); s == 0 everywhere is the
+        solver without a reaction, s == c at shift 0 is BatchSolver(shift=c), bit for bit.  The count is independent of the
+        coefficient's (a shared a with per-instance s, and so on), and set_coefficient, set_reaction and set_krylov work in
+        any order.  The arrays are copied: they may be freed after the call.  A refused reaction (MGError "[2] ...": a wrong
+        shape, more than max_batch terms, a negative or not finite value, whose instance the message names) leaves the solver
+        as it was.  While a reaction is set, adjoint() is refused ("[3]")."""
+        self._set_arrays(_need_rx_batch("mg_batch_solver_set_reaction"), "mg_batch_solver_set_reaction", s, "reaction", "reaction")
+
+    @property
+    def has_reaction(self):
+        """True when a reaction term is set (shared or per instance)."""
+        return self.n_reactions > 0
+
+    @property
+    def n_reactions(self):
+        """0 without a reaction, 1 with one shared by every instance, else the number of per-instance reaction terms."""
+        return int(_need_rx_batch("mg_batch_solver_has_reaction")(self._s))
 
     def set_krylov(self, m):
         """m = 1 .. 16: restarted GCR(m) around the cycle, per instance (include/mg_krylov_batch.h; the method is
@@ -2297,6 +2335,31 @@ def solve_batched_krylov(F, m, U=None, L=1.0, coef=None, **opts):
         s.close()
 
 
+def solve_batched_reaction(F, s, U=None, L=1.0, coef=None, krylov=0, **opts):
+    """solve_batched with a variable reaction term: B problems div(a_i grad U_i) - (sigma + s_i)*U_i = F_i in one batched call;
+    returns (U, infos).  s: (N, N), shared by every instance, or (B, N, N) / a sequence of B (N, N) ones, one per instance
+    (BatchSolver.set_reaction); coef: None, or what solve_batched_coef takes as a; krylov = m > 0 wraps every instance in
+    GCR(m) (BatchSolver.set_krylov); F and U as solve_batched takes them.  Every instance is bit-identical to
+    solve(F_i, U_i, L, reaction=s_i, coef=a_i, krylov=m, ...) alone; s == 0 everywhere is solve_batched, bit for bit."""
+    Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
+    if U is None:
+        B = 1 if shared else len(Fs)
+    else:
+        B = len(U) if isinstance(U, (list, tuple)) else (1 if isinstance(U, DeviceGrid) or len(U.shape) == 2 else int(U.shape[0]))
+    count = lambda x: 0 if x is None else len(x) if isinstance(x, (list, tuple)) else (int(x.shape[0]) if len(x.shape) == 3 else 1)
+    N = int(Fs[0].shape[-1])
+    b = BatchSolver(N, L, max_batch=max(B, count(s), count(coef), 1), **opts)
+    try:
+        if coef is not None:
+            b.set_coefficient(coef)
+        b.set_reaction(s)
+        if krylov:
+            b.set_krylov(krylov)
+        return b.solve(F, U)
+    finally:
+        b.close()
+
+
 def _need_adjoint(name):
     if not hasattr(lib(), name):
         raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the adjoint sensitivities are not in this library)")
@@ -2371,6 +2434,12 @@ def _need_krylov_batch(name):
 def _need_vc_batch(name):
     if not hasattr(lib(), name):
         raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched variable-coefficient solver is not in this library)")
+    return getattr(_lib, name)
+
+
+def _need_rx_batch(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched reaction solver is not in this library)")
     return getattr(_lib, name)
 
 

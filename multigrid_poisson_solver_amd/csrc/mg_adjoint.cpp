@@ -263,6 +263,10 @@ int mg_batch_solver_adjoint(mg_batch_solver *s, int n, const double *const *Ubar
         fail(MG_ERR_ARG, "%s: n = %d outside [1, max_batch = %d]", who, n, max_batch);
         return refuse(MG_ERR_ARG);
     }
+    if (mg_batch_solver_has_reaction(s)) {   // (include/mg_rx_batch.h: refused as mg_solver_adjoint refuses it)
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the adjoint is not built for a reaction", who);
+        return refuse(MG_ERR_UNSUPPORTED);
+    }
     const int n_coef = mg_batch_solver_has_coefficient(s);
     if (n_coef > 1 && n > n_coef) {
         fail(MG_ERR_ARG, "%s: n = %d instances, but the solver holds %d coefficients (one per instance)", who, n, n_coef);

@@ -564,6 +564,20 @@ void gauss_seidel_relative_rx(hipStream_t s, int N, double h2, double inv, doubl
                               const double *F, double atol, double rtol, int max_iters, int *state, double *err_out);
 // *flag = 1 when a value of S[0..n) is not finite or not >= 0 (the caller zeroes the flag)
 void reaction_check(hipStream_t s, const double *S, size_t n, int *flag);
+// batched forms of the above (mg_reaction_batch_kernels.hip, driven by mg_solve_batch.cpp; include/mg_rx_batch.h): one launch
+// over n instances, each running the code and the block partition of its single launch (the bodies are shared:
+// mg_reaction_impl.h).  items[i]: the arrays of instance i as the `_vc_batch` launchers take them, the level's reaction term in
+// the slot `Fc`; has_a: the slot `coarse` of EVERY instance holds its coefficient (false: it is not read, a = 1).
+void wjacobi_rx_batch(hipStream_t s, int n, int N, double dx2, double sd, double omega, bool zero_in, bool has_a, const NodeBatchItem *items);
+void residual_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items, int sign);
+// A*z: in = z, coarse = a, Fc = s, out
+void apply_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items);
+void resnorm_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items, double *part,
+                      double *out);
+void gauss_seidel_relative_rx_batch(hipStream_t s, int n, int N, double h2, double inv, double sd, bool has_a, const NodeBatchItem *items,
+                                    double atol, double rtol, int max_iters, int *state);
+// check of `count` values: in = s, flags[i] = 1 for an instance with a value that is not finite or not >= 0 (zeroed by the caller)
+void reaction_check_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items, int *flags);
 // the pass of the semilinear solve (mg_newton_kernels.hip, driven by mg_solve.cpp; the expressions and their order:
 // include/mg_newton.h): V = U + t*dlt (dlt == nullptr: no step, V not written), S = kappa*W*g'(V) on all N^2 points,
 // D = (F + kappa*W*g(V)) - inv*b(V) inside and +0 on the rim, *out = sqrt(sum of D^2) in the partition and order of resnorm

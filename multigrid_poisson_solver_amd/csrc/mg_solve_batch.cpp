@@ -12,6 +12,9 @@
 // in its steps, through the batched `_vc` kernels (mg_varcoef_batch_kernels.hip).
 // With mg_batch_solver_set_krylov(m > 0) (include/mg_krylov_batch.h) the loop is restarted GCR(m) per instance around either
 // cycle: krylov_iterate_batch below, launch by launch over the active set (mg_krylov_batch_kernels.hip).
+// With a reaction set (include/mg_rx_batch.h) the cycle is the operator-by-operator one too, with or without a coefficient,
+// through the batched `_rx` kernels (mg_reaction_batch_kernels.hip): the level's reaction term rides in the slot `Fc` of the
+// sweep, residual and coarse-solve tables, which the recorded steps leave empty -- the steps themselves do not change.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,6 +50,11 @@ struct mg_batch_solver {
     int n_coef = 0;                          // 0: none set; 1: one shared by every instance; n > 1: instance i uses copy i
     int *coef_flags = nullptr;               // device [max_batch]: the check found a bad value in that instance
     int *host_coef_flags = nullptr;          // pinned [max_batch]
+    // variable reaction term (include/mg_rx_batch.h; nothing of it is allocated before the first mg_batch_solver_set_reaction);
+    // the check borrows coef_flags / host_coef_flags
+    std::vector<double *> react;             // per level: the nodal reaction terms of react_cap instances at the instance pitch
+    int react_cap = 0;                       // instances the level storage holds
+    int n_react = 0;                         // 0: none set; 1: one shared by every instance; n > 1: instance i uses copy i
     // Krylov acceleration (include/mg_krylov_batch.h; nothing of it is allocated before the first enabling
     // mg_batch_solver_set_krylov).  Everything is indexed by the instance's position in the call, not by its active slot.
     int kr_m = 0;                            // 0: off
@@ -80,6 +88,7 @@ void release(mg_batch_solver *s)
     for (double *p : s->B) if (p) (void)hipFree(p);
     for (double *p : s->F) if (p) (void)hipFree(p);
     for (double *p : s->coef) if (p) (void)hipFree(p);
+    for (double *p : s->react) if (p) (void)hipFree(p);
     if (s->coef_flags) (void)hipFree(s->coef_flags);
     if (s->host_coef_flags) (void)hipHostFree(s->host_coef_flags);
     for (double *p : s->kr_Z) if (p) (void)hipFree(p);
@@ -99,11 +108,18 @@ void release(mg_batch_solver *s)
     delete s;
 }
 
-// the cycle the tables are built for: with a coefficient operator by operator, whatever mg_set_smoother says
-const SolveCycle &cycle_of(const mg_batch_solver *s) { return s->n_coef > 0 ? s->cyc_ops : s->cyc_fused; }
+// the cycle the tables are built for: with a coefficient or a reaction operator by operator, whatever mg_set_smoother says
+const SolveCycle &cycle_of(const mg_batch_solver *s) { return s->n_coef > 0 || s->n_react > 0 ? s->cyc_ops : s->cyc_fused; }
+
+// the level-l reaction term of instance i (copy i, or the one copy in shared mode); nullptr without a reaction
+double *react_of(const mg_batch_solver *s, int l, int i)
+{
+    return s->n_react > 0 ? level(s, s->react, l, s->n_react == 1 ? 0 : i) : nullptr;
+}
 
 // the arrays of instance i (active slot j) in the table of every step of the cycle; table 0: the norm's entry.  The coefficient
-// is copy i, or the one copy in shared mode
+// is copy i, or the one copy in shared mode.  With a reaction the level's term goes into the slot `Fc` of the norm, the sweeps,
+// the residuals and the coarse solve, whose steps record none there (and, without a coefficient, nothing into `coarse`)
 void fill_slot(mg_batch_solver *s, const SolveCycle &c, int j, const double *F0, double *U0, int i)
 {
     const int ci = s->n_coef == 1 ? 0 : i;
@@ -114,14 +130,17 @@ void fill_slot(mg_batch_solver *s, const SolveCycle &c, int j, const double *F0,
         case Field::A: return level(s, s->A, r.level, i);
         case Field::B: return level(s, s->B, r.level, i);
         case Field::F: return level(s, s->F, r.level, i);
-        case Field::Coef: return level(s, s->coef, r.level, ci);
+        case Field::Coef: return s->n_coef > 0 ? level(s, s->coef, r.level, ci) : nullptr;
         case Field::None: break;
         }
         return nullptr;
     };
     auto item = [&](int t) -> NodeBatchItem & { return s->host_tab[(size_t)t * s->max_batch + j]; };
-    item(0) = NodeBatchItem{U0, F0, s->n_coef > 0 ? level(s, s->coef, 0, ci) : nullptr, nullptr, nullptr};
-    for (const SolveStep &t : c.steps) item(t.slot) = NodeBatchItem{at(t.in), at(t.F), at(t.coarse), at(t.out), at(t.Fc)};
+    item(0) = NodeBatchItem{U0, F0, s->n_coef > 0 ? level(s, s->coef, 0, ci) : nullptr, nullptr, react_of(s, 0, i)};
+    for (const SolveStep &t : c.steps) {
+        const bool op = t.kind == SolveStep::Sweep || t.kind == SolveStep::Residual || t.kind == SolveStep::Coarse;
+        item(t.slot) = NodeBatchItem{at(t.in), at(t.F), at(t.coarse), at(t.out), op && s->n_react > 0 ? react_of(s, t.level, i) : at(t.Fc)};
+    }
 }
 
 // (without a coefficient: no more tables, and bytes, than the solver uploaded before it knew of one)
@@ -132,12 +151,12 @@ bool upload_tables(mg_batch_solver *s, hipStream_t st)
 }
 
 // one cycle of the n active instances whose tables are uploaded: every step ONE launch over them from the table of its slot,
-// with the `_vc` kernels when a coefficient is set; returns the launches it enqueued
+// with the `_rx` kernels when a reaction is set, else the `_vc` kernels when a coefficient is; returns the launches it enqueued
 int run_cycle_batch(mg_batch_solver *s, hipStream_t st, const SolveCycle &c, int n)
 {
     const mg_solve_opts &o = s->o;
     const int nl = (int)s->sizes.size(), mb = s->max_batch;
-    const bool vc = s->n_coef > 0;
+    const bool vc = s->n_coef > 0, rx = s->n_react > 0;
     for (const SolveStep &t : c.steps) {
         const int l = t.level, N = s->sizes[l], M = l + 1 < nl ? s->sizes[l + 1] : 0;   // (M: the coarse size of a transfer)
         const LevelConsts &lc = s->lc[l];
@@ -151,14 +170,21 @@ int run_cycle_batch(mg_batch_solver *s, hipStream_t st, const SolveCycle &c, int
             k::jacobi_stream(st, nd);
             break;
         }
-        case SolveStep::Sweep: k::wjacobi_vc_batch(st, n, N, lc.dx2, lc.sd, o.omega, t.in.f == Field::None, tab); break;
+        case SolveStep::Sweep:
+            if (rx) k::wjacobi_rx_batch(st, n, N, lc.dx2, lc.sd, o.omega, t.in.f == Field::None, vc, tab);
+            else k::wjacobi_vc_batch(st, n, N, lc.dx2, lc.sd, o.omega, t.in.f == Field::None, tab);
+            break;
         case SolveStep::Residual:
-            if (vc) k::residual_vc_batch(st, n, N, lc.inv, lc.sd, tab, -1);
+            if (rx) k::residual_rx_batch(st, n, N, lc.dx2, lc.inv, lc.sd, vc, tab, -1);
+            else if (vc) k::residual_vc_batch(st, n, N, lc.inv, lc.sd, tab, -1);
             else k::residual_batch(st, n, N, lc.inv, tab, -1, lc.sh);
             break;
         case SolveStep::Restrict: k::restrict_batch(st, n, N, M, tab, restrict_table(N, M), +1); break;
         case SolveStep::Coarse:
-            if (vc)
+            if (rx)
+                k::gauss_seidel_relative_rx_batch(st, n, N, lc.dx2, lc.inv, lc.sd, vc, tab, o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
+                                                  rb_state(s->dev_rb, mb));
+            else if (vc)
                 k::gauss_seidel_relative_vc_batch(st, n, N, lc.dx2, lc.inv, lc.sd, tab, o.coarse_atol, o.coarse_rtol, o.coarse_max_iters,
                                                   rb_state(s->dev_rb, mb));
             else
@@ -206,6 +232,20 @@ int norms_vc(mg_batch_solver *s, hipStream_t st, int n, double *out)
     return 2;
 }
 
+// the residual norm with the reaction (and the coefficient, when one is set)
+int norms_rx(mg_batch_solver *s, hipStream_t st, int n, double *out)
+{
+    k::resnorm_rx_batch(st, n, s->N, s->lc[0].dx2, s->lc[0].inv, s->lc[0].sd, s->n_coef > 0, s->dev_tab, s->part, out);
+    return 2;
+}
+
+// the stopping norm ||F - AU|| of the n instances of table 0 with the operator that is set
+int norms_res(mg_batch_solver *s, hipStream_t st, int n, double *out)
+{
+    if (s->n_react > 0) return norms_rx(s, st, n, out);
+    return s->n_coef > 0 ? norms_vc(s, st, n, out) : norms(s, st, n, true, out);
+}
+
 bool read_back(mg_batch_solver *s, hipStream_t st)
 {
     if (!MG_HIP(hipMemcpyAsync(s->host_rb, s->dev_rb, rb_bytes(s->max_batch), hipMemcpyDeviceToHost, st))) return false;
@@ -224,9 +264,10 @@ bool overlap(const void *a, const void *b, size_t bytes)
 constexpr int KR_REC_MAX = MG_KRYLOV_MAX_M + 7;
 
 // the tables of one iteration, one block in pinned and one in device memory, uploaded together: by active slot the Krylov
-// kernels' entries and A*z (in = z_k, coarse = a_i or NULL, out = q_k); by slot of the restarting subset the record to mark
-// and the residual and norm (in = U_i, F = F_i, coarse = a_i or NULL, out = r_i); `first` is the latter for the residual
-// that starts the loop, a table of its own because it is uploaded while the first iteration's tables are written
+// kernels' entries and A*z (in = z_k, coarse = a_i or NULL, out = q_k, Fc = s_i or NULL); by slot of the restarting subset the
+// record to mark and the residual and norm (in = U_i, F = F_i, coarse = a_i or NULL, out = r_i, Fc = s_i or NULL); `first` is
+// the latter for the residual that starts the loop, a table of its own because it is uploaded while the first iteration's
+// tables are written
 struct KrylovTables {
     k::KrylovBatchItem *act, *mark;
     NodeBatchItem *apply, *recompute, *first;
@@ -269,7 +310,8 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
     const int N = s->N, m = s->kr_m, rec_len = m + 7, mb = s->max_batch;
     const size_t p0 = s->pitch[0], n_part = (size_t)k::KRYLOV_MAX_K * k::krylov_blocks(N), log_stride = krylov_log_stride(s);
     const double pts = (double)N * N, sd = s->lc[0].sd;
-    const bool vc = s->n_coef > 0, simple = ctx().smoother == SMOOTHER_SIMPLE;
+    const bool vc = s->n_coef > 0, rx = s->n_react > 0, simple = ctx().smoother == SMOOTHER_SIMPLE;
+    const double dx2 = s->lc[0].dx2;
     const KrylovTables host = krylov_tables(s->kr_host_tab, mb), dev = krylov_tables(s->kr_dev_tab, mb);
     s->kr_log_m = m;
     s->kr_n = n;
@@ -289,27 +331,29 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
     auto fill_recompute = [&](const std::vector<int> &sub) {
         for (size_t js = 0; js < sub.size(); ++js) {
             const int i = sub[js];
-            host.recompute[js] = NodeBatchItem{U_dev[i], F_dev[i], coef_of(i), s->kr_r + (size_t)i * p0, nullptr};
+            host.recompute[js] = NodeBatchItem{U_dev[i], F_dev[i], coef_of(i), s->kr_r + (size_t)i * p0, react_of(s, 0, i)};
             host.mark[js] = k::KrylovBatchItem{};
             host.mark[js].rec = rec_of(i);
         }
     };
     auto residual = [&](int ns, const NodeBatchItem *items) {
-        ProfScope ps("krylov_residual_batch", N, pts * ns * (vc ? 32.0 : 24.0));
-        if (vc) k::residual_vc_batch(st, ns, N, s->lc[0].inv, sd, items, -1);
+        ProfScope ps("krylov_residual_batch", N, pts * ns * ((vc ? 32.0 : 24.0) + (rx ? 8.0 : 0.0)));
+        if (rx) k::residual_rx_batch(st, ns, N, dx2, s->lc[0].inv, sd, vc, items, -1);
+        else if (vc) k::residual_vc_batch(st, ns, N, s->lc[0].inv, sd, items, -1);
         else k::residual_batch(st, ns, N, s->lc[0].inv, items, -1, s->lc[0].sh);
         return 1;
     };
     auto recompute = [&](int ns) {
         int launches = residual(ns, dev.recompute);
-        if (vc) k::resnorm_vc_batch(st, ns, N, s->lc[0].inv, sd, dev.recompute, s->part, rb_res(s->dev_rb));
+        if (rx) k::resnorm_rx_batch(st, ns, N, dx2, s->lc[0].inv, sd, vc, dev.recompute, s->part, rb_res(s->dev_rb));
+        else if (vc) k::resnorm_vc_batch(st, ns, N, s->lc[0].inv, sd, dev.recompute, s->part, rb_res(s->dev_rb));
         else k::resnorm_batch(st, ns, N, s->lc[0].inv, true, dev.recompute, s->part, rb_res(s->dev_rb), s->lc[0].sh);
         k::krylov_log_restart_batch(st, ns, m, dev.mark, rb_res(s->dev_rb));
         return launches + 3;
     };
     if (act.empty()) return true;
     for (size_t j = 0; j < act.size(); ++j)
-        host.first[j] = NodeBatchItem{U_dev[act[j]], F_dev[act[j]], coef_of(act[j]), s->kr_r + (size_t)act[j] * p0, nullptr};
+        host.first[j] = NodeBatchItem{U_dev[act[j]], F_dev[act[j]], coef_of(act[j]), s->kr_r + (size_t)act[j] * p0, react_of(s, 0, act[j])};
     if (!MG_HIP(hipMemcpyAsync(dev.first, host.first, act.size() * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st))) return false;
     bs.launches += residual((int)act.size(), dev.first);
     std::vector<int> known, late, next;   // restarts known before the read-back (k + 1 == m), and found by it
@@ -327,7 +371,7 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
             fill_slot(s, cycle_of(s), j, ri, z, i);
             host.act[j] = k::KrylovBatchItem{U_dev[i], ri, z, q, s->kr_scal + (size_t)i * k::KRYLOV_SCAL_COUNT,
                                              s->kr_part + (size_t)i * n_part, rec_of(i), (size_t)i * p0, kk, 0};
-            host.apply[j] = NodeBatchItem{z, nullptr, coef_of(i), q, nullptr};
+            host.apply[j] = NodeBatchItem{z, nullptr, coef_of(i), q, react_of(s, 0, i)};
             if (kk > kmax) kmax = kk;
             dots_bytes += kk > 0 ? 8.0 + 8.0 * kk : 0.0;
             orth_bytes += kk > 0 ? 40.0 + 16.0 * kk : 16.0;
@@ -340,11 +384,12 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
             k::krylov_zero_batch(st, na, N, dev.act);
         }
         bs.launches += 1;
-        bs.launches += simple && !vc ? vcycle_simple_each(s, st, act, s->kr_F.data(), s->kr_U.data())
+        bs.launches += simple && !vc && !rx ? vcycle_simple_each(s, st, act, s->kr_F.data(), s->kr_U.data())
                                      : run_cycle_batch(s, st, cycle_of(s), na);
         {
-            ProfScope ps("krylov_apply_batch", N, pts * na * (vc ? 24.0 : 16.0));
-            k::apply_vc_batch(st, na, N, s->lc[0].inv, sd, dev.apply);
+            ProfScope ps("krylov_apply_batch", N, pts * na * ((vc ? 24.0 : 16.0) + (rx ? 8.0 : 0.0)));
+            if (rx) k::apply_rx_batch(st, na, N, dx2, s->lc[0].inv, sd, vc, dev.apply);
+            else k::apply_vc_batch(st, na, N, s->lc[0].inv, sd, dev.apply);
         }
         bs.launches += 1;
         if (kmax > 0) {
@@ -425,7 +470,7 @@ int mg::batch_solver_cycle(mg_batch_solver *s, hipStream_t st, int n, const doub
         fill_slot(s, cycle_of(s), i, F0[i], U0[i], i);
     }
     if (!upload_tables(s, st)) return -1;
-    if (s->n_coef == 0 && ctx().smoother == SMOOTHER_SIMPLE) return vcycle_simple_each(s, st, act, F0, U0);
+    if (s->n_coef == 0 && s->n_react == 0 && ctx().smoother == SMOOTHER_SIMPLE) return vcycle_simple_each(s, st, act, F0, U0);
     return run_cycle_batch(s, st, cycle_of(s), n);
 }
 
@@ -552,6 +597,10 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
         fail(MG_ERR_ARG, "mg_batch_solver_solve: n = %d instances, but the solver holds %d coefficients (one per instance)", n, s->n_coef);
         return finish(MG_ERR_ARG);
     }
+    if (s->n_react > 1 && n > s->n_react) {
+        fail(MG_ERR_ARG, "mg_batch_solver_solve: n = %d instances, but the solver holds %d reaction terms (one per instance)", n, s->n_react);
+        return finish(MG_ERR_ARG);
+    }
     for (int i = 0; i < n; ++i) s->history[i].clear();
     const size_t bytes = (size_t)s->N * s->N * sizeof(double);
     for (int i = 0; i < n; ++i) {
@@ -578,7 +627,7 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
     const hipStream_t st = ctx().stream;
     const mg_solve_opts &o = s->o;
     const int mb = s->max_batch;
-    const bool vc = s->n_coef > 0;   // (the variable-coefficient cycle, whatever mg_set_smoother says)
+    const bool ops = s->n_coef > 0 || s->n_react > 0;   // (the operator-by-operator cycle, whatever mg_set_smoother says)
     const bool simple = ctx().smoother == SMOOTHER_SIMPLE;
     std::vector<int> act(n);
     std::vector<double> tol(n);
@@ -591,7 +640,7 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
     if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
     if (!build()) return finish(MG_ERR_HIP);
     bs.launches += norms(s, st, n, false, rb_ref(s->dev_rb, mb));
-    bs.launches += vc ? norms_vc(s, st, n, rb_res(s->dev_rb)) : norms(s, st, n, true, rb_res(s->dev_rb));
+    bs.launches += norms_res(s, st, n, rb_res(s->dev_rb));
     if (!read_back(s, st)) return finish(MG_ERR_HIP);
     std::vector<int> next;
     for (int i = 0; i < n; ++i) {
@@ -611,8 +660,8 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
             if (!build()) return finish(MG_ERR_HIP);
         }
         const int na = (int)act.size();
-        bs.launches += simple && !vc ? vcycle_simple_each(s, st, act, F_dev, U_dev) : run_cycle_batch(s, st, cycle_of(s), na);
-        bs.launches += vc ? norms_vc(s, st, na, rb_res(s->dev_rb)) : norms(s, st, na, true, rb_res(s->dev_rb));
+        bs.launches += simple && !ops ? vcycle_simple_each(s, st, act, F_dev, U_dev) : run_cycle_batch(s, st, cycle_of(s), na);
+        bs.launches += norms_res(s, st, na, rb_res(s->dev_rb));
         if (!read_back(s, st)) return finish(MG_ERR_HIP);
         next.clear();
         for (int j = 0; j < na; ++j) {
@@ -743,6 +792,107 @@ int mg_batch_solver_set_coefficient(mg_batch_solver *s, int n, const double *con
 }
 
 int mg_batch_solver_has_coefficient(const mg_batch_solver *s) { return s ? s->n_coef : 0; }
+
+// ------------------------------------------------------------------ variable reaction term (include/mg_rx_batch.h)
+// mg_batch_solver_set_coefficient's steps with the reaction's check (>= 0) and storage of its own
+int mg_batch_solver_set_reaction(mg_batch_solver *s, int n, const double *const *s_dev)
+{
+    if (!require_ready("mg_batch_solver_set_reaction")) return MG_ERR_NOT_INIT;
+    if (!s) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: NULL solver");
+        return MG_ERR_ARG;
+    }
+    if (n < 0 || n > s->max_batch) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: n = %d outside [0, max_batch = %d]", n, s->max_batch);
+        return MG_ERR_ARG;
+    }
+    if (n == 0) {
+        if (s_dev) {
+            fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: n = 0 takes the reaction away and needs a NULL array");
+            return MG_ERR_ARG;
+        }
+        s->n_react = 0;   // the solver without a reaction again (the level storage stays for the next one)
+        return MG_OK;
+    }
+    if (!s_dev) {
+        fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: NULL array of %d reaction terms", n);
+        return MG_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!s_dev[i] || (uintptr_t)s_dev[i] % 16 != 0) {
+            fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: the reaction term of instance %d is NULL or not 16-byte aligned", i);
+            return MG_ERR_ARG;
+        }
+    const hipStream_t st = ctx().stream;
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    if (!s->coef_flags &&
+        !(MG_HIP(hipMalloc((void **)&s->coef_flags, mb * sizeof(int))) &&
+          MG_HIP(hipHostMalloc((void **)&s->host_coef_flags, mb * sizeof(int), hipHostMallocDefault)))) {
+        if (s->coef_flags) { (void)hipFree(s->coef_flags); s->coef_flags = nullptr; }
+        return MG_ERR_HIP;
+    }
+    // level storage for n instances: what is there when it is large enough, else a fresh set, which replaces the old one
+    // only once the check has passed -- a refused reaction leaves the solver's own untouched
+    std::vector<double *> fresh;
+    auto drop_fresh = [&]() {
+        for (double *p : fresh) if (p) (void)hipFree(p);
+        fresh.clear();
+    };
+    if (s->react_cap < n) {
+        fresh.assign(nl, nullptr);
+        for (int l = 0; l < nl; ++l)
+            if (!MG_HIP(hipMalloc((void **)&fresh[l], s->pitch[l] * n * sizeof(double)))) {
+                drop_fresh();
+                return MG_ERR_HIP;
+            }
+    }
+    const std::vector<double *> &dst = fresh.empty() ? s->react : fresh;
+    // tables: the check and the copy into level 0 (slot 0: in = the caller's s_i, out = level 0), then per level the
+    // coarsening (slot 1 + l: in = level l, out = level l + 1).  The solver's own tables: every solve rebuilds them.
+    for (int i = 0; i < n; ++i) {
+        s->host_tab[i] = NodeBatchItem{s_dev[i], nullptr, nullptr, dst[0] + (size_t)i * s->pitch[0], nullptr};
+        for (int l = 0; l + 1 < nl; ++l)
+            s->host_tab[(size_t)(1 + l) * mb + i] =
+                NodeBatchItem{dst[l] + (size_t)i * s->pitch[l], nullptr, nullptr, dst[l + 1] + (size_t)i * s->pitch[l + 1], nullptr};
+    }
+    const size_t n0 = (size_t)s->N * s->N;
+    bool ok = MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)nl * mb * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)) &&
+              MG_HIP(hipMemsetAsync(s->coef_flags, 0, n * sizeof(int), st));
+    if (ok) {
+        // the check comes first and reads the CALLER's arrays
+        k::reaction_check_batch(st, n, n0, s->dev_tab, s->coef_flags);
+        ok = MG_HIP(hipMemcpyAsync(s->host_coef_flags, s->coef_flags, n * sizeof(int), hipMemcpyDeviceToHost, st)) &&
+             MG_HIP(hipStreamSynchronize(st));
+    }
+    if (!ok) {
+        drop_fresh();
+        return MG_ERR_HIP;
+    }
+    for (int i = 0; i < n; ++i)
+        if (s->host_coef_flags[i]) {
+            drop_fresh();
+            fail(MG_ERR_ARG, "mg_batch_solver_set_reaction: every value of s must be finite and >= 0 (instance %d has one that is not)", i);
+            return MG_ERR_ARG;
+        }
+    // from here on the level storage is overwritten: until it is whole again the solver has NO reaction, so a HIP error
+    // below never leaves a solver on a half-replaced term
+    s->n_react = 0;
+    if (!fresh.empty()) {
+        for (double *p : s->react) if (p) (void)hipFree(p);
+        s->react.swap(fresh);
+        fresh.clear();
+        s->react_cap = n;
+    }
+    k::copy_batch(st, n, n0, s->dev_tab);
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen_batch(st, n, s->sizes[l], s->sizes[l + 1], s->dev_tab + (size_t)(1 + l) * mb,
+                              restrict_table(s->sizes[l], s->sizes[l + 1]));
+    if (!MG_HIP(hipStreamSynchronize(st))) return MG_ERR_HIP;   // (the caller may free the s_i, or solve on another stream)
+    s->n_react = n;
+    return MG_OK;
+}
+
+int mg_batch_solver_has_reaction(const mg_batch_solver *s) { return s ? s->n_react : 0; }
 
 // ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov_batch.h)
 int mg_batch_solver_set_krylov(mg_batch_solver *s, int m)
