@@ -518,6 +518,7 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 /* the semilinear problem div(a grad U) - sigma*U - kappa*w*g(U) = F, Newton around the solver: mg_solver_newton, ... */
 #include "mg_newton.h"
 #include "mg_rx_batch.h"
+#include "mg_newton_batch.h"
 /* Neumann and mixed boundary kinds per side in the solver and the heat stepper: mg_solver_set_boundary, mg_neumannSource, ... */
 #include "mg_bc.h"
 /* the batched solver with the Krylov acceleration, GCR(m) per instance: mg_batch_solver_set_krylov, ... */

@@ -55,7 +55,8 @@
  *                           on w); a NULL solver, F or U; an array that is not 16-byte aligned; options out of range (rtol,
  *                           atol negative or not finite, max_iters or max_backtracks negative); a start whose residual is not
  *                           finite
- * Not built: the batched solver, the heat stepper, the adjoint of a semilinear solve, boundary kinds, a user-supplied g.
+ * The batched solver runs this driver for many instances in one call: mg_newton_batch.h.
+ * Not built: the heat stepper, the adjoint of a semilinear solve, boundary kinds, a user-supplied g.
  */
 #ifndef MG_NEWTON_H
 #define MG_NEWTON_H

@@ -38,7 +38,8 @@
  * mg_batch_solver_set_coefficient, mg_batch_solver_set_reaction and mg_batch_solver_set_krylov work in any order.
  *
  * Refused: mg_batch_solver_adjoint while a reaction is set (MG_ERR_UNSUPPORTED, the solver unchanged, as mg_solver_adjoint).
- * Not built: a batched Newton solve (mg_newton.h); a reaction in the heat stepper or the eigensolver, whose private batch
+ * The batched Newton solve (mg_newton_batch.h) installs the Newton matrices' terms through this operator for the length of its
+ * call.  Not built: a reaction in the heat stepper or the eigensolver, whose private batch
  * solvers never set one and whose launches do not change; the adjoint.
  *
  * Memory contract (mg_hip.h): mg_batch_solver_set_reaction reads the s_dev[i] and writes only storage the solver owns; a solve

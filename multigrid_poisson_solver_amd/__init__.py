@@ -308,6 +308,23 @@ ABI_NEWTON = {
 NEWTON_KINDS = {"cubic": 0, "sinh": 1, "exp": 2}
 NEWTON_CONVERGED, NEWTON_NOT_CONVERGED, NEWTON_STALLED = 0, -1, -2
 
+
+# the symbols include/mg_newton_batch.h declares (the semilinear problem on the batched solver: Newton's method for many
+# instances in lockstep); bound like ABI_RX_BATCH: a library without them still loads, BatchSolver.newton_batch() /
+# solve_semilinear_batched() / nonlinear_residual_batch() then raise
+class BatchNewtonStats(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("trial_rounds", C.c_int), ("inner_cycles", C.c_int), ("launches", C.c_int),
+                ("device_ms", C.c_double)]
+
+
+ABI_NEWTON_BATCH = {
+    "mg_batch_solver_newton": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(NewtonOpts), C.POINTER(NewtonResult),
+                                    C.POINTER(BatchNewtonStats)]),
+    "mg_batch_solver_newton_history": (_i, [_vp, _i, C.POINTER(NewtonIter), _i]),
+    "mg_batch_solver_newton_inner_history": (_i, [_vp, _i, _vp, _i]),
+    "mg_nonlinearResidual_batch": (_i, [_i, _i, _d, _d, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
+}
+
 # the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
 # ABI_FMG: a library without it still loads, solve_cycle() then raises
 ABI_SOLVE_CYCLE = {
@@ -374,7 +391,7 @@ def load_library(path=None):
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
             list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()) + \
-            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()) + list(ABI_RX_BATCH.items()):
+            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()) + list(ABI_RX_BATCH.items()) + list(ABI_NEWTON_BATCH.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -820,6 +837,45 @@ def nonlinear_residual(N, L, shift, a, kind, kappa, w, U, F, D, S, dlt=None, t=1
         _check()
         raise MGError(f"mg_nonlinearResidual failed with status {status}")
     return float(out.value)
+
+
+def _need_newton_batch(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the batched semilinear solve is not in this library)")
+    return getattr(_lib, name)
+
+
+def _counted_pointers(arrays, n, what):
+    """None, one DeviceGrid (anything with .ptr) or a sequence of 1 or n of them -> (count, pointer array or None)"""
+    if arrays is None:
+        return 0, None
+    items = [arrays] if hasattr(arrays, "ptr") else list(arrays)
+    if len(items) not in (1, n):
+        raise MGError(f"[2] {what}: {len(items)} arrays for {n} instances (one shared by all, or one per instance)")
+    return len(items), _pointer_array(items)
+
+
+def nonlinear_residual_batch(N, L, shift, a, kind, kappa, w, U, F, D, S, dlt=None, t=1.0, V=None):
+    """Test hook: nonlinear_residual for n instances in ONE launch (include/mg_newton_batch.h: mg_nonlinearResidual_batch).  U,
+    F, D, S (and dlt, V in the step form): sequences of n DeviceGrids; a, w: None, one DeviceGrid shared by every instance, or
+    a sequence of n; kappa: a scalar or a sequence of n.  Instance i gets the V, D, S and norm of nonlinear_residual on it
+    alone, bit for bit.  Returns the list of the n norms."""
+    n = len(U)
+    for name, xs in (("F", F), ("D", D), ("S", S)) + ((("dlt", dlt), ("V", V)) if dlt is not None else ()):
+        if xs is None or len(xs) != n:
+            raise MGError(f"[2] {name}: expected {n} arrays")
+    n_a, a_arr = _counted_pointers(a, n, "a")
+    n_w, w_arr = _counted_pointers(w, n, "w")
+    kap = np.ascontiguousarray(np.broadcast_to(np.asarray(kappa, dtype=np.float64), (n,)))
+    norms = np.zeros(n)
+    status = _need_newton_batch("mg_nonlinearResidual_batch")(
+        n, int(N), float(L), float(shift), n_a, a_arr, _newton_kind(kind), kap.ctypes.data, n_w, w_arr, _pointer_array(U),
+        None if dlt is None else _pointer_array(dlt), float(t), _pointer_array(F), None if dlt is None else _pointer_array(V),
+        _pointer_array(D), _pointer_array(S), norms.ctypes.data)
+    if status:
+        _check()
+        raise MGError(f"mg_nonlinearResidual_batch failed with status {status}")
+    return [float(v) for v in norms]
 
 
 def _need_bc(name):
@@ -1685,6 +1741,8 @@ class Solver:
         if status > 0:
             _check()
             raise MGError(f"mg_solver_newton failed with status {status}")
+        if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))   # (krylov_log(): the last inner solve's records)
         recs = (NewtonIter * max(res.n_history, 1))()
         n = _lib.mg_solver_newton_history(self._s, recs, res.n_history)
         iters = [dict(res=r.res, t=r.t, backtracks=r.backtracks, inner_cycles=r.inner_cycles,
@@ -1907,6 +1965,12 @@ def _staged(ts, share, nn, dev):
     return [buf[i].data_ptr() for i in range(len(ts))], buf
 
 
+class BatchNewtonInfos(list):
+    """The per-instance info dicts of BatchSolver.newton_batch, in the order of the instances; stats: the dict of the call's own
+    figures (status, iterations, trial_rounds, inner_cycles, launches, device_ms)."""
+    stats = None
+
+
 class BatchSolver:
     """Batched residual-tolerance solver of include/mg_hip.h: up to max_batch problems of size N with one set of options
     (see solve_opts) in one call, every instance bit-identical to a Solver solve of it alone (U, history, cycles, status).
@@ -1921,7 +1985,9 @@ class BatchSolver:
     bit-identical to Solver(krylov=m) on it alone: for coefficients on which the plain cycle crawls or diverges.
     set_reaction(s) solves div(a_i grad U_i) - (sigma + s_i)*U_i = F_i, one reaction term per instance or one shared by all,
     with or without a coefficient and with set_krylov, every instance bit-identical to Solver(reaction=s_i, coef=a_i) on it
-    alone (include/mg_rx_batch.h)."""
+    alone (include/mg_rx_batch.h).
+    newton_batch(F, U, kind, kappa, weight) solves the semilinear problems div(a_i grad U_i) - sigma*U_i - kappa_i*w_i*g(U_i) = F_i by
+    Newton's method in lockstep, every instance bit-identical to Solver.newton on it alone (include/mg_newton_batch.h)."""
 
     def __init__(self, N, L=1.0, max_batch=64, **opts):
         self.N, self.L, self.max_batch = int(N), float(L), int(max_batch)
@@ -2088,7 +2154,7 @@ class BatchSolver:
             return self._solve_torch(F, U)
         return self._solve_host(F, U)
 
-    def _solve_torch(self, F, U):
+    def _solve_torch(self, F, U, run=None):
         import torch
         N = self.N
         Fs, shared = _instances(F, "F")
@@ -2113,7 +2179,7 @@ class BatchSolver:
         prev = _lib.mg_get_stream()
         _lib.mg_set_stream(stream.cuda_stream)
         try:
-            infos = self.solve_ptrs(F_ptrs, U_ptrs)
+            infos = (run or self.solve_ptrs)(F_ptrs, U_ptrs)
         finally:
             _lib.mg_set_stream(prev)
         if Ubuf is not None:
@@ -2122,7 +2188,7 @@ class BatchSolver:
         del Fbuf
         return U, infos
 
-    def _solve_host(self, F, U):
+    def _solve_host(self, F, U, run=None):
         N = self.N
         keep = []
 
@@ -2155,10 +2221,104 @@ class BatchSolver:
             Fd = Fd * len(Ud)
         if len(Fd) != len(Ud):
             raise MGError(f"{len(Fd)} F instances for {len(Ud)} U instances")
-        infos = self.solve_ptrs([f.ptr for f in Fd], [u.ptr for u in Ud])
+        infos = (run or self.solve_ptrs)([f.ptr for f in Fd], [u.ptr for u in Ud])
         if host_U:
             return np.stack([u.to_host() for u in Ud]), infos
         return Ud, infos
+
+    def newton_ptrs(self, F_ptrs, U_ptrs, kind="sinh", kappa=1.0, w_ptrs=None, rtol=1e-8, atol=0.0, max_iters=20, max_backtracks=12):
+        """mg_batch_solver_newton on sequences of device addresses of N x N fp64 arrays (16-byte aligned; U in/out), on the engine
+        stream.  kappa: a scalar or a sequence of n; w_ptrs: None (w = 1), one address shared by every instance, or n.  Returns
+        the list of the n info dicts of Solver.newton_ptr; its attribute `stats` holds the call's status, iterations (the most
+        of any instance), trial_rounds, inner_cycles, launches and device_ms."""
+        fn = _need_newton_batch("mg_batch_solver_newton")
+        n = len(U_ptrs)
+        if len(F_ptrs) != n:
+            raise MGError(f"{len(F_ptrs)} F pointers for {n} U pointers")
+        kap = np.asarray(kappa, dtype=np.float64)
+        if kap.ndim > 1 or (kap.ndim == 1 and kap.shape[0] != n):
+            raise MGError(f"[2] kappa: expected a scalar or {n} values, got shape {kap.shape}")
+        kap = np.ascontiguousarray(np.broadcast_to(kap, (n,)))
+        if w_ptrs is not None and not isinstance(w_ptrs, (list, tuple)):
+            w_ptrs = [w_ptrs]
+        n_w = 0 if w_ptrs is None else len(w_ptrs)
+        arr = lambda ps: (C.c_void_p * max(len(ps), 1))(*ps)
+        o = NewtonOpts(float(rtol), float(atol), int(max_iters), int(max_backtracks))
+        res = (NewtonResult * max(n, 1))()
+        st = BatchNewtonStats()
+        status = fn(self._s, n, _newton_kind(kind), kap.ctypes.data, n_w, arr(w_ptrs) if n_w else None, arr(F_ptrs), arr(U_ptrs),
+                    C.byref(o), res, C.byref(st))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_batch_solver_newton failed with status {status}")
+        infos = BatchNewtonInfos()
+        infos.stats = dict(status=status, iterations=st.iterations, trial_rounds=st.trial_rounds, inner_cycles=st.inner_cycles,
+                           launches=st.launches, device_ms=st.device_ms)
+        for i, r in enumerate(res[:n]):
+            recs = (NewtonIter * max(r.n_history, 1))()
+            got = _lib.mg_batch_solver_newton_history(self._s, i, recs, r.n_history)
+            iters = [dict(res=x.res, t=x.t, backtracks=x.backtracks, inner_cycles=x.inner_cycles,
+                          inner_converged=bool(x.inner_converged), inner_capped=bool(x.inner_capped)) for x in recs[:got]]
+            infos.append(dict(status=r.status, iterations=r.iterations, converged=bool(r.converged), stalled=r.status == NEWTON_STALLED,
+                              res0=r.res0, res=r.res, inner_cycles=r.inner_cycles, trials=r.trials,
+                              history=[r.res0] + [x["res"] for x in iters[:r.iterations]], steps=iters,
+                              last_inner_history=self._newton_inner_history(i) if iters else []))
+        if hasattr(_lib, "mg_batch_solver_krylov") and _lib.mg_batch_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_batch_solver_krylov(self._s))   # (krylov_log(i): instance i's last inner solve)
+        return infos
+
+    def _newton_inner_history(self, i):
+        n = _lib.mg_batch_solver_newton_inner_history(self._s, i, None, 0)
+        buf = np.zeros(max(n, 1))
+        got = _lib.mg_batch_solver_newton_inner_history(self._s, i, buf.ctypes.data, n)
+        return [float(v) for v in buf[:got]]
+
+    def newton_batch(self, F, U=None, kind="sinh", kappa=1.0, weight=None, rtol=1e-8, atol=0.0, max_iters=20, max_backtracks=12):
+        """Solve B semilinear problems div(a_i grad U_i) - sigma*U_i - kappa_i*w_i*g(U_i) = F_i in one call: Solver.newton's
+        Newton iteration with its backtracking line search for all instances in lockstep (include/mg_newton_batch.h).  Every
+        instance is bit-identical to Solver(coef=a_i, krylov=m).newton(F_i, U_i, kind, kappa_i, w_i, ...) on it alone -- U and
+        the whole info dict -- whatever the other instances are and wherever it sits in the batch.  kind ("cubic", "sinh",
+        "exp"), rtol, atol, max_iters and max_backtracks are one per call, with Solver.newton's defaults; kappa is a scalar or a
+        sequence of B; weight is None (w = 1), one (N, N) field shared by all, or B of them ((B, N, N) or a sequence), values
+        finite and >= 0; a and GCR(m) are what set_coefficient and set_krylov have set.  F, U, weight: numpy arrays,
+        DeviceGrids or float64 torch CUDA tensors, as solve() takes them (torch inputs run on torch.cuda.current_stream()).
+        An instance that has converged, stalled or reached max_iters leaves the batch and is not written again; every Newton
+        iteration and every line-search round is one set of launches over those that remain.  Returns (U, infos): infos[i]
+        is the dict Solver.newton returns (status, iterations, converged, stalled, res0, res, inner_cycles, trials, history,
+        steps, last_inner_history), infos.stats the call's status (0 when every instance converged, else -1), iterations,
+        trial_rounds, inner_cycles, launches and device_ms.  Refused ("[3]") while set_reaction is on, and ("[2]") for a bad
+        kappa, weight (the message names the instance), count or option, with every U untouched; the solver has no reaction
+        afterwards, as before.  The first call allocates about 51*N^2*max_batch bytes; later calls allocate nothing.
+        (The name is not `newton`: tests/test_newton_gpu.py pins that BatchSolver has no attribute of that name.)"""
+        N = self.N
+        opts = dict(kind=kind, kappa=kappa, rtol=rtol, atol=atol, max_iters=max_iters, max_backtracks=max_backtracks)
+        if weight is None:
+            ws = None
+        elif isinstance(weight, (list, tuple)):
+            ws = list(weight)
+        elif len(weight.shape) == 3:
+            ws = [weight[i] for i in range(weight.shape[0])]
+        elif len(weight.shape) == 2:
+            ws = [weight]
+        else:
+            raise MGError(f"[2] weight: expected (N, N), (B, N, N) or a sequence of (N, N) arrays, got shape {tuple(weight.shape)}")
+        keep = []
+
+        def run(F_ptrs, U_ptrs):   # (inside _solve_torch the engine is on the tensors' stream here)
+            try:
+                w_ptrs = None if ws is None else [_coefficient_address(N, w, keep) for w in ws]
+            except MGError as e:
+                raise MGError("[2] " + str(e).replace("coef:", "weight:", 1)) from None
+            return self.newton_ptrs(F_ptrs, U_ptrs, w_ptrs=w_ptrs, **opts)
+
+        first = lambda X: X[0] if isinstance(X, (list, tuple)) else X
+        try:
+            if _is_torch(first(F)) or (U is not None and _is_torch(first(U))):
+                return self._solve_torch(F, U, run)
+            return self._solve_host(F, U, run)
+        finally:
+            for g in keep:
+                g.free()
 
     def adjoint_ptrs(self, Ubar_ptrs, U_ptrs, lam_ptrs, gA_ptrs=None, gU_ptrs=None):
         """mg_batch_solver_adjoint on sequences of device addresses (one N x N fp64 array per instance, 16-byte aligned), on the
@@ -2356,6 +2516,36 @@ def solve_batched_reaction(F, s, U=None, L=1.0, coef=None, krylov=0, **opts):
         if krylov:
             b.set_krylov(krylov)
         return b.solve(F, U)
+    finally:
+        b.close()
+
+
+def solve_semilinear_batched(F, U=None, L=1.0, kind="sinh", kappa=1.0, weight=None, coef=None, krylov=0, rtol=1e-8, atol=0.0,
+                             max_iters=20, max_backtracks=12, inner_rtol=None, inner_atol=None, **opts):
+    """solve_semilinear for B problems in one batched call (BatchSolver.newton_batch, include/mg_newton_batch.h); returns (U, infos),
+    infos.stats holding the call's figures.  F and U as solve_batched takes them; kappa: a scalar or B values; weight: None,
+    (N, N) shared by every instance, or (B, N, N) / a sequence of B; coef: None, or what solve_batched_coef takes as a; krylov =
+    m > 0 wraps every inner solve in GCR(m); kind, rtol, atol, max_iters and max_backtracks are the Newton iteration's, one set
+    for the batch; inner_rtol / inner_atol and **opts (shift, max_cycles, omega, ...) make the BatchSolver every Newton step
+    runs on.  Every instance is bit-identical to solve_semilinear(F_i, U_i, L, kind, kappa_i, w_i, coef=a_i, krylov=m, ...)."""
+    Fs, shared = _instances(F, "F") if not isinstance(F, DeviceGrid) else ([F], True)
+    if U is None:
+        B = 1 if shared else len(Fs)
+    else:
+        B = len(U) if isinstance(U, (list, tuple)) else (1 if isinstance(U, DeviceGrid) or len(U.shape) == 2 else int(U.shape[0]))
+    count = lambda x: 0 if x is None else len(x) if isinstance(x, (list, tuple)) else (int(x.shape[0]) if len(x.shape) == 3 else 1)
+    for name, v in (("rtol", inner_rtol), ("atol", inner_atol)):
+        if v is not None:
+            opts[name] = v
+    N = int(Fs[0].shape[-1])
+    b = BatchSolver(N, L, max_batch=max(B, count(coef), 1), **opts)
+    try:
+        if coef is not None:
+            b.set_coefficient(coef)
+        if krylov:
+            b.set_krylov(krylov)
+        return b.newton_batch(F, U, kind=kind, kappa=kappa, weight=weight, rtol=rtol, atol=atol, max_iters=max_iters,
+                        max_backtracks=max_backtracks)
     finally:
         b.close()
 

@@ -585,6 +585,17 @@ void reaction_check_batch(hipStream_t s, int n, size_t count, const NodeBatchIte
 void newton_residual(hipStream_t s, int N, double inv, double sd, int kind, double kappa, const double *A, const double *W,
                      const double *U, const double *dlt, double t, const double *F, double *V, double *D, double *S, double *part,
                      double *out);
+// the batched form of the pass (mg_newton_batch_kernels.hip, driven by mg_solve_batch.cpp; include/mg_newton_batch.h): one launch
+// over n instances, each running the code, the block partition and the summation order of its single launch (the bodies are
+// shared: mg_newton_impl.h).  items[z]: the arrays and the kappa of the instance in slot z; has_a / has_w / has_step: EVERY
+// instance's A / W / (dlt, V) is there (false: the slot is not read).  Partials at part + z*resnorm_partials(N), norms to out[z].
+struct NewtonBatchItem {
+    const double *A, *W, *U, *dlt, *F;
+    double *V, *D, *S;
+    double kappa;
+};
+void newton_residual_batch(hipStream_t s, int n, int N, double inv, double sd, int kind, bool has_a, bool has_w, bool has_step, double t,
+                           const NewtonBatchItem *items, double *part, double *out);
 // Krylov acceleration of the residual-tolerance solver (mg_krylov_kernels.hip, driven by mg_solve.cpp; the method and the
 // order of every operation: include/mg_krylov.h).  All sums run over the interior; no rim is read into a result or written.
 constexpr int KRYLOV_MAX_K = MG_KRYLOV_MAX_M - 1;   // stored directions an iteration orthogonalises against

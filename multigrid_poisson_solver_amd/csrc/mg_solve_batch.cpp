@@ -15,6 +15,9 @@
 // With a reaction set (include/mg_rx_batch.h) the cycle is the operator-by-operator one too, with or without a coefficient,
 // through the batched `_rx` kernels (mg_reaction_batch_kernels.hip): the level's reaction term rides in the slot `Fc` of the
 // sweep, residual and coarse-solve tables, which the recorded steps leave empty -- the steps themselves do not change.
+// mg_batch_solver_newton (include/mg_newton_batch.h) is Newton's method around that loop for all instances in lockstep: the
+// batched pass of mg_newton_batch_kernels.hip, and solve_instances below on the instances that still iterate, whose level-0
+// reaction term is whichever of the driver's two S sets holds the accepted iterate's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -71,6 +74,14 @@ struct mg_batch_solver {
     std::vector<const double *> kr_F;        // per instance: the cycle's F0 = r_i (MG_SMOOTHER=simple takes pointers by instance)
     std::vector<double *> kr_U;              // per instance: the cycle's U0 = z_k of this iteration
     int kr_log_m = 0, kr_n = 0;              // the m and the instances of the last accelerated solve
+    // batched Newton driver (include/mg_newton_batch.h; nothing of it is allocated before the first mg_batch_solver_newton)
+    double *nw_field = nullptr;              // 5 fields of max_batch instances each at the level-0 pitch: V, D, D', S', delta
+    void *nw_dev = nullptr, *nw_host = nullptr;   // one block in device and one in pinned memory: NewtonBlock (below)
+    hipEvent_t nw_ev_begin = nullptr, nw_ev_end = nullptr;
+    std::vector<double *> nw_S0;             // per instance: its level-0 reaction term while nw_on (either of its two S sets)
+    bool nw_on = false;                      // an inner solve of the driver is running: react_of takes level 0 from nw_S0
+    std::vector<std::vector<mg_newton_iter>> nw_hist;   // per instance of the last call
+    int nw_n = 0;                            // the instances of the last call
 };
 
 namespace {
@@ -97,6 +108,11 @@ void release(mg_batch_solver *s)
     if (s->kr_dev_tab) (void)hipFree(s->kr_dev_tab);
     if (s->kr_host_rb) (void)hipHostFree(s->kr_host_rb);
     if (s->kr_host_tab) (void)hipHostFree(s->kr_host_tab);
+    if (s->nw_field) (void)hipFree(s->nw_field);
+    if (s->nw_dev) (void)hipFree(s->nw_dev);
+    if (s->nw_host) (void)hipHostFree(s->nw_host);
+    if (s->nw_ev_begin) (void)hipEventDestroy(s->nw_ev_begin);
+    if (s->nw_ev_end) (void)hipEventDestroy(s->nw_ev_end);
     if (s->part) (void)hipFree(s->part);
     if (s->dev_rb) (void)hipFree(s->dev_rb);
     if (s->host_rb) (void)hipHostFree(s->host_rb);
@@ -111,9 +127,11 @@ void release(mg_batch_solver *s)
 // the cycle the tables are built for: with a coefficient or a reaction operator by operator, whatever mg_set_smoother says
 const SolveCycle &cycle_of(const mg_batch_solver *s) { return s->n_coef > 0 || s->n_react > 0 ? s->cyc_ops : s->cyc_fused; }
 
-// the level-l reaction term of instance i (copy i, or the one copy in shared mode); nullptr without a reaction
+// the level-l reaction term of instance i (copy i, or the one copy in shared mode); nullptr without a reaction.  Inside
+// mg_batch_solver_newton the level-0 term is the one of the driver's two S sets that holds the instance's accepted iterate's
 double *react_of(const mg_batch_solver *s, int l, int i)
 {
+    if (l == 0 && s->nw_on) return s->nw_S0[i];
     return s->n_react > 0 ? level(s, s->react, l, s->n_react == 1 ? 0 : i) : nullptr;
 }
 
@@ -301,10 +319,10 @@ bool krylov_read_back(mg_batch_solver *s, hipStream_t st)
 
 // The loop of include/mg_krylov.h for every instance of `act` (those above their tolerance after history[0]), each with its
 // own k, tolerance and restart decisions; one launch per kernel of the single solver's iteration over the active set
-// (include/mg_krylov_batch.h).  false on a HIP error.
+// (include/mg_krylov_batch.h).  members: the instances the solve started with, whose state is reset.  false on a HIP error.
 bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const double *const *F_dev, double *const *U_dev,
                           const std::vector<double> &tol, std::vector<mg_solve_result> &r, mg_batch_solve_stats &bs,
-                          std::vector<int> act)
+                          const std::vector<int> &members, std::vector<int> act)
 {
     const mg_solve_opts &o = s->o;
     const int N = s->N, m = s->kr_m, rec_len = m + 7, mb = s->max_batch;
@@ -315,7 +333,7 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
     const KrylovTables host = krylov_tables(s->kr_host_tab, mb), dev = krylov_tables(s->kr_dev_tab, mb);
     s->kr_log_m = m;
     s->kr_n = n;
-    for (int i = 0; i < n; ++i) {
+    for (int i : members) {   // (the instances of this solve: 0 .. n-1, or those of a Newton call that still iterate)
         s->kr_k[i] = s->kr_records[i] = 0;
         s->kr_brk[i] = 0;
     }
@@ -444,6 +462,226 @@ bool krylov_iterate_batch(mg_batch_solver *s, hipStream_t st, int n, const doubl
         act.swap(next);
     }
     return MG_HIP(hipMemcpyAsync(s->kr_log_host.data(), s->kr_log, (size_t)n * log_stride * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+// the F and U of the n instances of a call: none NULL or misaligned, no U overlapping another U or any F
+bool instances_ok(const char *who, const mg_batch_solver *s, int n, const double *const *F_dev, double *const *U_dev)
+{
+    const size_t bytes = (size_t)s->N * s->N * sizeof(double);
+    for (int i = 0; i < n; ++i) {
+        if (!F_dev[i] || !U_dev[i]) {
+            fail(MG_ERR_ARG, "%s: NULL F or U of instance %d", who, i);
+            return false;
+        }
+        if (((uintptr_t)F_dev[i] | (uintptr_t)U_dev[i]) % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: F and U of instance %d must be 16-byte aligned", who, i);
+            return false;
+        }
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (j > i && overlap(U_dev[i], U_dev[j], bytes)) {
+                fail(MG_ERR_ARG, "%s: U of instances %d and %d overlap", who, i, j);
+                return false;
+            }
+            if (overlap(U_dev[i], F_dev[j], bytes)) {
+                fail(MG_ERR_ARG, "%s: U of instance %d overlaps F of instance %d", who, i, j);
+                return false;
+            }
+        }
+    return true;
+}
+
+// mg_batch_solver_solve's loop on the instances `start` of a call of n (ascending positions: 0 .. n-1 for mg_batch_solver_solve
+// itself; for mg_batch_solver_newton those that still iterate).  F_dev, U_dev, r, the level storage, the reaction copies and the
+// Krylov state are indexed by the position in the call, tables and read-backs by active slot; r[i] and history[i] of the
+// instances of `start` arrive zeroed.  Returns MG_SOLVE_CONVERGED, MG_SOLVE_NOT_CONVERGED (over `start`) or MG_ERR_HIP.
+int solve_instances(mg_batch_solver *s, int n, const double *const *F_dev, double *const *U_dev, const std::vector<int> &start,
+                    std::vector<mg_solve_result> &r, mg_batch_solve_stats &bs)
+{
+    const hipStream_t st = ctx().stream;
+    const mg_solve_opts &o = s->o;
+    const int mb = s->max_batch;
+    const bool ops = s->n_coef > 0 || s->n_react > 0;   // (the operator-by-operator cycle, whatever mg_set_smoother says)
+    const bool simple = ctx().smoother == SMOOTHER_SIMPLE;
+    std::vector<int> act(start);
+    std::vector<double> tol(n);
+    const int n0 = (int)start.size();
+    auto build = [&]() {
+        for (size_t j = 0; j < act.size(); ++j)
+            fill_slot(s, cycle_of(s), (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
+        return upload_tables(s, st);
+    };
+    if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return MG_ERR_HIP;
+    if (!build()) return MG_ERR_HIP;
+    bs.launches += norms(s, st, n0, false, rb_ref(s->dev_rb, mb));
+    bs.launches += norms_res(s, st, n0, rb_res(s->dev_rb));
+    if (!read_back(s, st)) return MG_ERR_HIP;
+    std::vector<int> next;
+    for (int j = 0; j < n0; ++j) {
+        const int i = start[j];
+        r[i].ref_norm = rb_ref(s->host_rb, mb)[j];
+        r[i].res0 = r[i].res = rb_res(s->host_rb)[j];
+        s->history[i].push_back(r[i].res);
+        tol[i] = std::fmax(o.rtol * r[i].ref_norm, o.atol);
+        if (!(r[i].res <= tol[i]) && o.max_cycles > 0) next.push_back(i);
+    }
+    if (s->kr_m > 0) {   // (the plain loop below then has nothing to do)
+        if (!krylov_iterate_batch(s, st, n, F_dev, U_dev, tol, r, bs, start, next)) return MG_ERR_HIP;
+        next.clear();
+    }
+    while (!next.empty()) {
+        if (next != act) {   // the active set changed: compact it, rebuild and upload the tables
+            act.swap(next);
+            if (!build()) return MG_ERR_HIP;
+        }
+        const int na = (int)act.size();
+        bs.launches += simple && !ops ? vcycle_simple_each(s, st, act, F_dev, U_dev) : run_cycle_batch(s, st, cycle_of(s), na);
+        bs.launches += norms_res(s, st, na, rb_res(s->dev_rb));
+        if (!read_back(s, st)) return MG_ERR_HIP;
+        next.clear();
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j];
+            r[i].res = rb_res(s->host_rb)[j];
+            s->history[i].push_back(r[i].res);
+            r[i].cycles += 1;
+            if (rb_state(s->host_rb, mb)[4 * j + 2]) r[i].coarse_capped = 1;
+            if (r[i].cycles > bs.cycles) bs.cycles = r[i].cycles;
+            if (!(r[i].res <= tol[i]) && r[i].cycles < o.max_cycles) next.push_back(i);
+        }
+    }
+    if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return MG_ERR_HIP;
+    float ms = 0.0f;
+    if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) bs.device_ms = ms;
+    bool all = true;
+    for (int i : start) {
+        r[i].converged = r[i].res <= tol[i] ? 1 : 0;
+        r[i].status = r[i].converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED;
+        all = all && r[i].converged;
+    }
+    return all ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED;
+}
+
+// ------------------------------------------------------------------ batched Newton driver (include/mg_newton_batch.h)
+// the driver's tables and norms, one block in pinned and one in device memory: per level below the finest the coarsening of S
+// (in = level l, out = level l + 1) by slot of the iterating instances, which also serves the copy home; the pass's items by slot
+// of its launch; the norms of that launch by slot.  The solver's own tables are not borrowed: a solve rewrites them on the host
+// while an upload enqueued here could still be reading them.
+struct NewtonBlock {
+    NodeBatchItem *coarsen;   // [max(nl - 1, 1)][mb]
+    k::NewtonBatchItem *pass;
+    double *norms;
+};
+size_t newton_block_bytes(int nl, int mb)
+{
+    return (size_t)mb * ((size_t)std::max(nl - 1, 1) * sizeof(NodeBatchItem) + sizeof(k::NewtonBatchItem) + sizeof(double));
+}
+NewtonBlock newton_block(void *base, int nl, int mb)
+{
+    NewtonBlock b;
+    b.coarsen = static_cast<NodeBatchItem *>(base);
+    b.pass = reinterpret_cast<k::NewtonBatchItem *>(b.coarsen + (size_t)std::max(nl - 1, 1) * mb);
+    b.norms = reinterpret_cast<double *>(b.pass + mb);
+    return b;
+}
+
+// what the first mg_batch_solver_newton allocates, all for max_batch instances (the byte count: include/mg_newton_batch.h);
+// later calls find everything there.  The reaction's level storage is replaced only when it holds fewer instances than
+// max_batch -- no reaction is set here, so nothing of value is in it.  false on a HIP error (the next call starts over).
+bool newton_storage(mg_batch_solver *s)
+{
+    const int nl = (int)s->sizes.size(), mb = s->max_batch;
+    const hipStream_t st = ctx().stream;
+    bool poisoned = false;
+    if (!s->coef_flags &&
+        !(MG_HIP(hipMalloc((void **)&s->coef_flags, mb * sizeof(int))) &&
+          MG_HIP(hipHostMalloc((void **)&s->host_coef_flags, mb * sizeof(int), hipHostMallocDefault)))) {
+        if (s->coef_flags) { (void)hipFree(s->coef_flags); s->coef_flags = nullptr; }
+        return false;
+    }
+    if (s->react_cap < mb) {
+        std::vector<double *> fresh(nl, nullptr);
+        for (int l = 0; l < nl; ++l)
+            if (!MG_HIP(hipMalloc((void **)&fresh[l], s->pitch[l] * mb * sizeof(double)))) {
+                for (double *p : fresh) if (p) (void)hipFree(p);
+                return false;
+            }
+        if (!MG_HIP(hipStreamSynchronize(st))) {   // (nothing enqueued still reads the old set)
+            for (double *p : fresh) (void)hipFree(p);
+            return false;
+        }
+        for (double *p : s->react) if (p) (void)hipFree(p);
+        s->react.swap(fresh);
+        s->react_cap = mb;
+        if (pool_poison_wanted()) {
+            for (int l = 0; l < nl; ++l) poison_block(s->react[l], s->pitch[l] * mb * sizeof(double));
+            poisoned = true;
+        }
+    }
+    if (!s->nw_field) {
+        const size_t field_bytes = 5 * s->pitch[0] * mb * sizeof(double), block = newton_block_bytes(nl, mb);
+        double *field = nullptr;
+        void *dev = nullptr, *host = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (!(MG_HIP(hipMalloc((void **)&field, field_bytes)) && MG_HIP(hipMalloc(&dev, block)) &&
+              MG_HIP(hipHostMalloc(&host, block, hipHostMallocDefault)) && MG_HIP(hipEventCreate(&e0)) && MG_HIP(hipEventCreate(&e1)))) {
+            if (field) (void)hipFree(field);
+            if (dev) (void)hipFree(dev);
+            if (host) (void)hipHostFree(host);
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            return false;
+        }
+        std::memset(host, 0, block);
+        s->nw_field = field;
+        s->nw_dev = dev;
+        s->nw_host = host;
+        s->nw_ev_begin = e0;
+        s->nw_ev_end = e1;
+        s->nw_S0.assign(mb, nullptr);
+        s->nw_hist.resize(mb);
+        if (pool_poison_wanted()) {
+            poison_block(field, field_bytes);
+            poisoned = true;
+        }
+    }
+    return !poisoned || MG_HIP(hipStreamSynchronize(st));
+}
+
+bool newton_kind_ok(const char *who, int kind)
+{
+    if (kind == MG_NEWTON_CUBIC || kind == MG_NEWTON_SINH || kind == MG_NEWTON_EXP) return true;
+    fail(MG_ERR_ARG, "%s: unknown kind %d (MG_NEWTON_CUBIC = 0, MG_NEWTON_SINH = 1, MG_NEWTON_EXP = 2)", who, kind);
+    return false;
+}
+
+// a count of optional per-instance arrays (0 / 1 shared / n) and its entries
+bool optional_arrays_ok(const char *who, const char *what, int n, int count, const double *const *arr)
+{
+    if (count != 0 && count != 1 && count != n) {
+        fail(MG_ERR_ARG, "%s: %d %s arrays for %d instances (0: none, 1: one shared by all, or one per instance)", who, count, what, n);
+        return false;
+    }
+    if ((count == 0) != (arr == nullptr)) {
+        fail(MG_ERR_ARG, "%s: %d %s arrays need %s", who, count, what, count == 0 ? "a NULL array" : "an array of device pointers");
+        return false;
+    }
+    for (int i = 0; i < count; ++i)
+        if (!arr[i] || (uintptr_t)arr[i] % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: the %s of instance %d is NULL or not 16-byte aligned", who, what, i);
+            return false;
+        }
+    return true;
+}
+
+bool kappas_ok(const char *who, int n, const double *kappa)
+{
+    for (int i = 0; i < n; ++i)
+        if (!(kappa[i] >= 0.0) || !std::isfinite(kappa[i])) {
+            fail(MG_ERR_ARG, "%s: kappa = %g of instance %d must be finite and >= 0", who, kappa[i], i);
+            return false;
+        }
+    return true;
 }
 
 }  // namespace
@@ -602,88 +840,10 @@ int mg_batch_solver_solve(mg_batch_solver *s, int n, const double *const *F_dev,
         return finish(MG_ERR_ARG);
     }
     for (int i = 0; i < n; ++i) s->history[i].clear();
-    const size_t bytes = (size_t)s->N * s->N * sizeof(double);
-    for (int i = 0; i < n; ++i) {
-        if (!F_dev[i] || !U_dev[i]) {
-            fail(MG_ERR_ARG, "mg_batch_solver_solve: NULL F or U of instance %d", i);
-            return finish(MG_ERR_ARG);
-        }
-        if (((uintptr_t)F_dev[i] | (uintptr_t)U_dev[i]) % 16 != 0) {
-            fail(MG_ERR_ARG, "mg_batch_solver_solve: F and U of instance %d must be 16-byte aligned", i);
-            return finish(MG_ERR_ARG);
-        }
-    }
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            if (j > i && overlap(U_dev[i], U_dev[j], bytes)) {
-                fail(MG_ERR_ARG, "mg_batch_solver_solve: U of instances %d and %d overlap", i, j);
-                return finish(MG_ERR_ARG);
-            }
-            if (overlap(U_dev[i], F_dev[j], bytes)) {
-                fail(MG_ERR_ARG, "mg_batch_solver_solve: U of instance %d overlaps F of instance %d", i, j);
-                return finish(MG_ERR_ARG);
-            }
-        }
-    const hipStream_t st = ctx().stream;
-    const mg_solve_opts &o = s->o;
-    const int mb = s->max_batch;
-    const bool ops = s->n_coef > 0 || s->n_react > 0;   // (the operator-by-operator cycle, whatever mg_set_smoother says)
-    const bool simple = ctx().smoother == SMOOTHER_SIMPLE;
-    std::vector<int> act(n);
-    std::vector<double> tol(n);
-    for (int i = 0; i < n; ++i) act[i] = i;
-    auto build = [&]() {
-        for (size_t j = 0; j < act.size(); ++j)
-            fill_slot(s, cycle_of(s), (int)j, F_dev[act[j]], U_dev[act[j]], act[j]);
-        return upload_tables(s, st);
-    };
-    if (!MG_HIP(hipEventRecord(s->ev_begin, st))) return finish(MG_ERR_HIP);
-    if (!build()) return finish(MG_ERR_HIP);
-    bs.launches += norms(s, st, n, false, rb_ref(s->dev_rb, mb));
-    bs.launches += norms_res(s, st, n, rb_res(s->dev_rb));
-    if (!read_back(s, st)) return finish(MG_ERR_HIP);
-    std::vector<int> next;
-    for (int i = 0; i < n; ++i) {
-        r[i].ref_norm = rb_ref(s->host_rb, mb)[i];
-        r[i].res0 = r[i].res = rb_res(s->host_rb)[i];
-        s->history[i].push_back(r[i].res);
-        tol[i] = std::fmax(o.rtol * r[i].ref_norm, o.atol);
-        if (!(r[i].res <= tol[i]) && o.max_cycles > 0) next.push_back(i);
-    }
-    if (s->kr_m > 0) {   // (the plain loop below then has nothing to do)
-        if (!krylov_iterate_batch(s, st, n, F_dev, U_dev, tol, r, bs, next)) return finish(MG_ERR_HIP);
-        next.clear();
-    }
-    while (!next.empty()) {
-        if (next != act) {   // the active set changed: compact it, rebuild and upload the tables
-            act.swap(next);
-            if (!build()) return finish(MG_ERR_HIP);
-        }
-        const int na = (int)act.size();
-        bs.launches += simple && !ops ? vcycle_simple_each(s, st, act, F_dev, U_dev) : run_cycle_batch(s, st, cycle_of(s), na);
-        bs.launches += norms_res(s, st, na, rb_res(s->dev_rb));
-        if (!read_back(s, st)) return finish(MG_ERR_HIP);
-        next.clear();
-        for (int j = 0; j < na; ++j) {
-            const int i = act[j];
-            r[i].res = rb_res(s->host_rb)[j];
-            s->history[i].push_back(r[i].res);
-            r[i].cycles += 1;
-            if (rb_state(s->host_rb, mb)[4 * j + 2]) r[i].coarse_capped = 1;
-            if (r[i].cycles > bs.cycles) bs.cycles = r[i].cycles;
-            if (!(r[i].res <= tol[i]) && r[i].cycles < o.max_cycles) next.push_back(i);
-        }
-    }
-    if (!MG_HIP(hipEventRecord(s->ev_end, st)) || !MG_HIP(hipEventSynchronize(s->ev_end))) return finish(MG_ERR_HIP);
-    float ms = 0.0f;
-    if (MG_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end))) bs.device_ms = ms;
-    bool all = true;
-    for (int i = 0; i < n; ++i) {
-        r[i].converged = r[i].res <= tol[i] ? 1 : 0;
-        r[i].status = r[i].converged ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED;
-        all = all && r[i].converged;
-    }
-    return finish(all ? MG_SOLVE_CONVERGED : MG_SOLVE_NOT_CONVERGED);
+    if (!instances_ok("mg_batch_solver_solve", s, n, F_dev, U_dev)) return finish(MG_ERR_ARG);
+    std::vector<int> all(n);
+    for (int i = 0; i < n; ++i) all[i] = i;
+    return finish(solve_instances(s, n, F_dev, U_dev, all, r, bs));
 }
 
 void mg_batch_solver_destroy(mg_batch_solver *s)
@@ -893,6 +1053,323 @@ int mg_batch_solver_set_reaction(mg_batch_solver *s, int n, const double *const 
 }
 
 int mg_batch_solver_has_reaction(const mg_batch_solver *s) { return s ? s->n_react : 0; }
+
+// ------------------------------------------------------------------ semilinear problem (include/mg_newton_batch.h)
+int mg_batch_solver_newton(mg_batch_solver *s, int n, int kind, const double *kappa, int n_w, const double *const *w_dev,
+                           const double *const *F_dev, double *const *U_dev, const mg_newton_opts *opts, mg_newton_result *out,
+                           mg_batch_newton_stats *stats)
+{
+    const char *who = "mg_batch_solver_newton";
+    mg_batch_newton_stats ns;
+    std::memset(&ns, 0, sizeof ns);
+    std::vector<mg_newton_result> r(n > 0 ? (size_t)n : 0);
+    for (auto &x : r) std::memset(&x, 0, sizeof x);
+    auto finish = [&](int status) {
+        if (out && s && n >= 1 && n <= s->max_batch)
+            for (int i = 0; i < n; ++i) {
+                if (status > 0) r[i].status = status;
+                r[i].n_history = i < s->nw_n ? (int)s->nw_hist[i].size() : 0;
+                out[i] = r[i];
+            }
+        if (stats) *stats = ns;
+        return status;
+    };
+    if (!require_ready(who)) return finish(MG_ERR_NOT_INIT);
+    if (!s || !kappa || !F_dev || !U_dev) {
+        fail(MG_ERR_ARG, "%s: NULL solver, kappa or array", who);
+        return finish(MG_ERR_ARG);
+    }
+    if (s->n_react > 0) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the driver installs the Newton matrices' own (take yours away with "
+                                 "mg_batch_solver_set_reaction(s, 0, NULL), or put it into w)", who);
+        return finish(MG_ERR_UNSUPPORTED);
+    }
+    if (n < 1 || n > s->max_batch) {
+        fail(MG_ERR_ARG, "%s: n = %d outside [1, max_batch = %d]", who, n, s->max_batch);
+        return finish(MG_ERR_ARG);
+    }
+    if (s->n_coef > 1 && n > s->n_coef) {
+        fail(MG_ERR_ARG, "%s: n = %d instances, but the solver holds %d coefficients (one per instance)", who, n, s->n_coef);
+        return finish(MG_ERR_ARG);
+    }
+    if (!optional_arrays_ok(who, "w", n, n_w, w_dev) || !newton_kind_ok(who, kind) || !kappas_ok(who, n, kappa) ||
+        !instances_ok(who, s, n, F_dev, U_dev))
+        return finish(MG_ERR_ARG);
+    mg_newton_opts o;
+    mg_newton_opts_default(&o);
+    if (opts) o = *opts;
+    if (!(o.rtol >= 0.0) || !(o.atol >= 0.0) || !std::isfinite(o.rtol) || !std::isfinite(o.atol) || o.max_iters < 0 || o.max_backtracks < 0) {
+        fail(MG_ERR_ARG, "%s: rtol = %g, atol = %g (non-negative, finite), max_iters = %d, max_backtracks = %d (>= 0 each)", who, o.rtol,
+             o.atol, o.max_iters, o.max_backtracks);
+        return finish(MG_ERR_ARG);
+    }
+    const hipStream_t st = ctx().stream;
+    const int N = s->N, nl = (int)s->sizes.size(), mb = s->max_batch;
+    const size_t n0 = (size_t)N * N, p0 = s->pitch[0];
+    const bool has_a = s->n_coef > 0, has_w = n_w > 0;
+    if (!newton_storage(s)) return finish(MG_ERR_HIP);
+    if (has_w) {   // one launch over the n_w arrays, a flag each, one read-back, as mg_batch_solver_set_reaction checks s
+        for (int i = 0; i < n_w; ++i) s->host_tab[i] = NodeBatchItem{w_dev[i], nullptr, nullptr, nullptr, nullptr};
+        if (!MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)n_w * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)) ||
+            !MG_HIP(hipMemsetAsync(s->coef_flags, 0, n_w * sizeof(int), st)))
+            return finish(MG_ERR_HIP);
+        k::reaction_check_batch(st, n_w, n0, s->dev_tab, s->coef_flags);
+        ns.launches += 1;
+        if (!MG_HIP(hipMemcpyAsync(s->host_coef_flags, s->coef_flags, n_w * sizeof(int), hipMemcpyDeviceToHost, st)) ||
+            !MG_HIP(hipStreamSynchronize(st)))
+            return finish(MG_ERR_HIP);
+        for (int i = 0; i < n_w; ++i)
+            if (s->host_coef_flags[i]) {
+                fail(MG_ERR_ARG, "%s: every value of w must be finite and >= 0 (instance %d has one that is not)", who, i);
+                return finish(MG_ERR_ARG);
+            }
+    }
+    // From here on the call's records replace the last call's.  Per instance: cur holds the last accepted iterate, D its
+    // right-hand side and S its Newton matrix's term; oth, D2 and S2 take the next trial.  U_dev[i] is one of (cur, oth): when
+    // the instance ends on the other one, the iterate is copied home.
+    struct Inst {
+        double *cur, *oth, *D, *D2, *S, *S2, *dlt;
+        double rn, tol;
+        bool stalled;
+    };
+    std::vector<Inst> in(n);
+    s->nw_n = n;
+    for (int i = 0; i < n; ++i) {
+        s->nw_hist[i].clear();
+        s->history[i].clear();
+        in[i] = Inst{U_dev[i], s->nw_field + (0 * (size_t)mb + i) * p0, s->nw_field + (1 * (size_t)mb + i) * p0,
+                     s->nw_field + (2 * (size_t)mb + i) * p0, level(s, s->react, 0, i), s->nw_field + (3 * (size_t)mb + i) * p0,
+                     s->nw_field + (4 * (size_t)mb + i) * p0, 0.0, 0.0, false};
+    }
+    if (s->kr_m > 0) {
+        s->kr_n = n;
+        for (int i = 0; i < n; ++i) {
+            s->kr_records[i] = 0;
+            s->kr_brk[i] = 0;
+        }
+    }
+    const LevelConsts &c0 = s->lc[0];
+    const NewtonBlock host = newton_block(s->nw_host, nl, mb), dev = newton_block(s->nw_dev, nl, mb);
+    auto coef_of = [&](int i) -> const double * { return has_a ? level(s, s->coef, 0, s->n_coef == 1 ? 0 : i) : nullptr; };
+    // the pass over the instances `sub` (step: the trial at t into the second set), their norms into host.norms by slot
+    auto pass = [&](const std::vector<int> &sub, bool step, double t) {
+        const int m = (int)sub.size();
+        for (int j = 0; j < m; ++j) {
+            const Inst &x = in[sub[j]];
+            host.pass[j] = k::NewtonBatchItem{coef_of(sub[j]), has_w ? w_dev[n_w == 1 ? 0 : sub[j]] : nullptr, x.cur, step ? x.dlt : nullptr,
+                                              F_dev[sub[j]], step ? x.oth : nullptr, step ? x.D2 : x.D, step ? x.S2 : x.S, kappa[sub[j]]};
+        }
+        if (!MG_HIP(hipMemcpyAsync(dev.pass, host.pass, (size_t)m * sizeof(k::NewtonBatchItem), hipMemcpyHostToDevice, st))) return false;
+        k::newton_residual_batch(st, m, N, c0.inv, c0.sd, kind, has_a, has_w, step, t, dev.pass, s->part, dev.norms);
+        ns.launches += 2;
+        return MG_HIP(hipMemcpyAsync(host.norms, dev.norms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st)) &&
+               MG_HIP(hipEventRecord(s->ev_sync, st)) && MG_HIP(hipEventSynchronize(s->ev_sync));
+    };
+    // every instance whose accepted iterate sits in solver storage goes home in one launch
+    auto home = [&]() {
+        int m = 0;
+        for (int i = 0; i < n; ++i)
+            if (in[i].cur != U_dev[i]) host.coarsen[m++] = NodeBatchItem{in[i].cur, nullptr, nullptr, U_dev[i], nullptr};
+        if (m == 0) return true;
+        if (!MG_HIP(hipMemcpyAsync(dev.coarsen, host.coarsen, (size_t)m * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st))) return false;
+        k::copy_batch(st, m, n0, dev.coarsen);
+        ns.launches += 1;
+        return MG_HIP(hipStreamSynchronize(st));
+    };
+    if (!MG_HIP(hipEventRecord(s->nw_ev_begin, st))) return finish(MG_ERR_HIP);
+    std::vector<int> act(n), next, pending;
+    for (int i = 0; i < n; ++i) act[i] = i;
+    if (!pass(act, false, 0.0)) return finish(MG_ERR_HIP);
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(host.norms[i])) {
+            fail(MG_ERR_ARG, "%s: the residual of the start of instance %d is not finite (%g)", who, i, host.norms[i]);
+            return finish(MG_ERR_ARG);
+        }
+    next.clear();
+    for (int i = 0; i < n; ++i) {
+        in[i].rn = r[i].res0 = r[i].res = host.norms[i];
+        in[i].tol = std::fmax(o.atol, o.rtol * in[i].rn);
+        if (!(in[i].rn <= in[i].tol) && o.max_iters > 0) next.push_back(i);
+    }
+    act.swap(next);
+    std::vector<const double *> Dp(n, nullptr);
+    std::vector<double *> dl(n, nullptr);
+    std::vector<mg_solve_result> inner(n);
+    std::vector<mg_newton_iter> it(n);
+    for (int i = 0; i < n; ++i) dl[i] = in[i].dlt;
+    while (!act.empty()) {
+        const int na = (int)act.size();
+        for (int j = 0; j < na; ++j) {
+            const int i = act[j];
+            for (int l = 0; l + 1 < nl; ++l)
+                host.coarsen[(size_t)l * mb + j] =
+                    NodeBatchItem{l == 0 ? in[i].S : level(s, s->react, l, i), nullptr, nullptr, level(s, s->react, l + 1, i), nullptr};
+            s->nw_S0[i] = in[i].S;
+            Dp[i] = in[i].D;
+            std::memset(&inner[i], 0, sizeof inner[i]);
+            s->history[i].clear();
+        }
+        int status = MG_OK;
+        if (nl > 1 && !MG_HIP(hipMemcpyAsync(dev.coarsen, host.coarsen, (size_t)(nl - 1) * mb * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)))
+            status = MG_ERR_HIP;
+        if (status == MG_OK) {
+            for (int l = 0; l + 1 < nl; ++l)
+                k::coef_coarsen_batch(st, na, s->sizes[l], s->sizes[l + 1], dev.coarsen + (size_t)l * mb,
+                                      restrict_table(s->sizes[l], s->sizes[l + 1]));
+            ns.launches += nl - 1;
+            // (the delta of all n instances are one region: one memset, whatever the number that still iterate)
+            if (!MG_HIP(hipMemsetAsync(s->nw_field + 4 * (size_t)mb * p0, 0, (size_t)n * p0 * sizeof(double), st))) status = MG_ERR_HIP;
+        }
+        if (status == MG_OK) {
+            mg_batch_solve_stats bs;
+            std::memset(&bs, 0, sizeof bs);
+            s->n_react = n;   // the driver's own per-instance reaction, for the length of the inner solve
+            s->nw_on = true;
+            status = solve_instances(s, n, Dp.data(), dl.data(), act, inner, bs);
+            s->nw_on = false;
+            s->n_react = 0;
+            ns.launches += bs.launches;
+            ns.inner_cycles += bs.cycles;
+        }
+        if (status > 0) {
+            (void)home();
+            return finish(status);
+        }
+        for (int i : act) {
+            it[i] = mg_newton_iter{in[i].rn, 0.0, 0, inner[i].cycles, inner[i].converged, inner[i].coarse_capped};
+            r[i].inner_cycles += inner[i].cycles;
+        }
+        // the line search in rounds: round k is one launch at t = 2^-k over the instances that have not accepted yet
+        pending = act;
+        next.clear();
+        double t = 1.0;
+        while (!pending.empty()) {
+            if (!pass(pending, true, t)) {
+                (void)home();
+                return finish(MG_ERR_HIP);
+            }
+            ns.trial_rounds += 1;
+            std::vector<int> again;
+            for (size_t j = 0; j < pending.size(); ++j) {
+                const int i = pending[j];
+                Inst &x = in[i];
+                const double rt = host.norms[j];
+                r[i].trials += 1;
+                if (std::isfinite(rt) && rt < (1.0 - 1e-4 * t) * x.rn) {
+                    std::swap(x.cur, x.oth);
+                    std::swap(x.D, x.D2);
+                    std::swap(x.S, x.S2);
+                    x.rn = rt;
+                    it[i].res = rt;
+                    it[i].t = t;
+                    s->nw_hist[i].push_back(it[i]);
+                    r[i].iterations += 1;
+                    if (r[i].iterations > ns.iterations) ns.iterations = r[i].iterations;
+                    continue;
+                }
+                it[i].backtracks += 1;
+                if (it[i].backtracks > o.max_backtracks) {
+                    s->nw_hist[i].push_back(it[i]);
+                    x.stalled = true;
+                } else {
+                    again.push_back(i);
+                }
+            }
+            pending.swap(again);
+            t *= 0.5;
+        }
+        for (int i : act)
+            if (!in[i].stalled && !(in[i].rn <= in[i].tol) && r[i].iterations < o.max_iters) next.push_back(i);
+        act.swap(next);
+    }
+    if (!home()) return finish(MG_ERR_HIP);
+    if (!MG_HIP(hipEventRecord(s->nw_ev_end, st)) || !MG_HIP(hipEventSynchronize(s->nw_ev_end))) return finish(MG_ERR_HIP);
+    float ms = 0.0f;
+    if (MG_HIP(hipEventElapsedTime(&ms, s->nw_ev_begin, s->nw_ev_end))) ns.device_ms = ms;
+    bool all = true;
+    for (int i = 0; i < n; ++i) {
+        r[i].res = in[i].rn;
+        r[i].converged = in[i].rn <= in[i].tol ? 1 : 0;
+        r[i].status = r[i].converged ? MG_NEWTON_CONVERGED : in[i].stalled ? MG_NEWTON_STALLED : MG_NEWTON_NOT_CONVERGED;
+        all = all && r[i].converged;
+    }
+    return finish(all ? MG_NEWTON_CONVERGED : MG_NEWTON_NOT_CONVERGED);
+}
+
+int mg_batch_solver_newton_history(const mg_batch_solver *s, int i, mg_newton_iter *out, int cap)
+{
+    if (!s || i < 0 || i >= s->nw_n) return 0;
+    const int n = (int)s->nw_hist[i].size();
+    for (int j = 0; out && j < n && j < cap; ++j) out[j] = s->nw_hist[i][j];
+    return n;
+}
+
+int mg_batch_solver_newton_inner_history(const mg_batch_solver *s, int i, double *out, int cap)
+{
+    if (!s || i < 0 || i >= s->nw_n) return 0;
+    const int n = (int)s->history[i].size();
+    for (int j = 0; out && j < n && j < cap; ++j) out[j] = s->history[i][j];
+    return n;
+}
+
+int mg_nonlinearResidual_batch(int n, int N, double L, double shift, int n_a, const double *const *a_dev, int kind, const double *kappa,
+                               int n_w, const double *const *w_dev, const double *const *U, const double *const *dlt, double t,
+                               const double *const *F, double *const *V, double *const *D, double *const *S, double *norms_out)
+{
+    const char *who = "mg_nonlinearResidual_batch";
+    if (!require_ready(who)) return MG_ERR_NOT_INIT;
+    if (n < 1 || n > 65535 || N < 3 || !(L > 0.0) || !std::isfinite(L) || !(shift >= 0.0) || !std::isfinite(shift)) {
+        fail(MG_ERR_ARG, "%s: n = %d inside [1, 65535], N = %d (at least 3), L = %g (positive, finite), shift = %g (finite, >= 0)", who, n, N,
+             L, shift);
+        return MG_ERR_ARG;
+    }
+    if (!kappa || !U || !F || !D || !S || (dlt && (!V || !std::isfinite(t)))) {
+        fail(MG_ERR_ARG, "%s: NULL kappa, U, F, D or S; with dlt, V must be there and t = %g finite", who, t);
+        return MG_ERR_ARG;
+    }
+    if (!optional_arrays_ok(who, "a", n, n_a, a_dev) || !optional_arrays_ok(who, "w", n, n_w, w_dev) || !newton_kind_ok(who, kind) ||
+        !kappas_ok(who, n, kappa))
+        return MG_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+        const bool there = U[i] && F[i] && D[i] && S[i] && (!dlt || (dlt[i] && V[i]));
+        const uintptr_t bits = (uintptr_t)U[i] | (uintptr_t)F[i] | (uintptr_t)D[i] | (uintptr_t)S[i] |
+                               (dlt && there ? (uintptr_t)dlt[i] | (uintptr_t)V[i] : 0);
+        if (!there || bits % 16 != 0) {
+            fail(MG_ERR_ARG, "%s: a NULL or not 16-byte aligned array of instance %d", who, i);
+            return MG_ERR_ARG;
+        }
+    }
+    const hipStream_t st = ctx().stream;
+    const size_t np = k::resnorm_partials(N);
+    const double dx = L / (double)(N - 1), dx2 = dx * dx;
+    std::vector<k::NewtonBatchItem> items(n);
+    for (int i = 0; i < n; ++i)
+        items[i] = k::NewtonBatchItem{n_a ? a_dev[n_a == 1 ? 0 : i] : nullptr, n_w ? w_dev[n_w == 1 ? 0 : i] : nullptr, U[i],
+                                      dlt ? dlt[i] : nullptr, F[i], dlt ? V[i] : nullptr, D[i], S[i], kappa[i]};
+    k::NewtonBatchItem *tab = nullptr;
+    double *buf = nullptr;   // the partials of every instance and, behind them, the n norms
+    if (!MG_HIP(hipMalloc((void **)&tab, (size_t)n * sizeof(k::NewtonBatchItem)))) return MG_ERR_HIP;
+    if (!MG_HIP(hipMalloc((void **)&buf, ((size_t)n * np + n) * sizeof(double)))) {
+        (void)hipFree(tab);
+        return MG_ERR_HIP;
+    }
+    std::vector<double> host(n, 0.0);
+    bool ok = MG_HIP(hipMemcpyAsync(tab, items.data(), (size_t)n * sizeof(k::NewtonBatchItem), hipMemcpyHostToDevice, st)) &&
+              MG_HIP(hipStreamSynchronize(st));   // (items is pageable host memory of this frame)
+    if (ok) {
+        // (timed for scripts/bench_newton_batched.py: the bytes of mg_nonlinearResidual's scope, times n)
+        const double pts = (double)N * N * n;
+        ProfScope ps(dlt ? "newton_step_batch" : "newton_residual_batch", N, pts * (32.0 + (n_a ? 8.0 : 0.0) + (n_w ? 8.0 : 0.0) + (dlt ? 16.0 : 0.0)));
+        k::newton_residual_batch(st, n, N, 1.0 / dx2, shift * dx2, kind, n_a > 0, n_w > 0, dlt != nullptr, t, tab, buf, buf + (size_t)n * np);
+    }
+    ok = ok && MG_HIP(hipMemcpyAsync(host.data(), buf + (size_t)n * np, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st)) &&
+         MG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(tab);
+    (void)hipFree(buf);
+    if (!ok) return MG_ERR_HIP;
+    for (int i = 0; norms_out && i < n; ++i) norms_out[i] = host[i];
+    return MG_OK;
+}
 
 // ------------------------------------------------------------------ Krylov acceleration (include/mg_krylov_batch.h)
 int mg_batch_solver_set_krylov(mg_batch_solver *s, int m)
