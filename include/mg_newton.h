@@ -13,7 +13,12 @@
  *   MG_NEWTON_EXP      e^u      e^u      g = gp = exp_libm(u)
  * exp_libm (csrc/mg_exp_libm.h) is the getSource kernel's exp: libm's algorithm in its FMA form, equal to the host's exp()
  * bit for bit where mg_source_is_bit_identical() says so, on its verified path |u| < 512.  The bit-for-bit contract of this
- * header covers |v| < 512; beyond it g^2 overflows the norm and a trial that goes there is rejected by the line search.
+ * header covers |v| < 512.  Beyond it exp_libm is the device library's exp(): a trial with v >= 512 is in practice rejected
+ * (g^2 overflows the norm for both kinds; e = +inf above 709.78 gives g = g' = +inf), and so is one with v <= -512 for
+ * MG_NEWTON_SINH, but MG_NEWTON_EXP REACHES v <= -512 IN ACCEPTED TRIALS: there g is tiny, the norm stays finite (F = +1e4 with
+ * zero rim data has its solution's minimum near -737).  What is guaranteed there is the class and the size of e, not libm's
+ * bits: +0 from -746 down and for -inf, NaN for NaN, otherwise a finite e >= 0, subnormal below -708.39, within 2 ulp of e^v
+ * (counted in the subnormal spacing where e^v is subnormal; measured 0.4984 ulp: tests/test_newton_exp_domain_gpu.py).
  * g' >= 0 makes every Newton matrix a reaction operator the solver accepts (mg_reaction.h: s >= 0).
  *
  * THE PASS (mg_nonlinearResidual; one kernel launch and the second stage of the norm).  At every point p:

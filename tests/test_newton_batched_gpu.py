@@ -236,6 +236,24 @@ def test_mixed_batch_at_defaults_equals_the_single_driver(mg, N, coef, kind):
     b.close()
 
 
+@pytest.mark.parametrize("N", [33, 514])
+def test_an_instance_beyond_minus_512_next_to_an_ordinary_one(mg, N):
+    """F == +1e4 with kind = "exp" (tests/test_newton_exp_domain_gpu.py: its solution has a minimum near -737, so accepted trials
+    evaluate exp through the device library's branch of exp_libm, into subnormal results) beside nref.problem at kappa = 10: per
+    instance U and the whole info dict of Solver.newton alone, in both orders"""
+    F, U0 = nref.problem(N)
+    inst = [(np.full((N, N), 1e4), np.zeros((N, N)), 1.0, np.ones((N, N))), (F, U0, 10.0, nref.smooth_weight(N))]
+    want = singles(mg, N, "exp", lambda i: None, inst)
+    assert all(info["converged"] for _, info, _ in want)
+    assert want[0][0].min() < -512.0 and np.abs(want[1][0]).max() < 512.0
+    b = mg.BatchSolver(N, 1.0, max_batch=2)
+    for order in ([0, 1], [1, 0]):
+        Us, infos = run_batch_in_guards(mg, b, "exp", inst, order)
+        assert_instances_equal(Us, infos, want, order, f"N={N} beyond -512, order {order}")
+        assert infos.stats["status"] == nref.CONVERGED and not b.has_reaction
+    b.close()
+
+
 @pytest.mark.parametrize("kind", nref.KINDS)
 @pytest.mark.parametrize("N", [33, 100])
 def test_stalled_and_capped_instances(mg, N, kind):

@@ -87,28 +87,43 @@ def test_pass_alone_bit_for_bit_inside_guard_bands(mg, N, coef, weight, kind):
 
 
 # ---------------------------------------------------------------- whole solves against the restatement
-@pytest.mark.parametrize("N,coef", [(33, None), (33, "exp"), (100, None), (100, "exp"), (257, None), (257, "exp"), (514, "exp")])
-def test_whole_solves_bit_identical_to_restatement(mg, oracle, N, coef):
-    """cubic with a smooth weight, inner solves of two cycles (unconverged: their steps are used and counted), three Newton
-    iterations: U after every iteration, the Newton history and the status with =="""
+def whole_solve_against_restatement(mg, oracle, N, coef, kind):
+    """a smooth weight at kappa = 10, inner solves of two cycles (unconverged: their steps are used and counted), three Newton
+    iterations: U after every iteration, the Newton history and the status with ==.  (tests/_newton_ref.py on the CPU: three
+    iterations are accepted without a backtrack for every kind at every size used here, |u| of order one.)"""
+    need_exp_bits(mg, kind)
     F, U0 = nref.problem(N)
     a, w, kappa = (None if coef is None else vref.field(coef, N)), nref.smooth_weight(N), 10.0
     inner = dict(rtol=0.0, max_cycles=2)
     margins, Us = [], []
-    want = nref.newton(oracle, a, "cubic", kappa, w, F, U0, 1.0, table=lib_table(mg), margins=margins, keep=Us, rtol=0.0,
+    want = nref.newton(oracle, a, kind, kappa, w, F, U0, 1.0, table=lib_table(mg), margins=margins, keep=Us, rtol=0.0,
                        max_iters=3, inner=inner)
-    ref.assert_qualified(margins, f"N={N} a={coef}")
+    ref.assert_qualified(margins, f"N={N} a={coef} {kind}")
     assert want["iterations"] == 3 and len(Us) == 3
     solver = mg.Solver(N, 1.0, coef=a, **inner)
     for k in (1, 2, 3):
-        got, info = solver.newton(F, U0, kind="cubic", kappa=kappa, weight=w, rtol=0.0, max_iters=k)
-        assert_bits(got, Us[k - 1], f"N={N} a={coef}: U after Newton iteration {k}")
+        got, info = solver.newton(F, U0, kind=kind, kappa=kappa, weight=w, rtol=0.0, max_iters=k)
+        assert_bits(got, Us[k - 1], f"N={N} a={coef} {kind}: U after Newton iteration {k}")
         assert info["history"] == want["history"][:k + 1], (info["history"], want["history"])
         assert info["status"] == nref.NOT_CONVERGED and info["iterations"] == k and not solver.has_reaction
         for s, x in zip(info["steps"], want["steps"]):
             assert (s["res"], s["t"], s["backtracks"], s["inner_cycles"], s["inner_converged"]) == \
                 (x["res"], x["t"], x["backtracks"], x["inner_cycles"], x["inner_converged"]), (s, x)
     solver.close()
+
+
+@pytest.mark.parametrize("N,coef", [(33, None), (33, "exp"), (100, None), (100, "exp"), (257, None), (257, "exp"), (514, "exp")])
+def test_whole_solves_bit_identical_to_restatement(mg, oracle, N, coef):
+    """cubic: no exp in it, so it runs on every host"""
+    whole_solve_against_restatement(mg, oracle, N, coef, "cubic")
+
+
+@pytest.mark.parametrize("kind", ["sinh", "exp"])
+@pytest.mark.parametrize("N,coef", [(33, None), (257, "exp"), (514, "exp")])
+def test_whole_solves_of_sinh_and_exp_bit_identical_to_restatement(mg, oracle, N, coef, kind):
+    """the kinds that go through exp_libm, |v| of order one (the verified path), where the engine's self-check vouches for the
+    host libm's bits: one column per lane (33, 257) and column pairs (514)"""
+    whole_solve_against_restatement(mg, oracle, N, coef, kind)
 
 
 def test_hard_cubic_start_reproduces_the_backtrack_sequence(mg, oracle):
