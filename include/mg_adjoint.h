@@ -31,6 +31,7 @@
  *
  * Out of scope, and not built: the derivative in shift; gradients through the heat stepper (mg_heat.h); a coefficient
  * shared by several instances of a batch (its gradient is the caller's sum of the per-instance gA); slab / multi-GPU plans.
+ * (The derivative in shift, and the adjoint with a reaction term or of a semilinear solve, are mg_adjoint_rx.h's.)
  *
  * Contract of every function below: synchronous, on the engine stream (mg_set_stream); N >= 3; device arrays 16-byte
  * aligned; no output overlaps an input or another output; bad arguments are refused with MG_ERR_ARG (mg_last_error) before

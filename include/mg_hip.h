@@ -519,6 +519,8 @@ void mg_batch_solver_destroy(mg_batch_solver *s);
 #include "mg_newton.h"
 #include "mg_rx_batch.h"
 #include "mg_newton_batch.h"
+/* the adjoint of solves with s(x, y) and of semilinear solves, gradients in s, sigma, w and kappa: mg_sourceGradient, ... */
+#include "mg_adjoint_rx.h"
 /* Neumann and mixed boundary kinds per side in the solver and the heat stepper: mg_solver_set_boundary, mg_neumannSource, ... */
 #include "mg_bc.h"
 /* the batched solver with the Krylov acceleration, GCR(m) per instance: mg_batch_solver_set_krylov, ... */

@@ -61,7 +61,8 @@
  *                           atol negative or not finite, max_iters or max_backtracks negative); a start whose residual is not
  *                           finite
  * The batched solver runs this driver for many instances in one call: mg_newton_batch.h.
- * Not built: the heat stepper, the adjoint of a semilinear solve, boundary kinds, a user-supplied g.
+ * Not built: the heat stepper, the adjoint of a semilinear solve, boundary kinds, a user-supplied g.  (The adjoint is built
+ * since, beside this header: mg_adjoint_rx.h, mg_solver_newton_adjoint.)
  */
 #ifndef MG_NEWTON_H
 #define MG_NEWTON_H

@@ -68,7 +68,8 @@
  *                           residual is not finite
  * The private batch solvers of the heat stepper and the eigensolver never call this; their launches do not change.
  * Not built: a kind or options per instance, boundary kinds, fmg, the adjoint of a semilinear solve, a semilinear heat
- * stepper, a user-supplied g.
+ * stepper, a user-supplied g.  (The adjoint is built since, beside this header: mg_adjoint_rx.h,
+ * mg_batch_solver_newton_adjoint.)
  */
 #ifndef MG_NEWTON_BATCH_H
 #define MG_NEWTON_BATCH_H

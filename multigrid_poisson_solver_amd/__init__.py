@@ -325,6 +325,20 @@ ABI_NEWTON_BATCH = {
     "mg_nonlinearResidual_batch": (_i, [_i, _i, _d, _d, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# the symbols include/mg_adjoint_rx.h declares (the adjoint of reaction and semilinear solves: gradients in s, sigma, w and
+# kappa); bound like ABI_ADJOINT: a library without them still loads, sourceGradient() / Solver.adjoint_reaction() / ... then raise
+_dp = C.POINTER(C.c_double)
+ABI_ADJOINT_RX = {
+    "mg_sourceGradient": (_i, [_i, _i, _d, _vp, _vp, _vp, _vp, _dp]),
+    "mg_sourceGradient_batch": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mg_solver_adjoint_reaction": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, C.POINTER(SolveResult)]),
+    "mg_solver_newton_adjoint": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _dp, C.POINTER(SolveResult)]),
+    "mg_batch_solver_adjoint_reaction": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BatchSolveStats)]),
+    "mg_batch_solver_newton_adjoint": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            C.POINTER(BatchSolveStats)]),
+}
+GRAD_KINDS = dict(NEWTON_KINDS, linear=3)   # MG_GRAD_LINEAR: g(u) = u
+
 # the symbol include/mg_solve_cycle.h declares (the recorded V-cycle both solvers walk, as a list of its launches); bound like
 # ABI_FMG: a library without it still loads, solve_cycle() then raises
 ABI_SOLVE_CYCLE = {
@@ -391,7 +405,8 @@ def load_library(path=None):
     for name, (res, args) in list(ABI_FMG.items()) + list(ABI_HEAT.items()) + list(ABI_VC.items()) + list(ABI_HEAT_VC.items()) + \
             list(ABI_VC_BATCH.items()) + list(ABI_KRYLOV.items()) + list(ABI_KRYLOV_BATCH.items()) + list(ABI_ADJOINT.items()) + \
             list(ABI_EIGS.items()) + list(ABI_BC.items()) + list(ABI_SINGULAR.items()) + list(ABI_SOLVE_CYCLE.items()) + \
-            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()) + list(ABI_RX_BATCH.items()) + list(ABI_NEWTON_BATCH.items()):
+            list(ABI_REACTION.items()) + list(ABI_NEWTON.items()) + list(ABI_RX_BATCH.items()) + list(ABI_NEWTON_BATCH.items()) + \
+            list(ABI_ADJOINT_RX.items()):
         if hasattr(lib, name):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -1880,6 +1895,59 @@ class Solver:
             return lam.to_host(), gA.to_host() if want_coef else None, gU.to_host() if want_rim else None, info
         return lam, gA, gU, info
 
+    def adjoint_reaction(self, Ubar, U, want_coef=True, want_rim=True, want_reaction=True):
+        """The adjoint of a solve of this solver with whatever it has set -- reaction term, coefficient, shift, krylov
+        (include/mg_adjoint_rx.h): for a functional J(U) of the solution U of div(a grad U) - (sigma + s)*U = F with Ubar = dJ/dU,
+        returns (lam, gA, gU, gS, info): lam, gA, gU as Solver.adjoint gives them, gS = dJ/ds = lam'*U on the interior and +0 on the
+        rim (want_reaction; None otherwise; without a reaction set: the sensitivity at s = 0), info the dict of solve() for the
+        adjoint solve with info["gshift"] = dJ/dsigma, the sum of gS (None without want_reaction).  Ubar, U: numpy arrays,
+        DeviceGrids or float64 torch CUDA tensors, as adjoint() takes them.  Bit for bit the sequence {zero fill, solve,
+        coefficientGradient, boundaryGradient, sourceGradient("linear", 1.0, None)} made by the caller; without a reaction set
+        lam, gA and gU are adjoint()'s."""
+        fn = _need_adjoint_rx("mg_solver_adjoint_reaction")
+        io = _AdjointIO(self.N, [Ubar, U])
+        ub, u = io.inp(Ubar, "Ubar"), io.inp(U, "U")
+        lam, gA, gU, gS = io.out(), io.out(want_coef), io.out(want_rim), io.out(want_reaction)
+        res, gshift = SolveResult(), C.c_double(0.0)
+        status = io.run(lambda: fn(self._s, ub, u, io.ptr(lam), io.ptr(gA), io.ptr(gU), io.ptr(gS),
+                                   C.byref(gshift) if want_reaction else None, C.byref(res)))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_solver_adjoint_reaction failed with status {status}")
+        info = _solve_info(res)
+        info["gshift"] = float(gshift.value) if want_reaction else None
+        if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))
+            info["breakdown"] = bool(_lib.mg_solver_krylov_breakdown(self._s))
+        return io.result(lam), io.result(gA), io.result(gU), io.result(gS), info
+
+    def newton_adjoint(self, Ubar, U, F, kind="sinh", kappa=1.0, weight=None, want_coef=True, want_rim=True, want_weight=True):
+        """The adjoint of a semilinear solve newton(F, U0, kind, kappa, weight) of this solver at its solution U
+        (include/mg_adjoint_rx.h): for a functional J(U) with Ubar = dJ/dU, returns (lam, gA, gU, gW, info): lam the adjoint field,
+        ONE solve of this solver with the reaction kappa*w*g'(U) and right-hand side Ubar from the zero field (dJ/dF is lam on the
+        interior); gA, gU as Solver.adjoint gives them; gW = dJ/dw = kappa*lam'*g(U) on the interior and +0 on the rim
+        (want_weight; None otherwise); info the dict of solve() for the adjoint solve with info["gkappa"] = dJ/dkappa, the sum of
+        w*lam'*g(U) (None without want_weight), and info["res_forward"] = ||N(U)||, which says how converged the U is that the
+        gradients are taken at.  Arrays: numpy arrays, DeviceGrids or float64 torch CUDA tensors.  Refused as newton() refuses;
+        the solver has no reaction afterwards, as before."""
+        fn = _need_adjoint_rx("mg_solver_newton_adjoint")
+        io = _AdjointIO(self.N, [Ubar, U, F])
+        ub, u, f, w = io.inp(Ubar, "Ubar"), io.inp(U, "U"), io.inp(F, "F"), io.inp(weight, "weight")
+        lam, gA, gU, gW = io.out(), io.out(want_coef), io.out(want_rim), io.out(want_weight)
+        res, gkappa, resf = SolveResult(), C.c_double(0.0), C.c_double(0.0)
+        status = io.run(lambda: fn(self._s, _newton_kind(kind), float(kappa), w, f, u, ub, io.ptr(lam), io.ptr(gA), io.ptr(gU), io.ptr(gW),
+                                   C.byref(gkappa) if want_weight else None, C.byref(resf), C.byref(res)))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_solver_newton_adjoint failed with status {status}")
+        info = _solve_info(res)
+        info["gkappa"] = float(gkappa.value) if want_weight else None
+        info["res_forward"] = float(resf.value)
+        if hasattr(_lib, "mg_solver_krylov") and _lib.mg_solver_krylov(self._s):
+            self._krylov_log_m = int(_lib.mg_solver_krylov(self._s))
+            info["breakdown"] = bool(_lib.mg_solver_krylov_breakdown(self._s))
+        return io.result(lam), io.result(gA), io.result(gU), io.result(gW), info
+
     def close(self):
         if getattr(self, "_s", None) and _initialised:
             _lib.mg_solver_destroy(self._s)
@@ -2422,6 +2490,68 @@ class BatchSolver:
             return back(lam), back(gA), back(gU), infos
         return lam, gA, gU, infos
 
+    def adjoint_reaction(self, Ubar, U, want_coef=True, want_rim=True, want_reaction=True):
+        """Solver.adjoint_reaction for B instances in one call (include/mg_adjoint_rx.h): returns (lam, gA, gU, gS, infos), every
+        instance bit-identical to Solver(reaction=s_i, coef=a_i).adjoint_reaction(Ubar_i, U_i) alone, infos[i]["gshift"] its
+        dJ/dsigma.  The adjoint solves run as one batched solve and each gradient is ONE launch over all instances.  Ubar, U:
+        [B, N, N] numpy arrays or float64 torch CUDA tensors, or lists of B (N, N) arrays / tensors / DeviceGrids, as adjoint()
+        takes them.  With a reaction term or a coefficient shared by the instances gS[i] and gA[i] are instance i's own
+        sensitivities; the gradient in the shared field is the caller's sum over i."""
+        fn = _need_adjoint_rx("mg_batch_solver_adjoint_reaction")
+        io = _AdjointIO(self.N, [Ubar, U])
+        ubs = io.many(Ubar, "Ubar")
+        B = len(ubs)
+        us = io.many(U, "U", B)
+        lam, gA, gU, gS = io.out(B=B), io.out(want_coef, B), io.out(want_rim, B), io.out(want_reaction, B)
+        res, st, gshift = (SolveResult * max(B, 1))(), BatchSolveStats(), np.zeros(B)
+        status = io.run(lambda: fn(self._s, B, _void_array(ubs), _void_array(us), _void_array(io.ptr(lam)), _void_array(io.ptr(gA)),
+                                   _void_array(io.ptr(gU)), _void_array(io.ptr(gS)), gshift.ctypes.data if want_reaction else None, res,
+                                   C.byref(st)))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_batch_solver_adjoint_reaction failed with status {status}")
+        infos = _batch_adjoint_infos(self, status, res, st, B)
+        for i, info in enumerate(infos):
+            info["gshift"] = float(gshift[i]) if want_reaction else None
+        return io.result(lam, True), io.result(gA, True), io.result(gU, True), io.result(gS, True), infos
+
+    def newton_adjoint_batch(self, Ubar, U, F, kind="sinh", kappa=1.0, weight=None, want_coef=True, want_rim=True, want_weight=True):
+        """Solver.newton_adjoint for B instances in one call (include/mg_adjoint_rx.h): returns (lam, gA, gU, gW, infos), every
+        instance bit-identical to Solver(coef=a_i).newton_adjoint(Ubar_i, U_i, F_i, kind, kappa_i, w_i) alone, infos[i]["gkappa"]
+        and infos[i]["res_forward"] its own.  ONE pass over all instances forms the Newton matrices, one batched solve gives the
+        adjoint fields, each gradient is one launch.  kappa: a scalar or a sequence of B; weight: None, one (N, N) field shared
+        by all (gW[i] is then instance i's own sensitivity, the gradient in the shared w the caller's sum) or B of them.  Ubar, U,
+        F: [B, N, N] numpy arrays or float64 torch CUDA tensors, or lists of B.  The solver has no reaction afterwards."""
+        fn = _need_adjoint_rx("mg_batch_solver_newton_adjoint")
+        io = _AdjointIO(self.N, [Ubar, U, F])
+        ubs = io.many(Ubar, "Ubar")
+        B = len(ubs)
+        us, fs = io.many(U, "U", B), io.many(F, "F", B)
+        if weight is None:
+            ws = None
+        elif hasattr(weight, "ptr") or (not isinstance(weight, (list, tuple)) and len(weight.shape) == 2):
+            ws = [io.inp(weight, "weight")]
+        else:
+            ws = io.many(weight, "weight")   # (a count other than 1 or B: the library refuses it)
+        kap = np.asarray(kappa, dtype=np.float64)
+        if kap.ndim > 1 or (kap.ndim == 1 and kap.shape[0] != B):
+            raise MGError(f"[2] kappa: expected a scalar or {B} values, got shape {kap.shape}")
+        kap = np.ascontiguousarray(np.broadcast_to(kap, (B,)))
+        lam, gA, gU, gW = io.out(B=B), io.out(want_coef, B), io.out(want_rim, B), io.out(want_weight, B)
+        res, st, gkappa, resf = (SolveResult * max(B, 1))(), BatchSolveStats(), np.zeros(B), np.zeros(B)
+        status = io.run(lambda: fn(self._s, B, _newton_kind(kind), kap.ctypes.data, 0 if ws is None else len(ws), _void_array(ws),
+                                   _void_array(fs), _void_array(us), _void_array(ubs), _void_array(io.ptr(lam)), _void_array(io.ptr(gA)),
+                                   _void_array(io.ptr(gU)), _void_array(io.ptr(gW)), gkappa.ctypes.data if want_weight else None,
+                                   resf.ctypes.data, res, C.byref(st)))
+        if status > 0:
+            _check()
+            raise MGError(f"mg_batch_solver_newton_adjoint failed with status {status}")
+        infos = _batch_adjoint_infos(self, status, res, st, B)
+        for i, info in enumerate(infos):
+            info["gkappa"] = float(gkappa[i]) if want_weight else None
+            info["res_forward"] = float(resf[i])
+        return io.result(lam, True), io.result(gA, True), io.result(gU, True), io.result(gW, True), infos
+
     def close(self):
         if getattr(self, "_s", None) and _initialised:
             _lib.mg_batch_solver_destroy(self._s)
@@ -2613,6 +2743,179 @@ def boundaryGradient_batch(N, L, a, lam, Ubar, gU):
                                                _optional_pointer_array(Ubar, n), _optional_pointer_array(gU, n))
     _check()
     return gU
+
+
+# ---------------------------------------------------------------- the adjoint of reaction and semilinear solves
+def _need_adjoint_rx(name):
+    if not hasattr(lib(), name):
+        raise MGError(f"{LIB_PATH} does not export {name}: rebuild it (the adjoint of reaction and semilinear solves is not in this library)")
+    return getattr(_lib, name)
+
+
+def _grad_kind(kind):
+    if kind in GRAD_KINDS:
+        return GRAD_KINDS[kind]
+    if isinstance(kind, str):
+        raise MGError(f"kind {kind!r}: expected one of {sorted(GRAD_KINDS)}")
+    return int(kind)   # (a number goes to the library, which refuses one it does not know)
+
+
+class _AdjointIO:
+    """The arrays of one adjoint call in the caller's form, as Solver.adjoint handles them: float64 torch CUDA tensors (outputs
+    are tensors, the engine runs on torch.cuda.current_stream()), DeviceGrids (outputs are DeviceGrids) or numpy arrays
+    (uploaded for the call; outputs come back as new numpy arrays).  `samples`: the inputs that decide the form."""
+
+    def __init__(self, N, samples):
+        flat = []
+        for x in samples:
+            flat += list(x) if isinstance(x, (list, tuple)) else [x]
+        flat = [x for x in flat if x is not None]
+        self.N, self.nn = N, N * N
+        self.torch = any(_is_torch(x) for x in flat)
+        self.host = not self.torch and not all(hasattr(x, "ptr") for x in flat)
+        self.device = next(x.device for x in flat if _is_torch(x)) if self.torch else None
+        self.keep = []
+
+    def inp(self, x, what):
+        """the device address of one N x N input (None stays None)"""
+        N = self.N
+        if x is None:
+            return None
+        if self.torch:
+            import torch
+            if not (_is_torch(x) and x.is_cuda and x.dtype == torch.float64 and tuple(x.shape) == (N, N) and x.is_contiguous()):
+                raise MGError(f"{what}: expected a contiguous float64 CUDA tensor of shape ({N}, {N})")
+            (p,), buf = _staged([x], False, self.nn, self.device)
+            self.keep.append(buf)
+            return p
+        if hasattr(x, "ptr") and hasattr(x, "shape"):
+            if tuple(x.shape) != (N, N):
+                raise MGError(f"{what}: DeviceGrid of shape {x.shape}, expected ({N}, {N})")
+            return x.ptr
+        a = np.asarray(x, dtype=np.float64)
+        if a.shape != (N, N):
+            raise MGError(f"{what}: array of shape {a.shape}, expected ({N}, {N})")
+        g = DeviceGrid.from_host(a)
+        self.keep.append(g)
+        return g.ptr
+
+    def many(self, X, what, B=None):
+        """the addresses of B inputs: [B, N, N], a list of (N, N), or one (N, N) / DeviceGrid for every instance"""
+        if hasattr(X, "ptr"):
+            xs, shared = [X], True
+        else:
+            xs, shared = _instances(X if isinstance(X, (list, tuple)) or _is_torch(X) else np.asarray(X), what)
+        ps = [self.inp(x, what) for x in xs]
+        if shared and B is not None:
+            ps = ps * B
+        if B is not None and len(ps) != B:
+            raise MGError(f"{len(ps)} {what} instances for {B} instances")
+        return ps
+
+    def out(self, wanted=True, B=None):
+        """one N x N output (B: a list of B), 16-byte aligned; None when it is not wanted"""
+        if not wanted:
+            return None
+        if self.torch:
+            import torch
+            if B is None:
+                return torch.empty((self.N, self.N), dtype=torch.float64, device=self.device)
+            return torch.empty((B, self.nn + self.nn % 2), dtype=torch.float64, device=self.device)
+        return DeviceGrid((self.N, self.N)) if B is None else [DeviceGrid((self.N, self.N)) for _ in range(B)]
+
+    def ptr(self, h):
+        if h is None:
+            return None
+        if self.torch:
+            return h.data_ptr() if h.dim() == 2 and tuple(h.shape) == (self.N, self.N) else [h[i].data_ptr() for i in range(h.shape[0])]
+        return [g.ptr for g in h] if isinstance(h, list) else h.ptr
+
+    def result(self, h, batched=False):
+        if h is None:
+            return None
+        if self.torch:
+            return h[:, :self.nn].reshape(h.shape[0], self.N, self.N) if batched else h
+        if self.host:
+            return np.stack([g.to_host() for g in h]) if batched else h.to_host()
+        return h
+
+    def run(self, call):
+        """call() with the engine on the tensors' stream"""
+        if not self.torch:
+            return call()
+        import torch
+        prev = _lib.mg_get_stream()
+        _lib.mg_set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        try:
+            return call()
+        finally:
+            _lib.mg_set_stream(prev)
+
+
+def _void_array(ps):
+    return None if ps is None else (C.c_void_p * max(len(ps), 1))(*ps)
+
+
+def sourceGradient(N, kind, kappa, w, lam, U, G=None):
+    """mg_sourceGradient (include/mg_adjoint_rx.h): G = kappa*(lam'*g(U)) on the interior and +0 on the rim, lam' = lam with its
+    rim taken as +0, and sum = the sum over the interior of w*(lam'*g(U)) (w = None: of lam'*g(U)) in the order of the semilinear
+    pass's norm.  kind: "cubic", "sinh", "exp" or "linear" (g(u) = u).  w, lam, U: numpy arrays, DeviceGrids or float64 torch
+    CUDA tensors; G = None: a new array of the inputs' form.  Returns (G, sum)."""
+    fn = _need_adjoint_rx("mg_sourceGradient")
+    io = _AdjointIO(N, [lam, U])
+    wp, lp, up = io.inp(w, "w"), io.inp(lam, "lam"), io.inp(U, "U")
+    made = G is None
+    if made:
+        G = io.out()
+    gp = io.ptr(G) if made else (G.data_ptr() if _is_torch(G) else G.ptr)
+    s = C.c_double(0.0)
+    status = io.run(lambda: fn(int(N), _grad_kind(kind), float(kappa), wp, lp, up, gp, C.byref(s)))
+    if status:
+        _check()
+        raise MGError(f"mg_sourceGradient failed with status {status}")
+    return (io.result(G) if made else G), float(s.value)
+
+
+def sourceGradient_batch(N, kind, kappa, w, lam, U, G=None):
+    """mg_sourceGradient_batch: sourceGradient for every instance in ONE launch, each bit-identical to the single call.  kappa: a
+    scalar or a sequence of B; w: None, one (N, N) field shared by all, or B of them; lam, U: [B, N, N] or sequences of B.
+    G = None: new arrays of the inputs' form, else a sequence of B DeviceGrids.  Returns (G, sums), sums a numpy array of B."""
+    fn = _need_adjoint_rx("mg_sourceGradient_batch")
+    io = _AdjointIO(N, [lam, U])
+    lps = io.many(lam, "lam")
+    B = len(lps)
+    ups = io.many(U, "U", B)
+    if w is None:
+        wps = None
+    elif hasattr(w, "ptr") or (not isinstance(w, (list, tuple)) and len(w.shape) == 2):
+        wps = [io.inp(w, "w")]
+    else:
+        wps = io.many(w, "w")   # (a count other than 1 or B: the library refuses it)
+    kap = np.asarray(kappa, dtype=np.float64)
+    if kap.ndim > 1 or (kap.ndim == 1 and kap.shape[0] != B):
+        raise MGError(f"[2] kappa: expected a scalar or {B} values, got shape {kap.shape}")
+    kap = np.ascontiguousarray(np.broadcast_to(kap, (B,)))
+    made = G is None
+    if made:
+        G = io.out(B=B)
+    gps = io.ptr(G) if made else [g.ptr for g in G]
+    sums = np.zeros(B)
+    status = io.run(lambda: fn(B, int(N), _grad_kind(kind), kap.ctypes.data, 0 if wps is None else len(wps), _void_array(wps),
+                               _void_array(lps), _void_array(ups), _void_array(gps), sums.ctypes.data))
+    if status:
+        _check()
+        raise MGError(f"mg_sourceGradient_batch failed with status {status}")
+    return (io.result(G, batched=True) if made else G), sums
+
+
+def _batch_adjoint_infos(self, status, res, st, n):
+    stats = dict(status=status, cycles=st.cycles, launches=st.launches, device_ms=st.device_ms)
+    out = [dict(_solve_info(r), stats=stats) for r in res[:n]]
+    if hasattr(_lib, "mg_batch_solver_krylov") and _lib.mg_batch_solver_krylov(self._s):
+        self._krylov_log_m = int(_lib.mg_batch_solver_krylov(self._s))
+        for i, info in enumerate(out):
+            info["breakdown"] = bool(_lib.mg_batch_solver_krylov_breakdown(self._s, i))
+    return out
 
 
 def _need_krylov_batch(name):

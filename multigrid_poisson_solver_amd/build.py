@@ -12,7 +12,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib", "libmgpoisson.so")
 EXE = os.path.join(PKG, "bin", "MG_HIP")
-SOURCES = ["mg_stream_f32.hip", "mg_stream.hip", "mg_tile.hip", "mg_tile_f32.hip", "mg_kernels.hip", "mg_solve_kernels.hip", "mg_fmg_kernels.hip", "mg_heat_kernels.hip", "mg_varcoef_kernels.hip", "mg_varcoef_batch_kernels.hip", "mg_heat_vc_kernels.hip", "mg_krylov_kernels.hip", "mg_krylov_batch_kernels.hip", "mg_adjoint_kernels.hip", "mg_eigs_kernels.hip", "mg_bc_kernels.hip", "mg_singular_kernels.hip", "mg_reaction_kernels.hip", "mg_reaction_batch_kernels.hip", "mg_newton_kernels.hip", "mg_newton_batch_kernels.hip", "mg_tail.hip", "mg_tail_f32.hip", "mg_abi.cpp", "mg_tables.cpp", "mg_cycle.cpp", "mg_slab.cpp", "mg_comm.cpp", "mg_solve.cpp", "mg_solve_batch.cpp", "mg_heat.cpp", "mg_adjoint.cpp", "mg_eigs.cpp"]
+SOURCES = ["mg_stream_f32.hip", "mg_stream.hip", "mg_tile.hip", "mg_tile_f32.hip", "mg_kernels.hip", "mg_solve_kernels.hip", "mg_fmg_kernels.hip", "mg_heat_kernels.hip", "mg_varcoef_kernels.hip", "mg_varcoef_batch_kernels.hip", "mg_heat_vc_kernels.hip", "mg_krylov_kernels.hip", "mg_krylov_batch_kernels.hip", "mg_adjoint_kernels.hip", "mg_eigs_kernels.hip", "mg_bc_kernels.hip", "mg_singular_kernels.hip", "mg_reaction_kernels.hip", "mg_reaction_batch_kernels.hip", "mg_newton_kernels.hip", "mg_newton_batch_kernels.hip", "mg_adjoint_rx_kernels.hip", "mg_tail.hip", "mg_tail_f32.hip", "mg_abi.cpp", "mg_tables.cpp", "mg_cycle.cpp", "mg_slab.cpp", "mg_comm.cpp", "mg_solve.cpp", "mg_solve_batch.cpp", "mg_heat.cpp", "mg_adjoint.cpp", "mg_adjoint_rx.cpp", "mg_eigs.cpp"]
 ARCH = "gfx950"
 
 
@@ -57,7 +57,7 @@ def _deps():
                          os.path.join(ROOT, "include", "mg_adjoint.h"), os.path.join(ROOT, "include", "mg_eigs.h"),
                          os.path.join(ROOT, "include", "mg_bc.h"), os.path.join(ROOT, "include", "mg_solve_cycle.h"),
                          os.path.join(ROOT, "include", "mg_singular.h"), os.path.join(ROOT, "include", "mg_reaction.h"),
-                         os.path.join(ROOT, "include", "mg_newton.h"), os.path.join(ROOT, "include", "mg_rx_batch.h"), os.path.join(ROOT, "include", "mg_newton_batch.h"), os.path.join(CSRC, "mg_newton_impl.h"), os.path.join(CSRC, "mg_exp_libm.h"),
+                         os.path.join(ROOT, "include", "mg_newton.h"), os.path.join(ROOT, "include", "mg_rx_batch.h"), os.path.join(ROOT, "include", "mg_newton_batch.h"), os.path.join(ROOT, "include", "mg_adjoint_rx.h"), os.path.join(CSRC, "mg_newton_impl.h"), os.path.join(CSRC, "mg_exp_libm.h"),
                          os.path.join(CSRC, "mg_bc_impl.h"), os.path.join(CSRC, "mg_singular_impl.h"), os.path.join(CSRC, "mg_reaction_impl.h"),
                          os.path.join(CSRC, "mg_varcoef_impl.h"), os.path.join(CSRC, "mg_krylov_impl.h"),
                          os.path.abspath(__file__)]

@@ -209,7 +209,7 @@ int mg_solver_adjoint(mg_solver *s, const double *Ubar, const double *U, double 
         return refuse(MG_ERR_UNSUPPORTED);
     }
     if (mg_solver_has_reaction(s)) {   // (include/mg_reaction.h: no gradient in s is built, the rest is not offered without it)
-        fail(MG_ERR_UNSUPPORTED, "mg_solver_adjoint: a reaction term is set; the adjoint is not built for a reaction");
+        fail(MG_ERR_UNSUPPORTED, "mg_solver_adjoint: a reaction term is set; the adjoint is not built for a reaction here (mg_solver_adjoint_reaction takes it)");
         return refuse(MG_ERR_UNSUPPORTED);
     }
     double L = 1.0;
@@ -264,7 +264,7 @@ int mg_batch_solver_adjoint(mg_batch_solver *s, int n, const double *const *Ubar
         return refuse(MG_ERR_ARG);
     }
     if (mg_batch_solver_has_reaction(s)) {   // (include/mg_rx_batch.h: refused as mg_solver_adjoint refuses it)
-        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the adjoint is not built for a reaction", who);
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the adjoint is not built for a reaction here (mg_batch_solver_adjoint_reaction takes it)", who);
         return refuse(MG_ERR_UNSUPPORTED);
     }
     const int n_coef = mg_batch_solver_has_coefficient(s);

@@ -829,4 +829,35 @@ k::TailArgsF tail_args_f32(const k::TailArgs &a);
 bool scan_tail(const std::vector<double> &tokens, size_t *tok_io, const std::vector<int> &sizes, int at0, int con_step,
                int top_N, double L, k::TailArgs *out, int *node_level);
 
+// the adjoint of reaction and semilinear solves (mg_adjoint_rx_kernels.hip, driven by mg_adjoint_rx.cpp; the expressions and
+// their order: include/mg_adjoint_rx.h).  G = kappa*(lam'*g(U)) on the interior and +0 on the rim, *out = the sum of
+// W*(lam'*g(U)) (W == nullptr: of lam'*g(U)) in the partition and order of the semilinear pass's norm, no square root
+// (part: resnorm_partials(N)).  kind: MG_NEWTON_* or MG_GRAD_LINEAR.  Two launches.
+namespace k {
+void src_grad(hipStream_t s, int N, int kind, double kappa, const double *W, const double *lam, const double *U, double *G, double *part,
+              double *out);
+// the same on n instances in one launch and one finish launch: items[z] the arrays and the kappa of instance z; has_w: EVERY
+// instance's W is there (false: the slot is not read).  Partials at part + z*resnorm_partials(N), sums to out[z].
+struct SrcGradItem {
+    const double *W, *lam, *U;
+    double *G;
+    double kappa;
+};
+void src_grad_batch(hipStream_t s, int n, int N, int kind, bool has_w, const SrcGradItem *items, double *part, double *out);
+}  // namespace k
+// The linearisation of the semilinear problem at U for a driver outside mg_solve.cpp (mg_adjoint_rx.cpp): refuses what
+// mg_solver_newton refuses (messages under `who`), checks w, runs the no-step pass on U -- S into the solver's level-0
+// reaction storage, *res = ||N(U)|| -- coarsens S as mg_solver_newton does and leaves the solver WITH that reaction.  Returns
+// MG_OK, or the error code with the solver without a reaction.  solver_drop_reaction: the solver without a reaction again.
+int solver_newton_linearise(mg_solver *s, const char *who, int kind, double kappa, const double *w_dev, const double *F_dev,
+                            const double *U_dev, double *res);
+void solver_drop_reaction(mg_solver *s);
+// the same for n instances of a batch solver (mg_solve_batch.cpp): what mg_batch_solver_newton refuses, ONE pass over all n --
+// S of instance i straight into its level-0 reaction storage, norms[i] = ||N(U_i)|| (host, may be nullptr) -- and one coarsening
+// launch per level; leaves the solver with n reaction terms, one per instance.  *launches grows by the kernel launches.
+int batch_solver_newton_linearise(mg_batch_solver *s, const char *who, int n, int kind, const double *kappa, int n_w,
+                                  const double *const *w_dev, const double *const *F_dev, const double *const *U_dev, double *norms,
+                                  int *launches);
+void batch_solver_drop_reaction(mg_batch_solver *s);
+
 }  // namespace mg

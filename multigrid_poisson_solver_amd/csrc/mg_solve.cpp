@@ -1268,6 +1268,67 @@ int mg_nonlinearResidual(int N, double L, double shift, const double *a_dev, int
     return MG_OK;
 }
 
+// ------------------------------------------------------------------ the linearisation at U for mg_adjoint_rx.cpp
+// mg_solver_newton's refusals, check of w and first pass, then its coarsening of S; the pass's D goes to nw_buf[1] and is dropped
+}  // extern "C"
+
+int mg::solver_newton_linearise(mg_solver *s, const char *who, int kind, double kappa, const double *w_dev, const double *F_dev,
+                                const double *U_dev, double *res)
+{
+    if (s->op.react) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the driver installs the Newton matrix's own (take yours away with "
+                                 "mg_solver_set_reaction(NULL), or put it into w)", who);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (s->op.kind) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a boundary with a Neumann side is set; the semilinear solve is built for Dirichlet sides", who);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (s->o.fmg != 0) {
+        fail(MG_ERR_UNSUPPORTED, "%s: the solver was created with fmg = %d; the full-multigrid start is not built for a reaction term",
+             who, s->o.fmg);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (!newton_kind_ok(who, kind, kappa)) return MG_ERR_ARG;
+    const hipStream_t st = ctx().stream;
+    const int N = s->N, nl = (int)s->sizes.size();
+    const size_t n0 = (size_t)N * N;
+    if (!react_storage(s)) return MG_ERR_HIP;
+    if (!s->nw_buf[1] && !dev_alloc(&s->nw_buf[1], n0)) return MG_ERR_HIP;
+    if (w_dev) {
+        if (!MG_HIP(hipMemsetAsync(s->react_flag, 0, sizeof(int), st))) return MG_ERR_HIP;
+        k::reaction_check(st, w_dev, n0, s->react_flag);
+        if (!MG_HIP(hipMemcpyAsync(s->host_react_flag, s->react_flag, sizeof(int), hipMemcpyDeviceToHost, st)) ||
+            !MG_HIP(hipStreamSynchronize(st)))
+            return MG_ERR_HIP;
+        if (*s->host_react_flag) {
+            fail(MG_ERR_ARG, "%s: every value of w must be finite and >= 0 (a negative or not finite value found)", who);
+            return MG_ERR_ARG;
+        }
+    }
+    const LevelConsts &c0 = s->lc[0];
+    k::newton_residual(st, N, c0.inv, c0.sd, kind, kappa, s->op.a(0), w_dev, U_dev, nullptr, 0.0, F_dev, nullptr, s->nw_buf[1], s->react[0],
+                       s->part, s->dev_scal);
+    if (!read_back(s, st)) return MG_ERR_HIP;
+    const double rn = s->host_scal[0];
+    if (res) *res = rn;
+    if (!std::isfinite(rn)) {
+        fail(MG_ERR_ARG, "%s: the residual of U is not finite (%g)", who, rn);
+        return MG_ERR_ARG;
+    }
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen(st, s->sizes[l], s->react[l], s->sizes[l + 1], s->react[l + 1], restrict_table(s->sizes[l], s->sizes[l + 1]));
+    s->op.react = &s->react;
+    return MG_OK;
+}
+
+void mg::solver_drop_reaction(mg_solver *s)
+{
+    if (s) s->op.react = nullptr;
+}
+
+extern "C" {
+
 // ------------------------------------------------------------------ boundary kinds per side (include/mg_bc.h)
 namespace {
 bool kinds_ok(const char *who, const int *kind)

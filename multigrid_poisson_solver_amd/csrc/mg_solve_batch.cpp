@@ -724,6 +724,83 @@ bool mg::batch_solver_coarse_capped(const mg_batch_solver *s, int n)
     return false;
 }
 
+// mg_batch_solver_newton's refusals, check of w and first pass over all n instances -- S straight into the level-0 reaction
+// storage of each, D into the driver's field 1 and dropped -- then one coarsening launch per level; no lockstep is needed
+int mg::batch_solver_newton_linearise(mg_batch_solver *s, const char *who, int n, int kind, const double *kappa, int n_w,
+                                      const double *const *w_dev, const double *const *F_dev, const double *const *U_dev, double *norms,
+                                      int *launches)
+{
+    if (s->n_react > 0) {
+        fail(MG_ERR_UNSUPPORTED, "%s: a reaction term is set; the driver installs the Newton matrices' own (take yours away with "
+                                 "mg_batch_solver_set_reaction(s, 0, NULL), or put it into w)", who);
+        return MG_ERR_UNSUPPORTED;
+    }
+    if (n < 1 || n > s->max_batch) {
+        fail(MG_ERR_ARG, "%s: n = %d outside [1, max_batch = %d]", who, n, s->max_batch);
+        return MG_ERR_ARG;
+    }
+    if (s->n_coef > 1 && n > s->n_coef) {
+        fail(MG_ERR_ARG, "%s: n = %d instances, but the solver holds %d coefficients (one per instance)", who, n, s->n_coef);
+        return MG_ERR_ARG;
+    }
+    if (!optional_arrays_ok(who, "w", n, n_w, w_dev) || !newton_kind_ok(who, kind) || !kappas_ok(who, n, kappa)) return MG_ERR_ARG;
+    const hipStream_t st = ctx().stream;
+    const int N = s->N, nl = (int)s->sizes.size(), mb = s->max_batch;
+    const size_t n0 = (size_t)N * N, p0 = s->pitch[0];
+    const bool has_a = s->n_coef > 0, has_w = n_w > 0;
+    if (!newton_storage(s)) return MG_ERR_HIP;
+    if (has_w) {
+        for (int i = 0; i < n_w; ++i) s->host_tab[i] = NodeBatchItem{w_dev[i], nullptr, nullptr, nullptr, nullptr};
+        if (!MG_HIP(hipMemcpyAsync(s->dev_tab, s->host_tab, (size_t)n_w * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)) ||
+            !MG_HIP(hipMemsetAsync(s->coef_flags, 0, n_w * sizeof(int), st)))
+            return MG_ERR_HIP;
+        k::reaction_check_batch(st, n_w, n0, s->dev_tab, s->coef_flags);
+        *launches += 1;
+        if (!MG_HIP(hipMemcpyAsync(s->host_coef_flags, s->coef_flags, n_w * sizeof(int), hipMemcpyDeviceToHost, st)) ||
+            !MG_HIP(hipStreamSynchronize(st)))
+            return MG_ERR_HIP;
+        for (int i = 0; i < n_w; ++i)
+            if (s->host_coef_flags[i]) {
+                fail(MG_ERR_ARG, "%s: every value of w must be finite and >= 0 (instance %d has one that is not)", who, i);
+                return MG_ERR_ARG;
+            }
+    }
+    const LevelConsts &c0 = s->lc[0];
+    const NewtonBlock host = newton_block(s->nw_host, nl, mb), dev = newton_block(s->nw_dev, nl, mb);
+    for (int i = 0; i < n; ++i) {
+        host.pass[i] = k::NewtonBatchItem{has_a ? level(s, s->coef, 0, s->n_coef == 1 ? 0 : i) : nullptr, has_w ? w_dev[n_w == 1 ? 0 : i] : nullptr,
+                                          U_dev[i], nullptr, F_dev[i], nullptr, s->nw_field + (1 * (size_t)mb + i) * p0,
+                                          level(s, s->react, 0, i), kappa[i]};
+        for (int l = 0; l + 1 < nl; ++l)
+            host.coarsen[(size_t)l * mb + i] = NodeBatchItem{level(s, s->react, l, i), nullptr, nullptr, level(s, s->react, l + 1, i), nullptr};
+    }
+    if (!MG_HIP(hipMemcpyAsync(dev.pass, host.pass, (size_t)n * sizeof(k::NewtonBatchItem), hipMemcpyHostToDevice, st))) return MG_ERR_HIP;
+    k::newton_residual_batch(st, n, N, c0.inv, c0.sd, kind, has_a, has_w, false, 0.0, dev.pass, s->part, dev.norms);
+    *launches += 2;
+    if (!MG_HIP(hipMemcpyAsync(host.norms, dev.norms, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st)) ||
+        !MG_HIP(hipEventRecord(s->ev_sync, st)) || !MG_HIP(hipEventSynchronize(s->ev_sync)))
+        return MG_ERR_HIP;
+    for (int i = 0; i < n; ++i) {
+        if (norms) norms[i] = host.norms[i];
+        if (!std::isfinite(host.norms[i])) {
+            fail(MG_ERR_ARG, "%s: the residual of U of instance %d is not finite (%g)", who, i, host.norms[i]);
+            return MG_ERR_ARG;
+        }
+    }
+    if (nl > 1 && !MG_HIP(hipMemcpyAsync(dev.coarsen, host.coarsen, (size_t)(nl - 1) * mb * sizeof(NodeBatchItem), hipMemcpyHostToDevice, st)))
+        return MG_ERR_HIP;
+    for (int l = 0; l + 1 < nl; ++l)
+        k::coef_coarsen_batch(st, n, s->sizes[l], s->sizes[l + 1], dev.coarsen + (size_t)l * mb, restrict_table(s->sizes[l], s->sizes[l + 1]));
+    *launches += nl - 1;
+    s->n_react = n;
+    return MG_OK;
+}
+
+void mg::batch_solver_drop_reaction(mg_batch_solver *s)
+{
+    if (s) s->n_react = 0;
+}
+
 extern "C" {
 
 mg_batch_solver *mg_batch_solver_create(int N, double L, int max_batch, const mg_solve_opts *opts)
