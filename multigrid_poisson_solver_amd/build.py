@@ -59,7 +59,7 @@ def _deps():
                          os.path.join(ROOT, "include", "mg_singular.h"), os.path.join(ROOT, "include", "mg_reaction.h"),
                          os.path.join(ROOT, "include", "mg_newton.h"), os.path.join(ROOT, "include", "mg_rx_batch.h"), os.path.join(ROOT, "include", "mg_newton_batch.h"), os.path.join(ROOT, "include", "mg_adjoint_rx.h"), os.path.join(CSRC, "mg_newton_impl.h"), os.path.join(CSRC, "mg_exp_libm.h"),
                          os.path.join(CSRC, "mg_bc_impl.h"), os.path.join(CSRC, "mg_singular_impl.h"), os.path.join(CSRC, "mg_reaction_impl.h"),
-                         os.path.join(CSRC, "mg_varcoef_impl.h"), os.path.join(CSRC, "mg_krylov_impl.h"),
+                         os.path.join(CSRC, "mg_varcoef_impl.h"), os.path.join(CSRC, "mg_krylov_impl.h"), os.path.join(CSRC, "mg_solver_common.h"),
                          os.path.abspath(__file__)]
     return deps + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]
 

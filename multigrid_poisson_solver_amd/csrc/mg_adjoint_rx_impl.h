@@ -120,7 +120,7 @@ __device__ __forceinline__ void sg_body(const SgArgs &x)
     if (threadIdx.x == 0) x.part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 
-// second stage: resnorm_finish_vc_body without the square root -- *out = the sum of the n partials, one block, fixed order
+// second stage: resnorm_finish_body without the square root -- *out = the sum of the n partials, one block, fixed order
 __device__ __forceinline__ void sg_finish_body(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
     double acc = 0.0;

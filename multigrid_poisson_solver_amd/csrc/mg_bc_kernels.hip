@@ -26,7 +26,7 @@ __global__ __launch_bounds__(TB) void k_bc(BcArgs b)
 
 __global__ __launch_bounds__(1024) void k_resnorm_finish_bc(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part, n, out);
+    resnorm_finish_body(part, n, out);
 }
 
 __global__ __launch_bounds__(1024) void k_gs_relative_bc(int N, BcGeom g, double h2, double inv, double sd,

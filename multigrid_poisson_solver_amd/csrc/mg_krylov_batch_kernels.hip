@@ -99,12 +99,6 @@ __global__ __launch_bounds__(TB) void k_krylov_zero_b(const KrylovBatchItem *__r
     if ((count & 1) && blockIdx.x == 0 && threadIdx.x == 0) z[count - 1] = 0.0;
 }
 
-inline dim3 with_instances(dim3 g, int n)
-{
-    g.z = n;
-    return g;
-}
-
 template <int K>
 void launch_dots_b(hipStream_t s, int n, int N, const KrylovBatchItem *items, const KrylovVecs &v)
 {

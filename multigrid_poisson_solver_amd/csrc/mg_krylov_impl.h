@@ -23,41 +23,12 @@
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"
+#include "mg_solver_common.h"
 
 namespace mg {
 namespace k {
 
 namespace {
-
-constexpr int TB = 256;          // threads per block
-constexpr int ROWS_PB = 4;       // rows per block, one point per lane
-constexpr int PR = 4;            // rows per thread of the 16-byte form
-constexpr int PAIR_MIN_N = 512;
-typedef double double2_v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over the block in a fixed order; valid in thread 0.  Every thread of the block must call it.
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double sm[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sm[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        const int nw = (blockDim.x + 63) >> 6;
-        for (int i = 0; i < nw; ++i) r += sm[i];
-    }
-    return r;
-}
 
 // One lane's points of a row: a double (PAIR = false) or two neighbouring columns (PAIR = true) of which mx / my tell
 // which are interior.  A value outside the mask is never summed and never stored.
@@ -286,12 +257,7 @@ __device__ __forceinline__ void krylov_update_finish_body(const double *__restri
     }
 }
 
-inline bool use_pairs(int N) { return N % 2 == 0 && N >= PAIR_MIN_N; }
-inline dim3 grid_of(int N)
-{
-    if (use_pairs(N)) return dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR);
-    return dim3((N + TB - 1) / TB, (N + ROWS_PB - 1) / ROWS_PB);
-}
+inline dim3 grid_of(int N) { return use_pairs(N) ? grid_pairs(N) : grid_rows(N); }
 
 }  // namespace
 

@@ -18,8 +18,7 @@
 // and 48 bytes per point.
 // Every sum is per-block partials in a fixed partition (block (x, y) -> slot y*gridDim.x + x, one stripe of slots per sum)
 // and a finish launch that adds them in a fixed order: no floating-point atomics, the same call twice gives the same bits.
-// wave_sum / block_sum are the third private copy (mg_solve_kernels.hip, mg_varcoef_impl.h); nothing here has to match the
-// other two bit for bit.
+// wave_sum / block_sum are mg_solver_common.h's, the ones of the solver's own norms.
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(TB) void k_newton_residual_b(int N, double inv, dou
 // out[i] = sqrt(sum of instance i's np partials): one block per instance, each the single-instance finish
 __global__ __launch_bounds__(1024) void k_newton_norm_finish_b(const double *__restrict__ part, size_t np, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part + blockIdx.x * np, np, out + blockIdx.x);
+    resnorm_finish_body(part + blockIdx.x * np, np, out + blockIdx.x);
 }
 
 struct Launch {

@@ -1,8 +1,8 @@
 // mg_newton_impl.h -- the point code of the semilinear residual (include/mg_newton.h; kernels and launcher:
 // mg_newton_kernels.hip).  The operator and the block sums are mg_varcoef_impl.h's (Faces, faces, bracket, block_sum,
-// resnorm_finish_vc_body), included, not copied; exp is mg_exp_libm.h's.  One streaming pass forms, per point, the trial value
+// resnorm_finish_body), included, not copied; exp is mg_exp_libm.h's.  One streaming pass forms, per point, the trial value
 // v = U + t*dlt, the Newton matrix's diagonal term S = kw*g'(v), the Newton right-hand side D = (F + kw*g(v)) - inv*b(v) and
-// the partial sums of D^2, in the shapes of the reaction kernels (mg_reaction_impl.h): a lane walks 4 rows down its column
+// the partial sums of D^2, in the shapes of the reaction kernels (mg_varcoef_impl.h): a lane walks 4 rows down its column
 // (any N) or its column pair (even N from PAIR_MIN_N on, 16-byte accesses) with a rolling window of three rows in registers.
 // The window holds v, not U and dlt apart: a row of U and of dlt is combined as it is loaded, once, by the expression every
 // other use of that point evaluates, so the step form carries one window more than the sweep's (a, v) and no third.
@@ -117,7 +117,7 @@ __device__ __forceinline__ double nw_cols(const NwArgs &x)
 }
 
 // ---------------------------------------------------------------- two columns per lane, 16-byte accesses
-// (even N, 16-byte aligned arrays, as rx_pairs).  NT: F and w through non-temporal loads, D, S and V through non-temporal
+// (even N, 16-byte aligned arrays, as vc_pairs).  NT: F and w through non-temporal loads, D, S and V through non-temporal
 // stores.  U, dlt and a are windows -- every row is read by the block above and the block below as well -- and stay ordinary.
 template <bool NT>
 __device__ __forceinline__ void nw_store(double *p, double2_v v)
@@ -205,7 +205,7 @@ __device__ __forceinline__ double nw_pairs(const NwArgs &x)
     return acc;
 }
 
-// the whole pass of one block: its points, then its partial of the sum of D^2 in the place and order of rx_resnorm_body
+// the whole pass of one block: its points, then its partial of the sum of D^2 in the place and order of resnorm_vc_body
 template <int KIND, bool PAIR, bool NT, bool HAS_A, bool HAS_W, bool HAS_STEP>
 __device__ __forceinline__ void nw_body(const NwArgs &x)
 {

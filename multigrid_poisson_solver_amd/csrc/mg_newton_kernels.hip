@@ -27,7 +27,7 @@ __global__ __launch_bounds__(TB) void k_newton_residual(NwArgs x)
 
 __global__ __launch_bounds__(1024) void k_newton_norm_finish(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part, n, out);
+    resnorm_finish_body(part, n, out);
 }
 
 // HAS_A, HAS_W, HAS_STEP from the pointers that are there

@@ -1,6 +1,6 @@
 // mg_reaction_batch_kernels.hip -- batched forms of the reaction kernels (include/mg_rx_batch.h; driven by
 // mg_solve_batch.cpp: run_cycle_batch): ONE launch runs a kernel of mg_reaction_kernels.hip for every active instance.  The
-// __device__ bodies are the ones of mg_reaction_impl.h, compiled here with the same flags (-ffp-contract=off): an instance
+// __device__ bodies are the ones of mg_varcoef_impl.h (HAS_S = true), compiled here with the same flags (-ffp-contract=off): an instance
 // runs the code, the block partition (grid x, y) and the summation order of its single launch, so its bits are the single
 // solve's.  Which instance a block works on: blockIdx.z for the streaming kernels, whose single grids are (column blocks,
 // row blocks); blockIdx.x for the one-workgroup coarse solve and the norm's finish; blockIdx.y for the check, whose single
@@ -26,11 +26,11 @@ namespace k {
 namespace {
 
 template <bool HAS_A>
-__device__ __forceinline__ RxArgs rx_item_args(const NodeBatchItem &it, int N, double dx2, double inv, double sd, double omega, double *out,
+__device__ __forceinline__ VcArgs rx_item_args(const NodeBatchItem &it, int N, double dx2, double inv, double sd, double omega, double *out,
                                                int sign)
 {
-    return RxArgs{VcArgs{N, dx2, inv, sd, omega, HAS_A ? static_cast<const double *>(it.coarse) : nullptr,
-                         static_cast<const double *>(it.in), static_cast<const double *>(it.F), out, sign},
+    return VcArgs{N, dx2, inv, sd, omega, HAS_A ? static_cast<const double *>(it.coarse) : nullptr,
+                  static_cast<const double *>(it.in), static_cast<const double *>(it.F), out, sign,
                   static_cast<const double *>(it.Fc)};
 }
 
@@ -38,9 +38,9 @@ template <bool ZERO_IN, bool PAIR, bool NT, bool HAS_A>
 __global__ __launch_bounds__(TB) void k_wjacobi_rx_b(int N, double dx2, double sd, double omega, const NodeBatchItem *__restrict__ items)
 {
     const NodeBatchItem &it = items[blockIdx.z];
-    const RxArgs x = rx_item_args<HAS_A>(it, N, dx2, 0.0, sd, omega, static_cast<double *>(it.out), +1);
-    if constexpr (PAIR) rx_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, HAS_A>(x);
-    else rx_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, HAS_A>(x);
+    const VcArgs k = rx_item_args<HAS_A>(it, N, dx2, 0.0, sd, omega, static_cast<double *>(it.out), +1);
+    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, HAS_A, true>(k);
+    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, HAS_A, true>(k);
 }
 
 // (the pair form is non-temporal at every size, as k_residual_rx's)
@@ -49,16 +49,16 @@ __global__ __launch_bounds__(TB) void k_residual_rx_b(int N, double dx2, double 
                                                       int sign)
 {
     const NodeBatchItem &it = items[blockIdx.z];
-    const RxArgs x = rx_item_args<HAS_A>(it, N, dx2, inv, sd, 0.0, static_cast<double *>(it.out), sign);
-    if constexpr (PAIR) rx_pairs<OP_RESIDUAL, true, HAS_A>(x);
-    else rx_cols<OP_RESIDUAL, HAS_A>(x);
+    const VcArgs k = rx_item_args<HAS_A>(it, N, dx2, inv, sd, 0.0, static_cast<double *>(it.out), sign);
+    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true, HAS_A, true>(k);
+    else vc_cols<OP_RESIDUAL, HAS_A, true>(k);
 }
 
 template <bool HAS_A>
 __global__ __launch_bounds__(TB) void k_apply_rx_b(int N, double dx2, double inv, double sd, const NodeBatchItem *__restrict__ items)
 {
     const NodeBatchItem &it = items[blockIdx.z];
-    rx_cols<OP_APPLY, HAS_A>(rx_item_args<HAS_A>(it, N, dx2, inv, sd, 0.0, static_cast<double *>(it.out), +1));
+    vc_cols<OP_APPLY, HAS_A, true>(rx_item_args<HAS_A>(it, N, dx2, inv, sd, 0.0, static_cast<double *>(it.out), +1));
 }
 
 // instance z's np partials at part + z*np
@@ -66,13 +66,13 @@ template <bool PAIR, bool NT, bool HAS_A>
 __global__ __launch_bounds__(TB) void k_resnorm_rx_b(int N, double dx2, double inv, double sd, const NodeBatchItem *__restrict__ items,
                                                      double *__restrict__ part, size_t np)
 {
-    rx_resnorm_body<PAIR, NT, HAS_A>(rx_item_args<HAS_A>(items[blockIdx.z], N, dx2, inv, sd, 0.0, part + blockIdx.z * np, +1));
+    resnorm_vc_body<PAIR, NT, HAS_A, true>(rx_item_args<HAS_A>(items[blockIdx.z], N, dx2, inv, sd, 0.0, part + blockIdx.z * np, +1));
 }
 
 // out[i] = sqrt(sum of instance i's np partials): one block per instance, each the single-instance finish
 __global__ __launch_bounds__(1024) void k_resnorm_finish_rx_b(const double *__restrict__ part, size_t np, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part + blockIdx.x * np, np, out + blockIdx.x);
+    resnorm_finish_body(part + blockIdx.x * np, np, out + blockIdx.x);
 }
 
 // one workgroup per instance: its own err0, its own stop, its state at state + 4i (no err_out)
@@ -81,9 +81,9 @@ __global__ __launch_bounds__(1024) void k_gs_relative_rx_b(int N, double h2, dou
                                                            double atol, double rtol, int max_iters, int *__restrict__ state)
 {
     const NodeBatchItem &it = items[blockIdx.x];
-    rx_gs_relative_body(N, h2, inv, sd, HAS_A ? static_cast<const double *>(it.coarse) : nullptr, static_cast<const double *>(it.Fc),
-                        static_cast<double *>(it.out), static_cast<const double *>(it.F), atol, rtol, max_iters, state + 4 * blockIdx.x,
-                        nullptr);
+    gs_relative_vc_body<true, true>(N, h2, inv, sd, HAS_A ? static_cast<const double *>(it.coarse) : nullptr,
+                                    static_cast<const double *>(it.Fc), static_cast<double *>(it.out), static_cast<const double *>(it.F), atol,
+                                    rtol, max_iters, state + 4 * blockIdx.x, nullptr);
 }
 
 // flags[i] = 1 when instance i (blockIdx.y) has a value that is not finite or not >= 0 (the caller zeroes the flags)
@@ -92,68 +92,40 @@ __global__ __launch_bounds__(TB) void k_reaction_check_b(const NodeBatchItem *__
     rx_check_body(static_cast<const double *>(items[blockIdx.y].in), n, flags + blockIdx.y);
 }
 
-inline dim3 with_instances(dim3 g, int n)
-{
-    g.z = n;
-    return g;
-}
-
-// launch K<..., HAS_A> with HAS_A = has_a
-#define MG_RXB_LAUNCH(KERNEL, GRID, BLOCK, LDS, TARGS, ...)                                                    \
-    do {                                                                                                      \
-        if (has_a) hipLaunchKernelGGL((KERNEL<MG_RXB_UNPACK TARGS true>), GRID, BLOCK, LDS, s, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((KERNEL<MG_RXB_UNPACK TARGS false>), GRID, BLOCK, LDS, s, __VA_ARGS__);       \
-    } while (0)
-#define MG_RXB_UNPACK(...) __VA_ARGS__
-
 }  // namespace
 
 // ------------------------------------------------------------------ launchers (the form is chosen as the single launcher
 // of the same name without `_batch` chooses it; has_a: every instance's slot `coarse` holds its coefficient)
 void wjacobi_rx_batch(hipStream_t s, int n, int N, double dx2, double sd, double omega, bool zero_in, bool has_a, const NodeBatchItem *items)
 {
-    const dim3 b(TB);
-    if (use_pairs(N)) {
-        const dim3 g = with_instances(grid_pairs(N), n);
-        const bool nt = N >= NT_MIN_N;
-        if (zero_in) {
-            if (nt) MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (true, true, true, ), N, dx2, sd, omega, items);
-            else MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (true, true, false, ), N, dx2, sd, omega, items);
-        } else {
-            if (nt) MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (false, true, true, ), N, dx2, sd, omega, items);
-            else MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (false, true, false, ), N, dx2, sd, omega, items);
-        }
-        return;
-    }
-    const dim3 g = with_instances(grid_rows(N), n);
-    if (zero_in) MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (true, false, false, ), N, dx2, sd, omega, items);
-    else MG_RXB_LAUNCH(k_wjacobi_rx_b, g, b, 0, (false, false, false, ), N, dx2, sd, omega, items);
+    dispatch_form(N, has_a, [&](auto pair, auto nt, auto a, dim3 g) {
+        g = with_instances(g, n);
+        if (zero_in) hipLaunchKernelGGL((k_wjacobi_rx_b<true, pair(), nt(), a()>), g, dim3(TB), 0, s, N, dx2, sd, omega, items);
+        else hipLaunchKernelGGL((k_wjacobi_rx_b<false, pair(), nt(), a()>), g, dim3(TB), 0, s, N, dx2, sd, omega, items);
+    });
 }
 
 void residual_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items, int sign)
 {
-    const dim3 b(TB);
-    if (use_pairs(N)) MG_RXB_LAUNCH(k_residual_rx_b, with_instances(grid_pairs(N), n), b, 0, (true, ), N, dx2, inv, sd, items, sign);
-    else MG_RXB_LAUNCH(k_residual_rx_b, with_instances(grid_rows(N), n), b, 0, (false, ), N, dx2, inv, sd, items, sign);
+    dispatch_form(N, has_a, [&](auto pair, auto, auto a, dim3 g) {
+        hipLaunchKernelGGL((k_residual_rx_b<pair(), a()>), with_instances(g, n), dim3(TB), 0, s, N, dx2, inv, sd, items, sign);
+    });
 }
 
 void apply_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items)
 {
-    MG_RXB_LAUNCH(k_apply_rx_b, with_instances(grid_rows(N), n), dim3(TB), 0, (), N, dx2, inv, sd, items);
+    const dim3 g = with_instances(grid_rows(N), n);
+    if (has_a) hipLaunchKernelGGL(k_apply_rx_b<true>, g, dim3(TB), 0, s, N, dx2, inv, sd, items);
+    else hipLaunchKernelGGL(k_apply_rx_b<false>, g, dim3(TB), 0, s, N, dx2, inv, sd, items);
 }
 
 void resnorm_rx_batch(hipStream_t s, int n, int N, double dx2, double inv, double sd, bool has_a, const NodeBatchItem *items, double *part,
                       double *out)
 {
     const size_t np = resnorm_partials(N);   // (the same partition as the constant norm)
-    const dim3 b(TB);
-    if (use_pairs(N)) {
-        const dim3 g = with_instances(grid_pairs(N), n);
-        if (N >= NT_MIN_N) MG_RXB_LAUNCH(k_resnorm_rx_b, g, b, 0, (true, true, ), N, dx2, inv, sd, items, part, np);
-        else MG_RXB_LAUNCH(k_resnorm_rx_b, g, b, 0, (true, false, ), N, dx2, inv, sd, items, part, np);
-    } else {
-        MG_RXB_LAUNCH(k_resnorm_rx_b, with_instances(grid_rows(N), n), b, 0, (false, false, ), N, dx2, inv, sd, items, part, np);
-    }
+    dispatch_form(N, has_a, [&](auto pair, auto nt, auto a, dim3 g) {
+        hipLaunchKernelGGL((k_resnorm_rx_b<pair(), nt(), a()>), with_instances(g, n), dim3(TB), 0, s, N, dx2, inv, sd, items, part, np);
+    });
     hipLaunchKernelGGL(k_resnorm_finish_rx_b, dim3(n), dim3(1024), 0, s, part, np, out);
 }
 
@@ -164,7 +136,8 @@ void gauss_seidel_relative_rx_batch(hipStream_t s, int n, int N, double h2, doub
     const size_t lds = 2 * cells * sizeof(double);   // (gauss_seidel_relative_rx's request: N <= 63, inside the default 64 KiB)
     int threads = (int)((cells + 63) / 64 * 64);
     if (threads > 1024) threads = 1024;
-    MG_RXB_LAUNCH(k_gs_relative_rx_b, dim3(n), dim3(threads), lds, (), N, h2, inv, sd, items, atol, rtol, max_iters, state);
+    if (has_a) hipLaunchKernelGGL(k_gs_relative_rx_b<true>, dim3(n), dim3(threads), lds, s, N, h2, inv, sd, items, atol, rtol, max_iters, state);
+    else hipLaunchKernelGGL(k_gs_relative_rx_b<false>, dim3(n), dim3(threads), lds, s, N, h2, inv, sd, items, atol, rtol, max_iters, state);
 }
 
 void reaction_check_batch(hipStream_t s, int n, size_t count, const NodeBatchItem *items, int *flags)

@@ -8,7 +8,7 @@
 // without a coefficient; without one no array of ones is streamed.  Memory-bound: a sweep moves 40 B per point with a
 // (U, a, s, F in, U out) and 32 B without (U, s, F in, U out).  d = (((aN + aS) + aE) + aW) + (sd + s*dx2), q = 1/d and
 // c = omega*q are formed per point: one product and one sum more than k_wjacobi_vc.
-// The __device__ bodies live in mg_reaction_impl.h, layered over mg_varcoef_impl.h.
+// The __device__ bodies are mg_varcoef_impl.h's with HAS_S = true; mg_reaction_impl.h adds the check of s.
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"
@@ -20,35 +20,35 @@ namespace k {
 namespace {
 
 template <bool ZERO_IN, bool PAIR, bool NT, bool HAS_A>
-__global__ __launch_bounds__(TB) void k_wjacobi_rx(RxArgs x)
+__global__ __launch_bounds__(TB) void k_wjacobi_rx(VcArgs k)
 {
-    if constexpr (PAIR) rx_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, HAS_A>(x);
-    else rx_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, HAS_A>(x);
+    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, HAS_A, true>(k);
+    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, HAS_A, true>(k);
 }
 
 // (the pair form is non-temporal at every size, as k_residual_vc's: no NT parameter)
 template <bool PAIR, bool HAS_A>
-__global__ __launch_bounds__(TB) void k_residual_rx(RxArgs x)
+__global__ __launch_bounds__(TB) void k_residual_rx(VcArgs k)
 {
-    if constexpr (PAIR) rx_pairs<OP_RESIDUAL, true, HAS_A>(x);
-    else rx_cols<OP_RESIDUAL, HAS_A>(x);
+    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true, HAS_A, true>(k);
+    else vc_cols<OP_RESIDUAL, HAS_A, true>(k);
 }
 
 template <bool HAS_A>
-__global__ __launch_bounds__(TB) void k_apply_rx(RxArgs x)
+__global__ __launch_bounds__(TB) void k_apply_rx(VcArgs k)
 {
-    rx_cols<OP_APPLY, HAS_A>(x);
+    vc_cols<OP_APPLY, HAS_A, true>(k);
 }
 
 template <bool PAIR, bool NT, bool HAS_A>
-__global__ __launch_bounds__(TB) void k_resnorm_rx(RxArgs x)
+__global__ __launch_bounds__(TB) void k_resnorm_rx(VcArgs k)
 {
-    rx_resnorm_body<PAIR, NT, HAS_A>(x);
+    resnorm_vc_body<PAIR, NT, HAS_A, true>(k);
 }
 
 __global__ __launch_bounds__(1024) void k_resnorm_finish_rx(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part, n, out);
+    resnorm_finish_body(part, n, out);
 }
 
 __global__ __launch_bounds__(1024) void k_gs_relative_rx(int N, double h2, double inv, double sd, const double *__restrict__ Ag,
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(1024) void k_gs_relative_rx(int N, double h2, doubl
                                                          const double *__restrict__ Fg, double atol, double rtol, int max_iters,
                                                          int *__restrict__ state, double *__restrict__ err_out)
 {
-    rx_gs_relative_body(N, h2, inv, sd, Ag, Sg, Ug, Fg, atol, rtol, max_iters, state, err_out);
+    gs_relative_vc_body<true, true>(N, h2, inv, sd, Ag, Sg, Ug, Fg, atol, rtol, max_iters, state, err_out);
 }
 
 __global__ __launch_bounds__(TB) void k_reaction_check(const double *__restrict__ S, size_t n, int *__restrict__ flag)
@@ -64,62 +64,43 @@ __global__ __launch_bounds__(TB) void k_reaction_check(const double *__restrict_
     rx_check_body(S, n, flag);
 }
 
-// launch K<..., HAS_A> with HAS_A = (A != nullptr)
-#define MG_RX_LAUNCH(KERNEL, GRID, ...)                                                                       \
-    do {                                                                                                      \
-        if (x.k.A) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true>), GRID, dim3(TB), 0, s, x);                  \
-        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false>), GRID, dim3(TB), 0, s, x);                       \
-    } while (0)
-
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
 void wjacobi_rx(hipStream_t s, int N, double dx2, double sd, double omega, const double *A, const double *S, const double *in,
                 const double *F, double *out)
 {
-    const RxArgs x{VcArgs{N, dx2, 0.0, sd, omega, A, in, F, out, +1}, S};
-    if (use_pairs(N)) {
-        const dim3 g = grid_pairs(N);
-        const bool nt = N >= NT_MIN_N;
-        if (!in) {
-            if (nt) MG_RX_LAUNCH(k_wjacobi_rx, g, true, true, true);
-            else MG_RX_LAUNCH(k_wjacobi_rx, g, true, true, false);
-        } else {
-            if (nt) MG_RX_LAUNCH(k_wjacobi_rx, g, false, true, true);
-            else MG_RX_LAUNCH(k_wjacobi_rx, g, false, true, false);
-        }
-        return;
-    }
-    if (!in) MG_RX_LAUNCH(k_wjacobi_rx, grid_rows(N), true, false, false);
-    else MG_RX_LAUNCH(k_wjacobi_rx, grid_rows(N), false, false, false);
+    const VcArgs k{N, dx2, 0.0, sd, omega, A, in, F, out, +1, S};
+    dispatch_form(N, A != nullptr, [&](auto pair, auto nt, auto has_a, dim3 g) {
+        if (!in) hipLaunchKernelGGL((k_wjacobi_rx<true, pair(), nt(), has_a()>), g, dim3(TB), 0, s, k);
+        else hipLaunchKernelGGL((k_wjacobi_rx<false, pair(), nt(), has_a()>), g, dim3(TB), 0, s, k);
+    });
 }
 
 void residual_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U,
                  const double *F, double *D, int sign)
 {
-    const RxArgs x{VcArgs{N, dx2, inv, sd, 0.0, A, U, F, D, sign}, S};
-    if (use_pairs(N)) MG_RX_LAUNCH(k_residual_rx, grid_pairs(N), true);
-    else MG_RX_LAUNCH(k_residual_rx, grid_rows(N), false);
+    const VcArgs k{N, dx2, inv, sd, 0.0, A, U, F, D, sign, S};
+    dispatch_form(N, A != nullptr, [&](auto pair, auto, auto has_a, dim3 g) {
+        hipLaunchKernelGGL((k_residual_rx<pair(), has_a()>), g, dim3(TB), 0, s, k);
+    });
 }
 
 void apply_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U, double *out)
 {
-    const RxArgs x{VcArgs{N, dx2, inv, sd, 0.0, A, U, nullptr, out, +1}, S};
-    if (A) hipLaunchKernelGGL(k_apply_rx<true>, grid_rows(N), dim3(TB), 0, s, x);
-    else hipLaunchKernelGGL(k_apply_rx<false>, grid_rows(N), dim3(TB), 0, s, x);
+    const VcArgs k{N, dx2, inv, sd, 0.0, A, U, nullptr, out, +1, S};
+    if (A) hipLaunchKernelGGL(k_apply_rx<true>, grid_rows(N), dim3(TB), 0, s, k);
+    else hipLaunchKernelGGL(k_apply_rx<false>, grid_rows(N), dim3(TB), 0, s, k);
 }
 
 void resnorm_rx(hipStream_t s, int N, double dx2, double inv, double sd, const double *A, const double *S, const double *U,
                 const double *F, double *part, double *out)
 {
     const size_t np = resnorm_partials(N);   // (the same partition as the constant norm)
-    const RxArgs x{VcArgs{N, dx2, inv, sd, 0.0, A, U, F, part, +1}, S};
-    if (use_pairs(N)) {
-        if (N >= NT_MIN_N) MG_RX_LAUNCH(k_resnorm_rx, grid_pairs(N), true, true);
-        else MG_RX_LAUNCH(k_resnorm_rx, grid_pairs(N), true, false);
-    } else {
-        MG_RX_LAUNCH(k_resnorm_rx, grid_rows(N), false, false);
-    }
+    const VcArgs k{N, dx2, inv, sd, 0.0, A, U, F, part, +1, S};
+    dispatch_form(N, A != nullptr, [&](auto pair, auto nt, auto has_a, dim3 g) {
+        hipLaunchKernelGGL((k_resnorm_rx<pair(), nt(), has_a()>), g, dim3(TB), 0, s, k);
+    });
     hipLaunchKernelGGL(k_resnorm_finish_rx, dim3(1), dim3(1024), 0, s, part, np, out);
 }
 

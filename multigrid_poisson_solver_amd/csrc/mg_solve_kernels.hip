@@ -10,47 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"
+#include "mg_solver_common.h"
 
 namespace mg {
 namespace k {
 
 namespace {
 
-constexpr int TB = 256;       // threads per block of the streaming kernels
-constexpr int ROWS_PB = 4;    // rows per block, one point per lane
-constexpr int PR = 4;         // rows per thread of the 16-byte forms (rolling window of three row pairs)
-constexpr int PAIR_MIN_N = 512;
-constexpr int NT_MIN_N = 4096;   // from here on the arrays are far larger than the caches: non-temporal F loads
-typedef double double2_s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over the block in a fixed order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double sm[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sm[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        const int nw = (blockDim.x + 63) >> 6;
-        for (int i = 0; i < nw; ++i) r += sm[i];
-    }
-    return r;
-}
-
-__device__ __forceinline__ bool rim(int r, int c, int N)
-{
-    return r == 0 || c == 0 || r == N - 1 || c == N - 1;
-}
+// (the block shape, wave_sum / block_sum, rim, the norm's finish and the grids: mg_solver_common.h)
 
 // 5-point bracket in the reference's order: row+1, row-1, col+1, col-1, then -4*centre (src/MG_solver_CPU.cpp:590)
 __device__ __forceinline__ double star_minus4(const double *__restrict__ A, size_t p, int N)
@@ -76,10 +43,10 @@ __device__ __forceinline__ double star_minus(const double *__restrict__ A, size_
 }
 
 template <bool NT>
-__device__ __forceinline__ double2_s load_f(const double *p)
+__device__ __forceinline__ double2_v load_f(const double *p)
 {
-    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const double2_s *>(p));
-    return *reinterpret_cast<const double2_s *>(p);
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const double2_v *>(p));
+    return *reinterpret_cast<const double2_v *>(p);
 }
 
 // ---------------------------------------------------------------- weighted Jacobi, one sweep
@@ -134,18 +101,18 @@ __device__ __forceinline__ void wjacobi_pairs_body(int N, double dx2, double cw,
     if (c >= N) return;
     auto row_pair = [&](int r) {
         r = r < 0 ? 0 : (r < N ? r : N - 1);   // (rows beyond the grid: clamped, never used)
-        return *reinterpret_cast<const double2_s *>(in + (size_t)r * N + c);
+        return *reinterpret_cast<const double2_v *>(in + (size_t)r * N + c);
     };
-    double2_s dn = row_pair(r0 - 1), ctr = row_pair(r0);
+    double2_v dn = row_pair(r0 - 1), ctr = row_pair(r0);
 #pragma unroll
     for (int k = 0; k < PR; ++k) {
         const int r = r0 + k;
         if (r >= N) break;
-        const double2_s up = row_pair(r + 1);
+        const double2_v up = row_pair(r + 1);
         const size_t p = (size_t)r * N + c;
-        double2_s o = ctr;
+        double2_v o = ctr;
         if (r > 0 && r < N - 1) {
-            const double2_s f = load_f<NT>(F + p);
+            const double2_v f = load_f<NT>(F + p);
             if (c > 0) {
                 const double w = in[p - 1];
                 o.x = ctr.x + cw * (up.x + dn.x + ctr.y + w - centre<SH>(ctr.x, d) - dx2 * f.x);
@@ -155,8 +122,8 @@ __device__ __forceinline__ void wjacobi_pairs_body(int N, double dx2, double cw,
                 o.y = ctr.y + cw * (up.y + dn.y + e + ctr.x - centre<SH>(ctr.y, d) - dx2 * f.y);
             }
         }
-        if (NT) __builtin_nontemporal_store(o, reinterpret_cast<double2_s *>(out + p));
-        else *reinterpret_cast<double2_s *>(out + p) = o;
+        if (NT) __builtin_nontemporal_store(o, reinterpret_cast<double2_v *>(out + p));
+        else *reinterpret_cast<double2_v *>(out + p) = o;
         dn = ctr;
         ctr = up;
     }
@@ -222,9 +189,9 @@ __device__ __forceinline__ void resnorm_pairs_body(int N, double inv, const doub
         const int cl = c > 0 ? c - 1 : 0, cr = c + 2 < N ? c + 2 : N - 1;
         auto row_pair = [&](int r) {
             r = r < 0 ? 0 : (r < N ? r : N - 1);
-            return *reinterpret_cast<const double2_s *>(U + (size_t)r * N + c);
+            return *reinterpret_cast<const double2_v *>(U + (size_t)r * N + c);
         };
-        double2_s up = {0.0, 0.0}, mid = {0.0, 0.0};
+        double2_v up = {0.0, 0.0}, mid = {0.0, 0.0};
         if (HAS_U) {
             up = row_pair(r0 - 1);
             mid = row_pair(r0);
@@ -233,12 +200,12 @@ __device__ __forceinline__ void resnorm_pairs_body(int N, double inv, const doub
         for (int k = 0; k < PR; ++k) {
             const int r = r0 + k;
             if (r >= N) break;
-            double2_s down = {0.0, 0.0};
+            double2_v down = {0.0, 0.0};
             if (HAS_U) down = row_pair(r + 1);
             if (r > 0 && r < N - 1) {
                 const size_t p = (size_t)r * N + c;
-                const double2_s f = load_f<NT>(F + p);
-                double2_s d = f;
+                const double2_v f = load_f<NT>(F + p);
+                double2_v d = f;
                 if (HAS_U) {
                     const double left = U[(size_t)r * N + cl], right = U[(size_t)r * N + cr];
                     d.x = inv * (down.x + up.x + mid.y + left - centre<SH>(mid.x, dc)) - f.x;
@@ -274,15 +241,6 @@ __global__ __launch_bounds__(TB) void k_resnorm_pairs_sh(int N, double inv, doub
                                                          const double *__restrict__ F, double *__restrict__ part)
 {
     resnorm_pairs_body<true, NT, true>(N, inv, U, F, part, dc);
-}
-
-// second stage: *out = sqrt(sum of the n partials), one block in a fixed order (run-to-run reproducible)
-__device__ __forceinline__ void resnorm_finish_body(const double *__restrict__ part, size_t n, double *__restrict__ out)
-{
-    double acc = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc += part[i];
-    const double s = block_sum(acc);
-    if (threadIdx.x == 0) *out = sqrt(s);
 }
 
 __global__ __launch_bounds__(1024) void k_resnorm_finish(const double *__restrict__ part, size_t n, double *__restrict__ out)
@@ -522,10 +480,6 @@ __global__ __launch_bounds__(TB) void k_copy_b(size_t n, const NodeBatchItem *__
     double *__restrict__ dst = static_cast<double *>(it.out);
     for (size_t i = (size_t)blockIdx.x * TB + threadIdx.x; i < n; i += (size_t)gridDim.x * TB) dst[i] = src[i];
 }
-
-inline dim3 grid_rows(int N) { return dim3((N + TB - 1) / TB, (N + ROWS_PB - 1) / ROWS_PB); }
-inline bool use_pairs(int N) { return N % 2 == 0 && N >= PAIR_MIN_N; }
-inline dim3 grid_pairs(int N) { return dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR); }
 
 }  // namespace
 

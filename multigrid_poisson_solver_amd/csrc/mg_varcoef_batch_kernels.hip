@@ -32,16 +32,16 @@ template <bool ZERO_IN, bool PAIR, bool NT>
 __global__ __launch_bounds__(TB) void k_wjacobi_vc_b(int N, double dx2, double sd, double omega, const NodeBatchItem *__restrict__ items)
 {
     const VcArgs k = item_args(items[blockIdx.z], N, dx2, 0.0, sd, omega, +1);
-    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT>(k);
-    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP>(k);
+    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, true, false>(k);
+    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, true, false>(k);
 }
 
 template <bool PAIR>
 __global__ __launch_bounds__(TB) void k_residual_vc_b(int N, double inv, double sd, const NodeBatchItem *__restrict__ items, int sign)
 {
     const VcArgs k = item_args(items[blockIdx.z], N, 0.0, inv, sd, 0.0, sign);
-    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true>(k);
-    else vc_cols<OP_RESIDUAL>(k);
+    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true, true, false>(k);
+    else vc_cols<OP_RESIDUAL, true, false>(k);
 }
 
 // the operator alone (apply_vc): the coefficient may be absent PER INSTANCE (a = 1 through the same expressions, as the
@@ -49,8 +49,8 @@ __global__ __launch_bounds__(TB) void k_residual_vc_b(int N, double inv, double 
 __global__ __launch_bounds__(TB) void k_apply_vc_b(int N, double inv, double sd, const NodeBatchItem *__restrict__ items)
 {
     const VcArgs k = item_args(items[blockIdx.z], N, 0.0, inv, sd, 0.0, +1);
-    if (k.A) vc_cols<OP_APPLY, true>(k);
-    else vc_cols<OP_APPLY, false>(k);
+    if (k.A) vc_cols<OP_APPLY, true, false>(k);
+    else vc_cols<OP_APPLY, false, false>(k);
 }
 
 // instance z's np partials at part + z*np
@@ -58,15 +58,15 @@ template <bool PAIR, bool NT>
 __global__ __launch_bounds__(TB) void k_resnorm_vc_b(int N, double inv, double sd, const NodeBatchItem *__restrict__ items,
                                                      double *__restrict__ part, size_t np)
 {
-    const NodeBatchItem &it = items[blockIdx.z];
-    resnorm_vc_body<PAIR, NT>(N, inv, sd, static_cast<const double *>(it.coarse), static_cast<const double *>(it.in),
-                              static_cast<const double *>(it.F), part + blockIdx.z * np);
+    VcArgs k = item_args(items[blockIdx.z], N, 0.0, inv, sd, 0.0, +1);
+    k.out = part + blockIdx.z * np;
+    resnorm_vc_body<PAIR, NT, true, false>(k);
 }
 
 // out[i] = sqrt(sum of instance i's np partials): one block per instance, each the single-instance finish
 __global__ __launch_bounds__(1024) void k_resnorm_finish_vc_b(const double *__restrict__ part, size_t np, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part + blockIdx.x * np, np, out + blockIdx.x);
+    resnorm_finish_body(part + blockIdx.x * np, np, out + blockIdx.x);
 }
 
 // one workgroup per instance: its own err0, its own stop, its state at state + 4i (no err_out)
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(1024) void k_gs_relative_vc_b(int N, double h2, dou
                                                            double atol, double rtol, int max_iters, int *__restrict__ state)
 {
     const NodeBatchItem &it = items[blockIdx.x];
-    gs_relative_vc_body(N, h2, inv, sd, static_cast<const double *>(it.coarse), static_cast<double *>(it.out),
-                        static_cast<const double *>(it.F), atol, rtol, max_iters, state + 4 * blockIdx.x, nullptr);
+    gs_relative_vc_body<false, false>(N, h2, inv, sd, static_cast<const double *>(it.coarse), nullptr, static_cast<double *>(it.out),
+                                      static_cast<const double *>(it.F), atol, rtol, max_iters, state + 4 * blockIdx.x, nullptr);
 }
 
 __global__ __launch_bounds__(TB) void k_coef_coarsen_b(int N, int M, const NodeBatchItem *__restrict__ items, const int *__restrict__ lo,
@@ -91,40 +91,24 @@ __global__ __launch_bounds__(TB) void k_coef_check_b(const NodeBatchItem *__rest
     coef_check_body(static_cast<const double *>(items[blockIdx.y].in), n, flags + blockIdx.y);
 }
 
-inline dim3 with_instances(dim3 g, int n)
-{
-    g.z = n;
-    return g;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ launchers (the form is chosen as the single launcher
 // of the same name without `_batch` chooses it)
 void wjacobi_vc_batch(hipStream_t s, int n, int N, double dx2, double sd, double omega, bool zero_in, const NodeBatchItem *items)
 {
-    const dim3 b(TB);
-    if (use_pairs(N)) {
-        const dim3 g = with_instances(grid_pairs(N), n);
-        const bool nt = N >= NT_MIN_N;
-        if (zero_in) {
-            if (nt) hipLaunchKernelGGL((k_wjacobi_vc_b<true, true, true>), g, b, 0, s, N, dx2, sd, omega, items);
-            else hipLaunchKernelGGL((k_wjacobi_vc_b<true, true, false>), g, b, 0, s, N, dx2, sd, omega, items);
-        } else {
-            if (nt) hipLaunchKernelGGL((k_wjacobi_vc_b<false, true, true>), g, b, 0, s, N, dx2, sd, omega, items);
-            else hipLaunchKernelGGL((k_wjacobi_vc_b<false, true, false>), g, b, 0, s, N, dx2, sd, omega, items);
-        }
-        return;
-    }
-    const dim3 g = with_instances(grid_rows(N), n);
-    if (zero_in) hipLaunchKernelGGL((k_wjacobi_vc_b<true, false, false>), g, b, 0, s, N, dx2, sd, omega, items);
-    else hipLaunchKernelGGL((k_wjacobi_vc_b<false, false, false>), g, b, 0, s, N, dx2, sd, omega, items);
+    dispatch_form(N, true, [&](auto pair, auto nt, auto, dim3 g) {
+        g = with_instances(g, n);
+        if (zero_in) hipLaunchKernelGGL((k_wjacobi_vc_b<true, pair(), nt()>), g, dim3(TB), 0, s, N, dx2, sd, omega, items);
+        else hipLaunchKernelGGL((k_wjacobi_vc_b<false, pair(), nt()>), g, dim3(TB), 0, s, N, dx2, sd, omega, items);
+    });
 }
 
 void residual_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items, int sign)
 {
-    if (use_pairs(N)) hipLaunchKernelGGL(k_residual_vc_b<true>, with_instances(grid_pairs(N), n), dim3(TB), 0, s, N, inv, sd, items, sign);
-    else hipLaunchKernelGGL(k_residual_vc_b<false>, with_instances(grid_rows(N), n), dim3(TB), 0, s, N, inv, sd, items, sign);
+    dispatch_form(N, true, [&](auto pair, auto, auto, dim3 g) {
+        hipLaunchKernelGGL(k_residual_vc_b<pair()>, with_instances(g, n), dim3(TB), 0, s, N, inv, sd, items, sign);
+    });
 }
 
 void apply_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items)
@@ -135,13 +119,9 @@ void apply_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const No
 void resnorm_vc_batch(hipStream_t s, int n, int N, double inv, double sd, const NodeBatchItem *items, double *part, double *out)
 {
     const size_t np = resnorm_partials(N);   // (the same partition as the constant norm)
-    if (use_pairs(N)) {
-        const dim3 g = with_instances(grid_pairs(N), n);
-        if (N >= NT_MIN_N) hipLaunchKernelGGL((k_resnorm_vc_b<true, true>), g, dim3(TB), 0, s, N, inv, sd, items, part, np);
-        else hipLaunchKernelGGL((k_resnorm_vc_b<true, false>), g, dim3(TB), 0, s, N, inv, sd, items, part, np);
-    } else {
-        hipLaunchKernelGGL((k_resnorm_vc_b<false, false>), with_instances(grid_rows(N), n), dim3(TB), 0, s, N, inv, sd, items, part, np);
-    }
+    dispatch_form(N, true, [&](auto pair, auto nt, auto, dim3 g) {
+        hipLaunchKernelGGL((k_resnorm_vc_b<pair(), nt()>), with_instances(g, n), dim3(TB), 0, s, N, inv, sd, items, part, np);
+    });
     hipLaunchKernelGGL(k_resnorm_finish_vc_b, dim3(n), dim3(1024), 0, s, part, np, out);
 }
 

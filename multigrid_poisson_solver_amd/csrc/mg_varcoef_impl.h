@@ -1,59 +1,33 @@
-// mg_varcoef_impl.h -- the point code of the variable-coefficient kernels (include/mg_varcoef.h), shared by the single-
-// instance kernels (mg_varcoef_kernels.hip) and their batched forms (mg_varcoef_batch_kernels.hip): both translation units
-// compile THESE bodies with the same flags (-ffp-contract=off), so an instance of a batched launch runs the code, the block
-// partition and the summation order of its single launch and gives the same bits.  A body takes the arrays of one instance
-// as arguments and reads blockIdx.x / blockIdx.y only as (column block, row block) of that instance; which instance a block
-// works on is the caller's business (blockIdx.z of the batched streaming kernels, blockIdx.x of the one-workgroup ones).
-// Everything here sits in an unnamed namespace: each translation unit has its own copy, and the kernels of
-// mg_varcoef_kernels.hip keep the names they had when these bodies were written there.
+// mg_varcoef_impl.h -- the point code of the variable-coefficient kernels (include/mg_varcoef.h) AND of the reaction kernels
+// (include/mg_reaction.h): ONE column body, ONE pair body, ONE norm body and ONE coarse solve, with two compile-time switches.
+//   HAS_A   a coefficient a(x, y) is streamed (rolling window of three rows); false: no array of ones is read, a = 1 goes
+//           through the same expressions (every face exactly 1)
+//   HAS_S   a nodal reaction term s(x, y) is streamed: the centre gets sd + s*dx2 per point (one load at the centre row, no
+//           window) instead of the level constant sd; false: k.S is not looked at
+// The `_vc` kernels are <HAS_A = true, HAS_S = false> (the operator alone also without a), the `_rx` kernels <HAS_A either,
+// HAS_S = true>.  A further per-point term of the centre plugs in the same way: a pointer in VcArgs, a switch, and its
+// expression in centre_sd -- the row loops, the rim and the stores are not touched.
+// The bodies are shared by the single-instance kernels (mg_varcoef_kernels.hip, mg_reaction_kernels.hip) and their batched
+// forms (mg_varcoef_batch_kernels.hip, mg_reaction_batch_kernels.hip): all translation units compile THESE bodies with the
+// same flags (-ffp-contract=off), so an instance of a batched launch runs the code, the block partition and the summation
+// order of its single launch and gives the same bits.  A body takes the arrays of one instance as arguments and reads
+// blockIdx.x / blockIdx.y only as (column block, row block) of that instance; which instance a block works on is the caller's
+// business (blockIdx.z of the batched streaming kernels, blockIdx.x of the one-workgroup ones).  The block shape, the block
+// sums and the norm's finish are mg_solver_common.h's, the ones mg_solve_kernels.hip runs: the norm of a == 1 is the constant
+// norm bit for bit (test_unit_coefficient_is_the_constant_solver compares the histories with ==).
+// Everything here sits in an unnamed namespace: each translation unit has its own copy.
 #ifndef MG_VARCOEF_IMPL_H
 #define MG_VARCOEF_IMPL_H
 
 #include <hip/hip_runtime.h>
 
 #include "mg_internal.h"
+#include "mg_solver_common.h"
 
 namespace mg {
 namespace k {
 
 namespace {
-
-constexpr int TB = 256;          // threads per block of the streaming kernels
-constexpr int ROWS_PB = 4;       // rows per block, one point per lane
-constexpr int PR = 4;            // rows per thread of the 16-byte forms
-constexpr int PAIR_MIN_N = 512;
-constexpr int NT_MIN_N = 4096;
-typedef double double2_v __attribute__((ext_vector_type(2)));
-
-// the block sums of mg_solve_kernels.hip, order for order: the norm of a == 1 must be the constant norm bit for bit
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over the block in a fixed order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double sm[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sm[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        const int nw = (blockDim.x + 63) >> 6;
-        for (int i = 0; i < nw; ++i) r += sm[i];
-    }
-    return r;
-}
-
-__device__ __forceinline__ bool rim(int r, int c, int N)
-{
-    return r == 0 || c == 0 || r == N - 1 || c == N - 1;
-}
 
 template <bool NT>
 __device__ __forceinline__ double2_v load_f(const double *p)
@@ -98,9 +72,19 @@ struct VcArgs {
     int N;
     double dx2, inv, sd, omega;
     const double *A, *U, *F;   // coefficient, field (not read by OP_SWEEP_ZERO), source (not read by OP_APPLY)
-    double *out;
+    double *out;               // (the norm: its per-block partials)
     int sign;                  // OP_RESIDUAL
+    const double *S;           // HAS_S: the level's nodal reaction term (needs dx2 whatever the operation); else not read
 };
+
+// the centre's shift term of one point: the level constant, or with a reaction term (include/mg_reaction.h) t = s*dx2,
+// sdp = sd + t, each rounded once
+template <bool HAS_S>
+__device__ __forceinline__ double centre_sd(const VcArgs &k, double s)
+{
+    if constexpr (HAS_S) return k.sd + s * k.dx2;
+    else return k.sd;
+}
 
 template <Op OP>
 __device__ __forceinline__ double point(const VcArgs &k, const Faces &f, double F, double u, double u_nxt, double u_prv,
@@ -113,8 +97,7 @@ __device__ __forceinline__ double point(const VcArgs &k, const Faces &f, double 
 }
 
 // ---------------------------------------------------------------- one column per lane (any N)
-// HAS_A = false (mg_applyOperator without a coefficient): a = 1 through the same expressions
-template <Op OP, bool HAS_A = true>
+template <Op OP, bool HAS_A, bool HAS_S>
 __device__ __forceinline__ void vc_cols(const VcArgs &k)
 {
     const int N = k.N;
@@ -125,6 +108,7 @@ __device__ __forceinline__ void vc_cols(const VcArgs &k)
     const bool col_in = c > 0 && c < N - 1;
     constexpr bool READS_U = OP != OP_SWEEP_ZERO, READS_F = OP != OP_APPLY;
     const double *__restrict__ A = k.A;
+    const double *__restrict__ S = k.S;
     const double *__restrict__ U = k.U;
     const double *__restrict__ F = k.F;
     auto row = [&](const double *__restrict__ X, int r) {
@@ -159,7 +143,7 @@ __device__ __forceinline__ void vc_cols(const VcArgs &k)
                 u_east = U[line + cr];
                 u_west = U[line + cl];
             }
-            const Faces f = faces(a_mid, a_nxt, a_prv, a_east, a_west, k.sd);
+            const Faces f = faces(a_mid, a_nxt, a_prv, a_east, a_west, centre_sd<HAS_S>(k, HAS_S ? S[p] : 0.0));
             v = point<OP>(k, f, READS_F ? F[p] : 0.0, u_mid, u_nxt, u_prv, u_east, u_west);
         }
         if (OP == OP_RESIDUAL && k.sign < 0) v = -v;
@@ -172,10 +156,10 @@ __device__ __forceinline__ void vc_cols(const VcArgs &k)
 }
 
 // ---------------------------------------------------------------- two columns per lane, 16-byte accesses
-// (even N, 16-byte aligned arrays: every pair is aligned and inside its row).  NT: F through non-temporal loads and the
-// output through non-temporal stores.  The sweeps take NT from NT_MIN_N on; the residual -- whose output is read once, by
+// (even N, 16-byte aligned arrays: every pair is aligned and inside its row).  NT: F and s through non-temporal loads and
+// the output through non-temporal stores.  The sweeps take NT from NT_MIN_N on; the residual -- whose output is read once, by
 // the restriction -- is instantiated with NT = true only, whatever N, as k_residual_pairs.
-template <Op OP, bool NT>
+template <Op OP, bool NT, bool HAS_A, bool HAS_S>
 __device__ __forceinline__ void vc_pairs(const VcArgs &k)
 {
     const int N = k.N;
@@ -185,13 +169,19 @@ __device__ __forceinline__ void vc_pairs(const VcArgs &k)
     const int cl = c > 0 ? c - 1 : 0, cr = c + 2 < N ? c + 2 : N - 1;
     constexpr bool READS_U = OP != OP_SWEEP_ZERO;
     const double *__restrict__ A = k.A;
+    const double *__restrict__ S = k.S;
     const double *__restrict__ U = k.U;
     const double *__restrict__ F = k.F;
     auto row_pair = [&](const double *__restrict__ X, int r) {
         r = r < 0 ? 0 : (r < N ? r : N - 1);
         return *reinterpret_cast<const double2_v *>(X + (size_t)r * N + c);
     };
-    double2_v a_prv = row_pair(A, r0 - 1), a_mid = row_pair(A, r0), u_prv = {0.0, 0.0}, u_mid = {0.0, 0.0};
+    const double2_v ones = {1.0, 1.0};
+    double2_v a_prv = ones, a_mid = ones, u_prv = {0.0, 0.0}, u_mid = {0.0, 0.0};
+    if constexpr (HAS_A) {
+        a_prv = row_pair(A, r0 - 1);
+        a_mid = row_pair(A, r0);
+    }
     if constexpr (READS_U) {
         u_prv = row_pair(U, r0 - 1);
         u_mid = row_pair(U, r0);
@@ -200,20 +190,22 @@ __device__ __forceinline__ void vc_pairs(const VcArgs &k)
     for (int i = 0; i < PR; ++i) {
         const int r = r0 + i;
         if (r >= N) break;
-        const double2_v a_nxt = row_pair(A, r + 1);
-        double2_v u_nxt = {0.0, 0.0};
+        double2_v a_nxt = ones, u_nxt = {0.0, 0.0};
+        if constexpr (HAS_A) a_nxt = row_pair(A, r + 1);
         if constexpr (READS_U) u_nxt = row_pair(U, r + 1);
         const size_t line = (size_t)r * N, p = line + c;
         double2_v v = {0.0, 0.0};
         if (OP == OP_SWEEP) v = u_mid;
         if (r > 0 && r < N - 1) {
             const double2_v f = load_f<NT>(F + p);
+            double2_v s = {0.0, 0.0};
+            if constexpr (HAS_S) s = load_f<NT>(S + p);
             if (c > 0) {
-                const Faces fc = faces(a_mid.x, a_nxt.x, a_prv.x, a_mid.y, A[line + cl], k.sd);
+                const Faces fc = faces(a_mid.x, a_nxt.x, a_prv.x, a_mid.y, HAS_A ? A[line + cl] : 1.0, centre_sd<HAS_S>(k, s.x));
                 v.x = point<OP>(k, fc, f.x, u_mid.x, u_nxt.x, u_prv.x, u_mid.y, READS_U ? U[line + cl] : 0.0);
             }
             if (c + 1 < N - 1) {
-                const Faces fc = faces(a_mid.y, a_nxt.y, a_prv.y, A[line + cr], a_mid.x, k.sd);
+                const Faces fc = faces(a_mid.y, a_nxt.y, a_prv.y, HAS_A ? A[line + cr] : 1.0, a_mid.x, centre_sd<HAS_S>(k, s.y));
                 v.y = point<OP>(k, fc, f.y, u_mid.y, u_nxt.y, u_prv.y, READS_U ? U[line + cr] : 0.0, u_mid.x);
             }
         }
@@ -229,12 +221,16 @@ __device__ __forceinline__ void vc_pairs(const VcArgs &k)
 
 // ---------------------------------------------------------------- residual L2 norm
 // per-block partial sums of d^2 over interior points, d = inv*b(U) - F, in the partition and the order of k_resnorm /
-// k_resnorm_pairs (mg_solve_kernels.hip) for the same N; nothing but the partials is written
-template <bool PAIR, bool NT>
-__device__ __forceinline__ void resnorm_vc_body(int N, double inv, double sd, const double *__restrict__ A,
-                                                const double *__restrict__ U, const double *__restrict__ F,
-                                                double *__restrict__ part)
+// k_resnorm_pairs (mg_solve_kernels.hip) for the same N; nothing but the partials (k.out) is written
+template <bool PAIR, bool NT, bool HAS_A, bool HAS_S>
+__device__ __forceinline__ void resnorm_vc_body(const VcArgs &k)
 {
+    const int N = k.N;
+    const double inv = k.inv;
+    const double *__restrict__ A = k.A;
+    const double *__restrict__ S = k.S;
+    const double *__restrict__ U = k.U;
+    const double *__restrict__ F = k.F;
     double acc = 0.0;
     if constexpr (!PAIR) {
         const int c = blockIdx.x * TB + threadIdx.x;
@@ -245,7 +241,8 @@ __device__ __forceinline__ void resnorm_vc_body(int N, double inv, double sd, co
                 const int r = r0 + i;
                 if (r < N && !rim(r, c, N)) {
                     const size_t p = (size_t)r * N + c;
-                    const Faces f = faces(A[p], A[p + N], A[p - N], A[p + 1], A[p - 1], sd);
+                    const double sdp = centre_sd<HAS_S>(k, HAS_S ? S[p] : 0.0);
+                    const Faces f = HAS_A ? faces(A[p], A[p + N], A[p - N], A[p + 1], A[p - 1], sdp) : faces(1.0, 1.0, 1.0, 1.0, 1.0, sdp);
                     const double d = inv * bracket(f, U[p], U[p + N], U[p - N], U[p + 1], U[p - 1]) - F[p];
                     acc += d * d;
                 }
@@ -260,22 +257,31 @@ __device__ __forceinline__ void resnorm_vc_body(int N, double inv, double sd, co
                 r = r < 0 ? 0 : (r < N ? r : N - 1);
                 return *reinterpret_cast<const double2_v *>(X + (size_t)r * N + c);
             };
-            double2_v a_prv = row_pair(A, r0 - 1), a_mid = row_pair(A, r0), u_prv = row_pair(U, r0 - 1), u_mid = row_pair(U, r0);
+            const double2_v ones = {1.0, 1.0};
+            double2_v a_prv = ones, a_mid = ones, u_prv = row_pair(U, r0 - 1), u_mid = row_pair(U, r0);
+            if constexpr (HAS_A) {
+                a_prv = row_pair(A, r0 - 1);
+                a_mid = row_pair(A, r0);
+            }
 #pragma unroll
             for (int i = 0; i < PR; ++i) {
                 const int r = r0 + i;
                 if (r >= N) break;
-                const double2_v a_nxt = row_pair(A, r + 1), u_nxt = row_pair(U, r + 1);
+                double2_v a_nxt = ones;
+                if constexpr (HAS_A) a_nxt = row_pair(A, r + 1);
+                const double2_v u_nxt = row_pair(U, r + 1);
                 if (r > 0 && r < N - 1) {
                     const size_t line = (size_t)r * N;
                     const double2_v f = load_f<NT>(F + line + c);
+                    double2_v s = {0.0, 0.0};
+                    if constexpr (HAS_S) s = load_f<NT>(S + line + c);
                     if (c > 0) {
-                        const Faces fc = faces(a_mid.x, a_nxt.x, a_prv.x, a_mid.y, A[line + cl], sd);
+                        const Faces fc = faces(a_mid.x, a_nxt.x, a_prv.x, a_mid.y, HAS_A ? A[line + cl] : 1.0, centre_sd<HAS_S>(k, s.x));
                         const double d = inv * bracket(fc, u_mid.x, u_nxt.x, u_prv.x, u_mid.y, U[line + cl]) - f.x;
                         acc += d * d;
                     }
                     if (c + 1 < N - 1) {
-                        const Faces fc = faces(a_mid.y, a_nxt.y, a_prv.y, A[line + cr], a_mid.x, sd);
+                        const Faces fc = faces(a_mid.y, a_nxt.y, a_prv.y, HAS_A ? A[line + cr] : 1.0, a_mid.x, centre_sd<HAS_S>(k, s.y));
                         const double d = inv * bracket(fc, u_mid.y, u_nxt.y, u_prv.y, U[line + cr], u_mid.x) - f.y;
                         acc += d * d;
                     }
@@ -287,32 +293,22 @@ __device__ __forceinline__ void resnorm_vc_body(int N, double inv, double sd, co
             }
         }
     }
-    const double s = block_sum(acc);
-    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
-}
-
-// second stage, the code of k_resnorm_finish (which is private to its translation unit): *out = sqrt(sum of the n
-// partials), one block in a fixed order.  wave_sum, block_sum, rim and this body are copies of mg_solve_kernels.hip's: the
-// bit identity of the a == 1 norm holds while the two copies agree (test_unit_coefficient_is_the_constant_solver compares
-// the histories with ==, so a change to either copy alone fails there).
-__device__ __forceinline__ void resnorm_finish_vc_body(const double *__restrict__ part, size_t n, double *__restrict__ out)
-{
-    double acc = 0.0;
-    for (size_t i = threadIdx.x; i < n; i += blockDim.x) acc += part[i];
-    const double s = block_sum(acc);
-    if (threadIdx.x == 0) *out = sqrt(s);
+    const double sum = block_sum(acc);
+    if (threadIdx.x == 0) k.out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 
 // ---------------------------------------------------------------- coarse solve
 // k_gs_relative (mg_solve_kernels.hip) with the operator of the header: ONE workgroup, U and F in LDS (the same dynamic
 // request, 2 N^2 doubles), zero start, colour 0 = (row + col) even then colour 1.  N <= 63 and threads = min(1024,
 // ceil64(N^2)): a thread owns at most GS_PTS = 4 points, the same ones in every loop, and keeps their four face coefficients,
-// d and q in registers from before the first iteration on -- the coefficient is read from memory once.
+// d and q in registers from before the first iteration on -- the coefficient and the reaction term are read from memory once.
+// OPT_A: Ag may be null (a = 1 through the same expressions); false: Ag is read without a look at it.
 constexpr int GS_PTS = 4;
+template <bool OPT_A, bool HAS_S>
 __device__ __forceinline__ void gs_relative_vc_body(int N, double h2, double inv, double sd, const double *__restrict__ Ag,
-                                                    double *__restrict__ Ug, const double *__restrict__ Fg, double atol,
-                                                    double rtol, int max_iters, int *__restrict__ state,
-                                                    double *__restrict__ err_out)
+                                                    const double *__restrict__ Sg, double *__restrict__ Ug,
+                                                    const double *__restrict__ Fg, double atol, double rtol, int max_iters,
+                                                    int *__restrict__ state, double *__restrict__ err_out)
 {
     extern __shared__ __align__(16) double lds[];
     __shared__ double s_val;
@@ -337,7 +333,9 @@ __device__ __forceinline__ void gs_relative_vc_body(int N, double h2, double inv
             if (!rim(r, c, N)) {
                 acc = acc + fabs(f);
                 colour_of[j] = (r + c) & 1;
-                fc[j] = faces(Ag[p], Ag[p + N], Ag[p - N], Ag[p + 1], Ag[p - 1], sd);
+                double sdp = sd;
+                if constexpr (HAS_S) sdp = sd + Sg[p] * h2;
+                fc[j] = !OPT_A || Ag ? faces(Ag[p], Ag[p + N], Ag[p - N], Ag[p + 1], Ag[p - 1], sdp) : faces(1.0, 1.0, 1.0, 1.0, 1.0, sdp);
                 qc[j] = 1.0 / fc[j].d;
             }
         }
@@ -425,10 +423,6 @@ __device__ __forceinline__ void coef_check_body(const double *__restrict__ A, si
     }
     if (bad) *flag = 1;
 }
-
-inline dim3 grid_rows(int N) { return dim3((N + TB - 1) / TB, (N + ROWS_PB - 1) / ROWS_PB); }
-inline bool use_pairs(int N) { return N % 2 == 0 && N >= PAIR_MIN_N; }
-inline dim3 grid_pairs(int N) { return dim3((N / 2 + TB - 1) / TB, (N + PR - 1) / PR); }
 
 }  // namespace
 

@@ -23,25 +23,26 @@ namespace k {
 
 namespace {
 
+// (the `_vc` kernels: a coefficient, no reaction term -- HAS_A = true, HAS_S = false)
 template <bool ZERO_IN, bool PAIR, bool NT>
 __global__ __launch_bounds__(TB) void k_wjacobi_vc(VcArgs k)
 {
-    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT>(k);
-    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP>(k);
+    if constexpr (PAIR) vc_pairs<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, NT, true, false>(k);
+    else vc_cols<ZERO_IN ? OP_SWEEP_ZERO : OP_SWEEP, true, false>(k);
 }
 
 // (the pair form is non-temporal at every size, see vc_pairs: no NT parameter)
 template <bool PAIR>
 __global__ __launch_bounds__(TB) void k_residual_vc(VcArgs k)
 {
-    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true>(k);
-    else vc_cols<OP_RESIDUAL>(k);
+    if constexpr (PAIR) vc_pairs<OP_RESIDUAL, true, true, false>(k);
+    else vc_cols<OP_RESIDUAL, true, false>(k);
 }
 
 template <bool HAS_A>
 __global__ __launch_bounds__(TB) void k_apply_vc(VcArgs k)
 {
-    vc_cols<OP_APPLY, HAS_A>(k);
+    vc_cols<OP_APPLY, HAS_A, false>(k);
 }
 
 template <bool PAIR, bool NT>
@@ -49,12 +50,12 @@ __global__ __launch_bounds__(TB) void k_resnorm_vc(int N, double inv, double sd,
                                                    const double *__restrict__ U, const double *__restrict__ F,
                                                    double *__restrict__ part)
 {
-    resnorm_vc_body<PAIR, NT>(N, inv, sd, A, U, F, part);
+    resnorm_vc_body<PAIR, NT, true, false>(VcArgs{N, 0.0, inv, sd, 0.0, A, U, F, part, +1});
 }
 
 __global__ __launch_bounds__(1024) void k_resnorm_finish_vc(const double *__restrict__ part, size_t n, double *__restrict__ out)
 {
-    resnorm_finish_vc_body(part, n, out);
+    resnorm_finish_body(part, n, out);
 }
 
 __global__ __launch_bounds__(1024) void k_gs_relative_vc(int N, double h2, double inv, double sd, const double *__restrict__ Ag,
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(1024) void k_gs_relative_vc(int N, double h2, doubl
                                                          double rtol, int max_iters, int *__restrict__ state,
                                                          double *__restrict__ err_out)
 {
-    gs_relative_vc_body(N, h2, inv, sd, Ag, Ug, Fg, atol, rtol, max_iters, state, err_out);
+    gs_relative_vc_body<false, false>(N, h2, inv, sd, Ag, nullptr, Ug, Fg, atol, rtol, max_iters, state, err_out);
 }
 
 __global__ __launch_bounds__(TB) void k_coef_coarsen(int N, const double *__restrict__ Af, int M, double *__restrict__ Ac,
@@ -83,28 +84,16 @@ void wjacobi_vc(hipStream_t s, int N, double dx2, double sd, double omega, const
                 double *out)
 {
     const VcArgs k{N, dx2, 0.0, sd, omega, A, in, F, out, +1};
-    const dim3 b(TB);
-    if (use_pairs(N)) {
-        const dim3 g = grid_pairs(N);
-        const bool nt = N >= NT_MIN_N;
-        if (!in) {
-            if (nt) hipLaunchKernelGGL((k_wjacobi_vc<true, true, true>), g, b, 0, s, k);
-            else hipLaunchKernelGGL((k_wjacobi_vc<true, true, false>), g, b, 0, s, k);
-        } else {
-            if (nt) hipLaunchKernelGGL((k_wjacobi_vc<false, true, true>), g, b, 0, s, k);
-            else hipLaunchKernelGGL((k_wjacobi_vc<false, true, false>), g, b, 0, s, k);
-        }
-        return;
-    }
-    if (!in) hipLaunchKernelGGL((k_wjacobi_vc<true, false, false>), grid_rows(N), b, 0, s, k);
-    else hipLaunchKernelGGL((k_wjacobi_vc<false, false, false>), grid_rows(N), b, 0, s, k);
+    dispatch_form(N, true, [&](auto pair, auto nt, auto, dim3 g) {
+        if (!in) hipLaunchKernelGGL((k_wjacobi_vc<true, pair(), nt()>), g, dim3(TB), 0, s, k);
+        else hipLaunchKernelGGL((k_wjacobi_vc<false, pair(), nt()>), g, dim3(TB), 0, s, k);
+    });
 }
 
 void residual_vc(hipStream_t s, int N, double inv, double sd, const double *A, const double *U, const double *F, double *D, int sign)
 {
     const VcArgs k{N, 0.0, inv, sd, 0.0, A, U, F, D, sign};
-    if (use_pairs(N)) hipLaunchKernelGGL(k_residual_vc<true>, grid_pairs(N), dim3(TB), 0, s, k);
-    else hipLaunchKernelGGL(k_residual_vc<false>, grid_rows(N), dim3(TB), 0, s, k);
+    dispatch_form(N, true, [&](auto pair, auto, auto, dim3 g) { hipLaunchKernelGGL(k_residual_vc<pair()>, g, dim3(TB), 0, s, k); });
 }
 
 void apply_vc(hipStream_t s, int N, double inv, double sd, const double *A, const double *U, double *out)
@@ -118,12 +107,9 @@ void resnorm_vc(hipStream_t s, int N, double inv, double sd, const double *A, co
                 double *out)
 {
     const size_t np = resnorm_partials(N);   // (the same partition as the constant norm)
-    if (use_pairs(N)) {
-        if (N >= NT_MIN_N) hipLaunchKernelGGL((k_resnorm_vc<true, true>), grid_pairs(N), dim3(TB), 0, s, N, inv, sd, A, U, F, part);
-        else hipLaunchKernelGGL((k_resnorm_vc<true, false>), grid_pairs(N), dim3(TB), 0, s, N, inv, sd, A, U, F, part);
-    } else {
-        hipLaunchKernelGGL((k_resnorm_vc<false, false>), grid_rows(N), dim3(TB), 0, s, N, inv, sd, A, U, F, part);
-    }
+    dispatch_form(N, true, [&](auto pair, auto nt, auto, dim3 g) {
+        hipLaunchKernelGGL((k_resnorm_vc<pair(), nt()>), g, dim3(TB), 0, s, N, inv, sd, A, U, F, part);
+    });
     hipLaunchKernelGGL(k_resnorm_finish_vc, dim3(1), dim3(1024), 0, s, part, np, out);
 }
 

@@ -94,7 +94,7 @@ def _block_sum(v):
 
 def engine_norm(D):
     """sqrt of the sum of D^2 over the interior in the partition and the order of the device norm (csrc/mg_varcoef_impl.h:
-    resnorm_vc_body, resnorm_finish_vc_body).  D: N x N with the residual inside; the rim is not read."""
+    resnorm_vc_body, resnorm_finish_body).  D: N x N with the residual inside; the rim is not read."""
     N = D.shape[0]
     sq = np.zeros((N, N))
     sq[1:-1, 1:-1] = D[1:-1, 1:-1] * D[1:-1, 1:-1]
